@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- images/s of the x4 SR forward path on N MI355X (default: IMDN fp32, 32 x 256x256 -> 1024x1024).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+      --dump-outputs DIR: after the timed steps, what the last one returned (rank 0) goes to DIR/sr_<k>.npy, see dump_outputs()
       N > 1 works both ways: under `python -m torch.distributed.run ... bench.py --gpus N ...` (RANK / LOCAL_RANK /
       WORLD_SIZE / MASTER_* from the environment) and as a plain `python bench.py --gpus N`, which re-executes itself
       under torch.distributed.run on 127.0.0.1 with N ranks.
@@ -346,6 +347,34 @@ def measure_other_config(spec, device, budget_s=1.2):
                                            "frac_of_hbm_peak", "hbm_copy_kernel_gbs") if k in r}}
 
 
+DUMP_BYTES = 60_000_000         # --dump-outputs: float32 values written in all (the files stay below 64 MB with their headers)
+
+
+def dump_outputs(ys, out_dir):
+    """--dump-outputs: the SR tensors one timed step returned, one out_dir/sr_<k>.npy (float32) per forward in step order.  An output
+    above its share of DUMP_BYTES is written as a fixed sample of its flattened elements instead: one element out of every `stride`
+    consecutive ones, at an offset drawn from numpy's default_rng(0) -- the same positions in every run with the same arguments, so two
+    builds compare element for element.  Returns what was written, per file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(1, len(ys))
+    info = {}
+    for k, y in enumerate(ys):
+        name, n = f"sr_{k:03d}", y.numel()
+        if n <= cap:
+            a, how = y.float().cpu().numpy(), "all"
+        else:
+            stride = -(-n // cap)
+            starts = np.arange(0, n, stride)
+            idx = starts + np.random.default_rng(0).integers(0, np.minimum(stride, n - starts))
+            a = y.reshape(-1)[torch.from_numpy(idx).to(y.device)].float().cpu().numpy()
+            how = f"{len(idx)} of {n} flat elements: one per {stride}, offsets from numpy default_rng(0)"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(y.shape), "written": how}
+    return info
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -391,7 +420,13 @@ def parse_args():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="rendezvous + timing reduction only (gloo on CPU, NO forward, not a measurement): lets the N > 1 "
                          "launch logic be tested on a box without GPUs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one (rank 0) as DIR/sr_<k>.npy, float32, one per forward "
+                         "in step order, at most 64 MB in all: a larger output as a fixed sample of its elements (bench.dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -513,25 +548,29 @@ def main():
     events_after = not args.no_kernel_events
 
     def step(spread=True):
-        y = None
+        """one step; returns the outputs of its forwards, in order"""
+        ys = []
         if streams is None or not spread:
             for i in my_items:
-                y = model(xs[i % len(xs)])
+                ys.append(model(xs[i % len(xs)]))
         else:
             for k, i in enumerate(my_items):
                 with torch.cuda.stream(streams[k % nstreams]):
-                    y = model(xs[i % len(xs)])
-        return y
+                    ys.append(model(xs[i % len(xs)]))
+        return ys
 
+    dumped = None
     with torch.no_grad():
         for _ in range(args.warmup):
-            y = step()
+            ys = step()
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            y = step()
+            ys = step()
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(ys, args.dump_outputs)
         instrumented_ms = None
         if events_after:
             step(False)                    # the default stream's context: plans, workspace
@@ -546,7 +585,7 @@ def main():
             instrumented_ms = (time.perf_counter() - t1) / args.steps * 1e3
     if my_items:
         hl, wl_ = shapes[my_items[-1] % len(shapes)]
-        assert tuple(y.shape) == (xs[my_items[-1] % len(xs)].shape[0], 3, 4 * hl, 4 * wl_)
+        assert tuple(ys[-1].shape) == (xs[my_items[-1] % len(xs)].shape[0], 3, 4 * hl, 4 * wl_)
     elapsed, recs = reduce_elapsed(elapsed, imgs_per_step * args.steps)
     seen = [r["rank"] for r in recs]
     per_image = None
@@ -611,6 +650,8 @@ def main():
             "model_frac_of_mfma_peak": None if roofline is None else round(exec_per_step / (elapsed / args.steps) / 1e12 / peak, 4),
             "roofline": roofline,
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if world == 1 and args.b1_latency:
             # the reference's own semantics (test_demo.py:416-433: one image per forward), outside the timed region
             with torch.no_grad():

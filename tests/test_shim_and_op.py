@@ -96,45 +96,20 @@ def test_forward_is_a_registered_custom_op_with_fake_impl():
         assert tuple(r(torch.empty(1, 3, 33, 21)).shape) == (1, 3, 132, 84)
 
 
-REF_DEMO = "/root/reference/test_demo.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_DEMO), reason="authoring container only: parses the reference's test_demo.py")
 def test_every_name_test_demo_uses_resolves_in_the_shim():
-    """ast-parse the reference's test_demo.py (never imported, never copied): every `util.<name>` / `utils_logger.<name>`
-    attribute it touches, every name it imports from utils.model_summary, and the `from models... import ...` lines of ids
-    -1 / 0 / 4 / 18 (+ riders 6, 8, 22, 26, 40) must resolve in shim/ with a compatible call signature
-    (test_demo.py:8-10, 17-30, 52-58, 150-157, 411-465)."""
-    import ast
+    """What the reference's test_demo.py uses (tests/golden/demo_calls.json: ast-parsed by tools/gen_golden_demo_calls.py, names
+    and call shapes only): every `util.<name>` / `utils_logger.<name>` attribute it touches, every name it imports from
+    utils.model_summary, and the `from models... import ...` lines of ids -1 / 0 / 4 / 18 (+ riders 6, 8, 22, 26, 40) must
+    resolve in shim/ with a compatible call signature (test_demo.py:8-10, 17-30, 52-58, 150-157, 411-465)."""
     import inspect
-    tree = ast.parse(open(REF_DEMO).read())
-    aliases = {}                                         # local alias -> shim module
-    from_summary = []
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.module == "utils":
-            for a in node.names:
-                aliases[a.asname or a.name] = "utils." + a.name
-        if isinstance(node, ast.ImportFrom) and node.module == "utils.model_summary":
-            from_summary += [a.name for a in node.names]
+    demo = json.load(open(os.path.join(GOLD, "demo_calls.json")))
+    aliases = demo["utils_aliases"]                      # local alias -> shim module
+    from_summary = demo["summary_imports"]
     assert aliases == {"utils_logger": "utils.utils_logger", "util": "utils.utils_image"}, aliases
-    used = {}                                            # (alias, attr) -> list of ast.Call (for the signature check)
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in aliases:
-            used.setdefault((node.value.id, node.attr), [])
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name) \
-                and node.func.value.id in aliases:
-            used.setdefault((node.func.value.id, node.func.attr), []).append(node)
+    used = {(a["alias"], a["attr"]): a["calls"] for a in demo["attributes"]}     # (alias, attr) -> call sites (positional count, keywords)
     assert ("util", "mkdir") in used and ("util", "imsave") in used and ("utils_logger", "logger_info") in used
     # registry entries this engine implements: model_id -> (module, class) from the select_model body
-    sel = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "select_model")
-    model_imports = {}
-    for node in ast.walk(sel):
-        if isinstance(node, ast.If) and isinstance(node.test, ast.Compare) and isinstance(node.test.left, ast.Name) \
-                and node.test.left.id == "model_id" and isinstance(node.test.comparators[0], (ast.Constant, ast.UnaryOp)):
-            mid = ast.literal_eval(node.test.comparators[0])
-            for st in node.body:
-                if isinstance(st, ast.ImportFrom):
-                    model_imports[mid] = (st.module, [a.name for a in st.names])
+    model_imports = {int(mid): tuple(v) for mid, v in demo["select_model_imports"].items()}
     want_ids = [-1, 0, 4, 18, 6, 8, 22, 26, 40]
     assert all(i in model_imports for i in want_ids), sorted(model_imports)
     code = ["import importlib, inspect, json", "out = {}"]
@@ -155,7 +130,7 @@ def test_every_name_test_demo_uses_resolves_in_the_shim():
             mod = importlib.import_module(aliases[alias])
             sig = inspect.signature(getattr(mod, attr))
             for c in calls:
-                sig.bind(*[None] * len(c.args), **{k.arg: None for k in c.keywords})
+                sig.bind(*[None] * c["nargs"], **{k: None for k in c["keywords"]})
     finally:
         sys.path.remove(SHIM)
         for m in [m for m in sys.modules if m == "utils" or m.startswith("utils.")]:
