@@ -44,8 +44,11 @@ typedef enum esr_act { ESR_ACT_NONE = 0, ESR_ACT_LRELU = 1, ESR_ACT_RELU = 2, ES
 
 /* where the residual enters relative to the activation:
  *   PRE : act(conv(x) + r)   RFDB  rfdn_baseline/block.py:151 ; ShortcutBlock basicblock.py:197-199 (act none)
- *   POST: act(conv(x)) + r   RLFB  team04_rlfn.py:117-119 */
-typedef enum esr_res { ESR_RES_NONE = 0, ESR_RES_PRE_ACT = 1, ESR_RES_POST_ACT = 2 } esr_res;
+ *   POST: act(conv(x)) + r   RLFB  team04_rlfn.py:117-119
+ *   GATE: sigmoid(conv(x)) * r, sigmoid(v) = 1 / (1 + exp(-v)) in fp32   FMEN's HFAB team03_fmen.py:67-73 (ABI v12, additive).
+ *         Requires act == ESR_ACT_NONE (ESR_ERR_UNSUPPORTED otherwise); esr_conv2d_f32 on conv_f32_kernel (fp32, NHWC output) and
+ *         conv_s16_kernel (16-bit storage, the gate operand staged from HBM like a residual); no fused tail / post chain / hi + lo */
+typedef enum esr_res { ESR_RES_NONE = 0, ESR_RES_PRE_ACT = 1, ESR_RES_POST_ACT = 2, ESR_RES_GATE = 3 } esr_res;
 
 /* arithmetic of the matrix products (accumulation is always fp32):
  *   F32          exact fp32 MFMA (v_mfma_f32_16x16x4_f32); storage must be ESR_STORE_F32 (or the NCHW head of a 16-bit network)
@@ -464,6 +467,13 @@ int esr_channel_attention_f32(const esr_ca_desc* d, void* hip_stream);
  * registers (rlfb_chain_kernel, csrc/esr_chain.hip).  Results are bit-identical to the three esr_conv2d_f32 launches it replaces.
  * wpacked[i] = esr_pack_conv_s16 (ksize 3) of layer i, post_wpacked / post2_wpacked = esr_pack_post_s16.  esr_conv_chain_supported() tells
  * whether a descriptor's shape has a kernel (today: three layers over 33..48 channels, a first 1x1 of 33..48 and a second of <= 16 outputs).
+ *
+ * res_mode ESR_RES_GATE -- FMEN's HFAB (team03_fmen.py:60-73) with one BasicBlock: n_layers == 4, cin == cout in 33..64, cmid <= 16,
+ * act == ESR_ACT_LRELU (slope from the descriptor), post_wpacked == post2_wpacked == NULL:
+ *     t_1 = act(squeeze(in)), t_2 = act(conv(t_1)), t_3 = act(conv(t_2)),  post_out = sigmoid(excitate(t_3)) * in
+ * (hfab_kernel, csrc/esr_hfab.hip: one block per 16 x 16 output tile, `in` and its 4-pixel halo staged once, t_i in LDS).  post_cout
+ * channels are stored (cout <= post_cout <= round_up(cout, 16), e.g. the whole pitch 56 of nf = 50); channels of `in` at and beyond cin
+ * are never read.  Bit-identical to the four esr_conv2d_f32 launches it replaces.
  */
 #define ESR_CHAIN_MAX_LAYERS 4
 typedef struct esr_chain_desc {
@@ -472,7 +482,7 @@ typedef struct esr_chain_desc {
     int32_t cin, cmid, cout;    /* logical channels: in -> cmid -> ... -> cmid -> cout */
     int32_t act;                /* esr_act of every 3x3 layer */
     float   slope;
-    int32_t res_mode;           /* esr_res of the LAST layer (residual = `in`) */
+    int32_t res_mode;           /* esr_res of the LAST layer (residual = `in`): ESR_RES_POST_ACT (RLFB) | ESR_RES_GATE (HFAB) */
     int32_t storage;            /* esr_storage of in / post_out / post2_out */
     int32_t compute;            /* esr_compute: the storage's type */
     esr_view in;

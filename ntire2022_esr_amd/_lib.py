@@ -15,7 +15,7 @@ ESR_OK = 0
 STATUS = {0: "ESR_OK", -1: "ESR_ERR_BAD_ARG", -2: "ESR_ERR_UNSUPPORTED", -3: "ESR_ERR_LAUNCH", -4: "ESR_ERR_TOO_SMALL"}
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_GELU = 0, 1, 2, 3
-RES_NONE, RES_PRE_ACT, RES_POST_ACT = 0, 1, 2
+RES_NONE, RES_PRE_ACT, RES_POST_ACT, RES_GATE = 0, 1, 2, 3                  # RES_GATE: sigmoid(conv) * res (FMEN's HFAB)
 NHWC, NCHW_IN, NCHW_SHUFFLE4 = 0, 1, 2
 BLOCKED_IN, BLOCKED_OUT1, BLOCKED_OUT0, BLOCKED_RES = 1, 2, 4, 8          # esr_conv_desc.blocked8 bits (ABI v6 / v9)
 HILO_IN, HILO_RES, HILO_OUT = 1, 2, 4                                     # esr_conv_desc.hilo bits (ABI v10)

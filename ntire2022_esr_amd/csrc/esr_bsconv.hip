@@ -403,6 +403,7 @@ extern "C" int esr_bsconv_f32(const esr_bsconv_desc* d, void* hip_stream)
     if (!d || !d->in.ptr || !d->out.ptr || !d->pw_packed || !d->dw_packed) return ESR_ERR_BAD_ARG;
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->c <= 0) return ESR_ERR_BAD_ARG;
     if (d->cin > 64 || d->c > 64) return ESR_ERR_UNSUPPORTED;
+    if (d->res_mode == ESR_RES_GATE) return ESR_ERR_UNSUPPORTED;           // the gate epilogue: esr_conv2d_f32 only
     const bool s16 = d->storage == ESR_STORE_BF16 || d->storage == ESR_STORE_F16;
     if (d->storage != ESR_STORE_F32 && !s16) return ESR_ERR_BAD_ARG;
     const int cin_phys = esr_round_up(d->cin, 8), cp = esr_round_up(d->c, 4);

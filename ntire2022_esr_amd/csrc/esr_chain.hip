@@ -701,6 +701,7 @@ extern "C" {
 
 int esr_conv_chain_supported(const esr_chain_desc* d)
 {
+    if (d && d->res_mode == ESR_RES_GATE) return esr_hfab_supported(d);      // FMEN's HFAB: hfab_kernel (esr_hfab.hip)
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
     if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
     if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
@@ -720,6 +721,7 @@ int esr_conv_chain_supported(const esr_chain_desc* d)
 
 int esr_conv_chain_s16(const esr_chain_desc* d, void* hip_stream)
 {
+    if (d && d->res_mode == ESR_RES_GATE) return esr_hfab_s16(d, hip_stream);
     if (!d || !d->in.ptr || !d->post_out.ptr || !d->post2_out.ptr) return ESR_ERR_BAD_ARG;
     for (int i = 0; i < 3; ++i)
         if (!d->wpacked[i]) return ESR_ERR_BAD_ARG;

@@ -761,6 +761,7 @@ int esr_dwconv3x3_f32(const esr_conv_desc* d, void* hip_stream)
     if (!d || !d->in.ptr || !d->out0.ptr || !d->wpacked) return ESR_ERR_BAD_ARG;
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cin != d->cout || d->ksize != 3) return ESR_ERR_BAD_ARG;
     if (d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;
+    if (d->res_mode == ESR_RES_GATE) return ESR_ERR_UNSUPPORTED;           // the gate epilogue: esr_conv2d_f32 only
     const int cp = esr_round_up(d->cin, 4);
     if ((d->in.pitch & 3) || (d->in.coff & 3) || d->in.coff + cp > d->in.pitch) return ESR_ERR_BAD_ARG;
     if ((d->out0.pitch & 3) || (d->out0.coff & 3) || d->out0.coff + cp > d->out0.pitch) return ESR_ERR_BAD_ARG;

@@ -150,6 +150,10 @@ __device__ __forceinline__ void epilogue_nhwc_checked(const ConvK& p, f32x4 (&ac
             v.x = act_any(v.x, p.act, p.slope); v.y = act_any(v.y, p.act, p.slope);
             v.z = act_any(v.z, p.act, p.slope); v.w = act_any(v.w, p.act, p.slope);
             if (p.res_mode == ESR_RES_POST_ACT) v += rv;
+            if (p.res_mode == ESR_RES_GATE) {           // (act none: the host requires it)
+                v.x = esr_sigmoid(v.x) * rv.x; v.y = esr_sigmoid(v.y) * rv.y;
+                v.z = esr_sigmoid(v.z) * rv.z; v.w = esr_sigmoid(v.w) * rv.w;
+            }
             *reinterpret_cast<f32x4*>(ybase + (size_t)(pix * ypitch)) = v;
         }
     }
@@ -197,6 +201,10 @@ __device__ __forceinline__ void epilogue_nhwc_fast(const ConvK& p, f32x4 (&acc)[
             f32x4 o;
             if (RES == ESR_RES_PRE_ACT) o = act4<ACT>(v[i] + rv[r][i], p.slope);
             else if (RES == ESR_RES_POST_ACT) o = act4<ACT>(v[i], p.slope) + rv[r][i];
+            else if (RES == ESR_RES_GATE) {
+                o.x = esr_sigmoid(v[i].x) * rv[r][i].x; o.y = esr_sigmoid(v[i].y) * rv[r][i].y;
+                o.z = esr_sigmoid(v[i].z) * rv[r][i].z; o.w = esr_sigmoid(v[i].w) * rv[r][i].w;
+            }
             else o = act4<ACT>(v[i], p.slope);
             const size_t pu = (size_t)(pix00 + r * p.W + 4 * i);                            // uniform
             if (!has_split) {
@@ -218,6 +226,7 @@ __device__ __forceinline__ void epilogue_nhwc_fast_res(const ConvK& p, f32x4 (&a
 {
     if (p.res_mode == ESR_RES_NONE) epilogue_nhwc_fast<ACT, ESR_RES_NONE, NT, Y1BLK>(p, acc, scr, n, x0, y0, wv, lane);
     else if (p.res_mode == ESR_RES_PRE_ACT) epilogue_nhwc_fast<ACT, ESR_RES_PRE_ACT, NT, Y1BLK>(p, acc, scr, n, x0, y0, wv, lane);
+    else if (ACT == ESR_ACT_NONE && p.res_mode == ESR_RES_GATE) epilogue_nhwc_fast<ACT, ESR_RES_GATE, NT, Y1BLK>(p, acc, scr, n, x0, y0, wv, lane);
     else epilogue_nhwc_fast<ACT, ESR_RES_POST_ACT, NT, Y1BLK>(p, acc, scr, n, x0, y0, wv, lane);
 }
 
@@ -1029,6 +1038,9 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
     if (!in_nchw && d->in_layout != ESR_NHWC) return ESR_ERR_BAD_ARG;
     const bool store16 = d->storage == ESR_STORE_BF16 || d->storage == ESR_STORE_F16;
     if (d->storage != ESR_STORE_F32 && !store16) return ESR_ERR_BAD_ARG;
+    // sigmoid(conv) * res (FMEN's HFAB): the plain NHWC epilogues of conv_f32_kernel / conv_s16_kernel only
+    if (d->res_mode == ESR_RES_GATE && (d->act != ESR_ACT_NONE || d->out_layout != ESR_NHWC || d->tail_wpacked || d->post_wpacked || d->hilo))
+        return ESR_ERR_UNSUPPORTED;
     if (store16 && !in_nchw) return esr_conv2d_s16(d, hip_stream);         // 16-bit storage: esr_s16.hip
     if (d->compute != ESR_COMPUTE_F32) return ESR_ERR_BAD_ARG;              // fp32 MFMA from here on (incl. the NCHW head)
     if (d->border_bias) return ESR_ERR_UNSUPPORTED;                        // border table: conv_s16_kernel only

@@ -15,6 +15,10 @@ static inline int esr_round_up(int v, int m) { return (v + m - 1) / m * m; }
 int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream);
 int esr_s16_block_waves(const esr_conv_desc* d);      // 4: two 4-wave blocks per CU (16 x 16 tiles), 8: one 8-wave block (16 x 32)
 
+// esr_hfab.hip: FMEN's HFAB as one launch (esr_conv_chain_s16 with res_mode ESR_RES_GATE; esr_conv_chain_supported asks the first)
+int esr_hfab_supported(const esr_chain_desc* d);
+int esr_hfab_s16(const esr_chain_desc* d, void* hip_stream);
+
 // esr_wino.hip: Winograd F(2x2, 3x3) fp32 convolution (called by esr_conv2d_f32 when d->wino_wpacked is set and the shape qualifies)
 int esr_conv2d_wino(const esr_conv_desc* d, void* hip_stream);
 
@@ -35,6 +39,13 @@ __device__ __forceinline__ float esr_lone(float v)
 {
     asm("" : "+v"(v));
     return v;
+}
+
+// ESR_RES_GATE: y = sigmoid(v) * r.  The ONE expression of the sigmoid: every kernel that implements the gate (conv_f32_kernel,
+// conv_s16_kernel, hfab_kernel) calls this, so the fused HFAB is bit-identical to its per-layer launches
+__device__ __forceinline__ float esr_sigmoid(float v)
+{
+    return 1.f / (1.f + expf(-v));
 }
 
 // GELU of the 16-bit storage modes (the scalar definition conv_s16_kernel's packed version follows bit for bit; accuracy and

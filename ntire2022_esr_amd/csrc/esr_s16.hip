@@ -695,6 +695,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_s16_kernel(cons
 #pragma unroll
         for (int i = 0; i < PPW; ++i) dma_piece(i);
         const bool post = KP()->res_mode == ESR_RES_POST_ACT;
+        const bool gate = KP()->res_mode == ESR_RES_GATE;
+        if (gate && c == p.nchunks) {
+            // sigmoid(conv) * res (ESR_RES_GATE, act none): the sigmoid on the accumulators first, the stages below multiply
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+                for (int r = 0; r < RW; ++r) {
+                    f32x4 v = acc[tt][r];
+                    v.x = esr_sigmoid(v.x); v.y = esr_sigmoid(v.y); v.z = esr_sigmoid(v.z); v.w = esr_sigmoid(v.w);
+                    acc[tt][r] = v;
+                }
+        }
         if (post && c == p.nchunks) {
             // act(conv) + res: the activation goes first, on the accumulators (the epilogue then sees slope 1)
             if (act_gelu) {
@@ -717,8 +729,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_s16_kernel(cons
             asm volatile("" : "+s"(cc));      // opaque per tile (see the res_in block of compute)
             if (tt == cc || (HILO && tt + NT == cc)) {             // HILO: stages NT .. 2 NT - 1 carry the residual's low parts
 #pragma unroll
-                for (int r = 0; r < RW; ++r)
-                    acc[tt][r] += unpack4<BF16>(*reinterpret_cast<const uint2*>(sb + c_off + r * (TH * 32)));
+                for (int r = 0; r < RW; ++r) {
+                    const f32x4 rf = unpack4<BF16>(*reinterpret_cast<const uint2*>(sb + c_off + r * (TH * 32)));
+                    if (gate) acc[tt][r] *= rf;
+                    else acc[tt][r] += rf;
+                }
             }
         }
         if (last && act_gelu && !post) gelu_inplace();
@@ -1335,6 +1350,11 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     if (d->compute != (bf16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return ESR_ERR_BAD_ARG;   // operand type = storage type
     if (d->in_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;                                  // the NCHW head runs on conv_f32_kernel
     if (d->blocked8) return ESR_ERR_UNSUPPORTED;                                               // an fp32 feature
+    // ESR_RES_GATE: conv_s16_kernel's residual stages carry the gate operand.  Every specialised kernel's predicate (conv48r / conv48rp / conv48rq /
+    // conv64r / conv64rq / conv48rl / conv64ml / esdb_r / rfdb_tail) requires no residual, one that is the input (pre-activation) or a pre / post-
+    // activation one, so a gate never reaches them
+    if (d->res_mode == ESR_RES_GATE && (d->act != ESR_ACT_NONE || d->tail_wpacked || d->post_wpacked || d->hilo || d->border_bias || d->out_layout != ESR_NHWC))
+        return ESR_ERR_UNSUPPORTED;
     if (d->tail_wpacked) return rfdb_tail_takes(d) ? run_rfdb_tail(d, bf16, static_cast<hipStream_t>(hip_stream)) : ESR_ERR_UNSUPPORTED;
     const bool post = d->post_wpacked != nullptr;
     if (d->border_bias && d->out_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;

@@ -955,6 +955,7 @@ inline size_t wn_index(int nhalves, int slot, int pos, int o)
 int esr_wino_supported(const esr_conv_desc* d)
 {
     if (!d || d->ksize != 3 || d->in_layout != ESR_NHWC) return 0;
+    if (d->res_mode == ESR_RES_GATE) return 0;                     // the gate epilogue: conv_f32_kernel
     if (d->out_layout == ESR_NCHW_SHUFFLE4) {                      // the network's last convolution: no residual, no split
         if ((d->cout & 15) || d->res_mode != ESR_RES_NONE || (d->split > 0 && d->split < d->cout) || (d->blocked8 & ESR_BLOCKED_OUT1)) return 0;
     } else if (d->out_layout != ESR_NHWC) return 0;

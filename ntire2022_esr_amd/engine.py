@@ -427,6 +427,20 @@ class Plan:
         del self.ops[mark:]
         self.ops.append(dict(kind="chain", replaces=sub, w=sub[0]["w"], cin=sub[0]["cin"], cout=last["cout"], k=3))
 
+    def hfab(self, mark):
+        """The four 3x3 convolutions appended since `mark = len(plan.ops)` -- FMEN's HFAB with one BasicBlock, x -> squeeze -> conv -> conv ->
+        sigmoid(excitate) * x (team03_fmen.py:60-73) -- as ONE esr_conv_chain_s16 op with res_mode L.RES_GATE (hfab_kernel, 16-bit plans): x is
+        read once, t1 .. t3 stay in LDS.  The conv op dicts stay attached as `replaces` (weights, complexity counters, algorithmic costs); the
+        result is bit-identical to running them one by one."""
+        sub = self.ops[mark:]
+        assert self.esize == 2 and len(sub) == 4 and all(o["kind"] == "conv" and o["k"] == 3 for o in sub)
+        for a, b in zip(sub[:-1], sub[1:]):
+            assert b["src"] is a["dst"] and a["res"] is None and a.get("post") is None and a["act"] == sub[0]["act"]
+        last = sub[-1]
+        assert last["res_mode"] == L.RES_GATE and last["res"] is sub[0]["src"] and last.get("post") is None and isinstance(last["dst"], Buffer)
+        del self.ops[mark:]
+        self.ops.append(dict(kind="chain", gate=True, replaces=sub, w=sub[0]["w"], cin=sub[0]["cin"], cout=last["cout"], k=3))
+
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, post=None, skip_y=False):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [dict(w=<1x1 path>, dst=<view>, cout, act, slope, res=<view>|None, linear=bool), ...] -- one or two 1x1
@@ -508,6 +522,12 @@ class Plan:
                 d.inp = self._view(first["src"], base)
                 for l, so in enumerate(sub):
                     d.wpacked[l] = weights[so["w"] + "#s16"].data_ptr()
+                if o.get("gate"):                                 # HFAB: the gated result goes to post_out, whole pad chunk included
+                    d.post_out = self._view(last["dst"], base)
+                    d.post_cout = min((last["cout"] + 15) // 16 * 16, last["dst"].pitch)
+                    if not L.lib().esr_conv_chain_supported(ctypes.byref(d)):
+                        raise L.EsrError(f"{o['w']}: no HFAB kernel for this shape (the plan should have kept separate ops)")
+                    continue
                 t = last["post"]
                 t2 = t["post2"]
                 pc = min((t["cout"] + 15) // 16 * 16, t["dst"].pitch) if isinstance(t["dst"], Buffer) else t["cout"]    # (whole dense buffer: pad channels too)
@@ -1234,6 +1254,15 @@ class HipSRModel(nn.Module):
                 if pt is not None:
                     wb += 4.0 * o["cout"] * pt["cout"] + (4.0 * pt["cout"] * pt["post2"]["cout"] if pt.get("post2") is not None else 0.0)
                 stored = float(st) + wb
+            elif kind == "chain" and o.get("gate"):  # HFAB in one launch: x read once (also the gate operand), the gated result written once
+                sub = o["replaces"]
+                kern = f"hfab_kernel<{'true' if plan.store == 'bf16' else 'false'}, {(sub[0]['cin'] + 15) // 16}>"
+                flops = sum(2.0 * npix * so["cin_alg"] * so["cout"] * 9 for so in sub)
+                wb = 4.0 * sum(so["cin_alg"] * so["cout"] * 9 for so in sub)
+                rd = float(npix * sub[0]["cin_alg"] * es) + wb
+                wr = float(npix * sub[-1]["cout"] * es)
+                chunk = 16
+                stored = float(npix * es * (_stored_channels(sub[0]["src"], sub[0]["cin"], chunk) + _stored_channels(sub[-1]["dst"], sub[-1]["cout"], chunk))) + wb
             elif kind == "chain":                   # the block's 3x3 chain + its two 1x1s in one launch: the input read once, only the 1x1 results written
                 sub = o["replaces"]
                 kern = f"rlfb_chain_kernel<{plan.store}>"

@@ -173,12 +173,16 @@ def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.
     return (y, yp) if yp2 is None else (y, yp, yp2)
 
 
-def conv_chain(x, weights, biases, post_weight, post_bias, post2_weight, post2_bias, *, act=L.ACT_LRELU, slope=0.05,
-               res_mode=L.RES_POST_ACT, post_act=L.ACT_NONE, cin=None):
+def conv_chain(x, weights, biases, post_weight=None, post_bias=None, post2_weight=None, post2_bias=None, *, act=L.ACT_LRELU, slope=0.05,
+               res_mode=L.RES_POST_ACT, post_act=L.ACT_NONE, cin=None, out=None):
     """esr_conv_chain_s16 (ABI v11): a residual block's chain of 3x3 convolutions in ONE launch on a 16-bit NHWC tensor x [N, H, W, P]
     (RLFB.forward, team04_rlfn.py:109-122): t = x; t = act(conv_i(t)) for all but the last 3x3; u = act(conv_n(t)) + x;
     v = post_act(post_weight . u + post_bias) -> stored; c1 = post2_weight . v_fp32 + post2_bias -> stored.  Returns (v, c1).
-    weights: list of OIHW fp32 3x3 weights, biases: list of fp32 biases (or None)."""
+    weights: list of OIHW fp32 3x3 weights, biases: list of fp32 biases (or None).
+    res_mode=L.RES_GATE is FMEN's HFAB (team03_fmen.py:60-73; four 3x3s, no post weights): t = act(conv_i(t)) for the first three,
+    y = sigmoid(conv_4(t)) * x, returned as an NHWC tensor of x's pitch (or stored into `out`, same geometry); `cin` channels of x are read."""
+    if res_mode == L.RES_GATE:
+        return _hfab(x, weights, biases, act=act, slope=slope, cin=cin, out=out)
     if not x.is_cuda:
         raise L.EsrError("conv_chain: tensors must live on the GPU; there is no CPU fallback")
     st = _STORE_OF[x.dtype]
@@ -210,6 +214,36 @@ def conv_chain(x, weights, biases, post_weight, post_bias, post2_weight, post2_b
     stream = torch.cuda.current_stream(x.device).cuda_stream
     L.check(lib.esr_conv_chain_s16(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_conv_chain_s16")
     return v, c1
+
+
+def _hfab(x, weights, biases, *, act, slope, cin, out):
+    if not x.is_cuda:
+        raise L.EsrError("conv_chain: tensors must live on the GPU; there is no CPU fallback")
+    st = _STORE_OF[x.dtype]
+    if st == "f32":
+        raise L.EsrError("conv_chain: 16-bit storage only")
+    lib = L.lib()
+    n, h, w, pitch = x.shape
+    d = L.ChainDesc()
+    d.n, d.h, d.w, d.n_layers = n, h, w, len(weights)
+    d.cin = weights[0].shape[1] if cin is None else cin
+    d.cmid, d.cout = weights[0].shape[0], weights[-1].shape[0]
+    d.act, d.slope, d.res_mode = act, slope, L.RES_GATE
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x)
+    keep = []
+    for i, (wt, b) in enumerate(zip(weights, biases)):
+        blob = pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device)
+        keep.append(blob)
+        d.wpacked[i] = blob.data_ptr()
+    y = torch.zeros((n, h, w, pitch), dtype=x.dtype, device=x.device) if out is None else out
+    d.post_out = _view(y)
+    d.post_cout = min((d.cout + 15) // 16 * 16, y.shape[-1])      # the pad channels of the last chunk too, as the per-layer store (zeros)
+    if not lib.esr_conv_chain_supported(ctypes.byref(d)):
+        raise L.EsrError("conv_chain: no kernel for this shape (esr_conv_chain_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    L.check(lib.esr_conv_chain_s16(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_conv_chain_s16")
+    return y
 
 
 def _hilo_pair(t, what, strides):
