@@ -16,7 +16,7 @@ through esr_conv_desc.border_bias (a 16-row table indexed by which sides of the 
 import torch
 
 from . import _lib as L
-from .engine import INPUT, OUTPUT, HipSRModel, Planar, pack_apply_post, pack_conv, pack_conv_s16, pack_head_s16
+from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Planar, Post, Tail, pack_apply_post, pack_conv, pack_conv_s16, pack_head_s16
 from .rlfn import FP, _lowres, _pad8
 
 
@@ -173,7 +173,7 @@ class BSRN(HipSRModel):
         # that input: the head for block 1, the previous block's conv_out for the others (one launch and one read of the tensor less)
         apply_out = fuse_d and bplanar and bool(L.lib().esr_esa_apply_post_supported(C, C, dc))
         def first_d(k):
-            return dict(w=f'B{k}.c1_d', dst=cs(0), cout=dc, act=L.ACT_GELU) if fuse_d else None
+            return Post(f'B{k}.c1_d', cs(0), dc, L.ACT_GELU) if fuse_d else None
         if hl:
             plan.conv('fea_conv#bs3', INPUT, fea2, self.in_nc, C, k=3, border='fea_conv#bs3#border', bs_of='fea_conv', post=first_d(1), hilo=L.HILO_OUT)
         elif merged:
@@ -196,7 +196,7 @@ class BSRN(HipSRModel):
                     # fp32 tile; the block's first one (c1_d, of the block input) rides with the producer of the block input (first_d).
                     if j == 1 and not fuse_d:
                         plan.conv(b + 'c1_d', rin, cs(0), C, dc, k=1, counted=False, **g)
-                    nxt = dict(w=b + f'c{j + 1}_d', dst=cs(j), cout=dc, act=L.ACT_GELU) if (j < 3 and fuse_d) else None
+                    nxt = Post(b + f'c{j + 1}_d', cs(j), dc, L.ACT_GELU) if (j < 3 and fuse_d) else None
                     bs3(b + f'c{j}_r', rin, rout, C, C, res=rin, res_mode=L.RES_PRE_ACT, post=nxt, **g)
                     if j < 3 and not fuse_d:
                         plan.conv(b + f'c{j + 1}_d', rout, cs(j), C, dc, k=1, counted=False, **g)
@@ -204,11 +204,11 @@ class BSRN(HipSRModel):
                     # c{j}_d (Linear + GELU) and c{j}_r = BSConvU (+ input, GELU) read the same tensor: one launch, the
                     # pointwise result stays in LDS (team18_bsrn.py:150-163)
                     plan.bsconv(b + f'c{j}_r.pw', b + f'c{j}_r.dw', rin, rout, C, C, res=rin, res_mode=L.RES_PRE_ACT,
-                                distill=dict(w=b + f'c{j}_d', dst=cs(j - 1), cout=dc, act=L.ACT_GELU), **g)
+                                distill=Post(b + f'c{j}_d', cs(j - 1), dc, L.ACT_GELU), **g)
             if fused_tail:
                 bs3(b + 'c4', r1, v, C, dc,
-                    tail=dict(w=b + 'c5#tail', cat=Planar(cat.segs[:3]), cat_c=3 * DP, cat_c_alg=3 * dc, cout=C, mid_act=L.ACT_GELU),
-                    post=dict(w=b + 'esa.conv1', dst=c1, cout=f, act=L.ACT_NONE))
+                    tail=Tail(b + 'c5#tail', Planar(cat.segs[:3]), 3 * DP, 3 * dc, C, L.ACT_GELU),
+                    post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             elif merged:
                 bs3(b + 'c4', r1, cs(3), C, dc, **g)
             else:
@@ -218,7 +218,7 @@ class BSRN(HipSRModel):
             elif plan.esize == 2 and (C + 15) // 16 in (3, 4) and f <= 16:
                 # 16-bit storage: esa.conv1 rides in c5's epilogue on the fp32 tile (one launch less per block)
                 plan.conv(b + 'c5', cat, v, 4 * DP if merged else 4 * dc, C, k=1, counted=False, cin_alg=4 * dc,
-                          post=dict(w=b + 'esa.conv1', dst=c1, cout=f, act=L.ACT_NONE))
+                          post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
                 plan.conv(b + 'c5', cat, v, 4 * DP if merged else 4 * dc, C, k=1, counted=False, cin_alg=4 * dc)
                 plan.conv(b + 'esa.conv1', v, c1, C, f, k=1, counted=False)
@@ -233,17 +233,16 @@ class BSRN(HipSRModel):
             plan.dwconv(b + 'esa.conv3_.dw', lt, lb, f, hw=lo)
             if self.fuse_esa_lowres:
                 # the eight launches above as one op of two (halo recompute; only the pooled map reaches memory)
-                ga = g.get("act", L.ACT_NONE)
                 plan.esa_lowres(mark, c1, la, lb, f, b + 'esa.conv2',
-                                [dict(kind=1, act=ga, w=b + 'esa.conv_max.pw', w_dw=b + 'esa.conv_max.dw'),
-                                 dict(kind=1, act=ga, w=b + 'esa.conv3.pw', w_dw=b + 'esa.conv3.dw'),
-                                 dict(kind=1, act=L.ACT_NONE, w=b + 'esa.conv3_.pw', w_dw=b + 'esa.conv3_.dw')])
+                                [EsaLayer(1, L.ACT_GELU, b + 'esa.conv_max.pw', b + 'esa.conv_max.dw'),
+                                 EsaLayer(1, L.ACT_GELU, b + 'esa.conv3.pw', b + 'esa.conv3.dw'),
+                                 EsaLayer(1, L.ACT_NONE, b + 'esa.conv3_.pw', b + 'esa.conv3_.dw')])
             out = bcat.seg(k - 1) if bplanar else bcat[(k - 1) * C:k * C]
             if apply_out:
                 # conv_out (. cw, + block input) and the next block's c1_d in the ESA apply launch: the attention output never reaches memory
-                chain = [dict(w=b + 'conv_out', dst=out, cout=C, act=L.ACT_NONE, res=src)]
+                chain = [Post(b + 'conv_out', out, C, res=src)]
                 if k < nb:
-                    chain.append(dict(w=f'B{k + 1}.c1_d', dst=cs(0), cout=dc, act=L.ACT_GELU))
+                    chain.append(Post(f'B{k + 1}.c1_d', cs(0), dc, L.ACT_GELU))
                 plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lb, out, C, f, post=chain, skip_y=True)
             else:
                 plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lb, u, C, f)
@@ -267,18 +266,19 @@ class BSRN(HipSRModel):
         counted by linear_flops_counter_hook (model_summary.py:305-312), which for a 4-D NHWC input adds
         input.shape[0]*input.shape[1]*output.shape[1] = 1*H*H -- the reference's own quirk, reproduced so the
         table matches (true MACs are 9.43 G); Linear outputs are not 'activations'."""
-        hw = o.get("hw")
-        h, w = (hw if hw else (plan.h, plan.w))
-        if o["kind"] == "dw":
-            return 9 * o["cin"] * plan.n * h * w, o["cout"] * plan.n * h * w, 1
-        if o["kind"] == "bs":                                             # depthwise Conv2d + 1 or 2 Linear calls in one launch
-            nlin = 1 + (o["distill"] is not None)
-            return 9 * o["cout"] * plan.n * h * w + nlin * plan.n * h * h, o["cout"] * plan.n * h * w, 1
-        if o["kind"] == "conv" and o.get("bs_of") is not None:           # a BSConvU run as a dense 3x3: one Linear + one depthwise Conv2d
-            nlin = 1 + (o.get("post") is not None) + (o.get("tail") is not None)     # (+ the Linear(s) riding in its launch)
-            return 9 * o["cout"] * plan.n * h * w + nlin * plan.n * h * h, o["cout"] * plan.n * h * w, 1
-        if o["kind"] == "conv" and not o.get("counted", True):
-            return (1 + (o.get("post") is not None)) * plan.n * h * h, 0, 0      # a Linear call (+ the one in its epilogue)
-        if o["kind"] == "apply":
-            return (2 + len(o.get("post") or ())) * plan.n * plan.h * plan.h, 0, 0       # conv_f and conv4 are Linear here (+ those riding in the launch)
+        if o.kind == "lowres":                                           # the fused ESA branch: the calls of the ops it replaces
+            return tuple(sum(t) for t in zip(*(self._complexity_terms(plan, s) for s in o.replaces)))
+        h, w = o.hw if o.kind in ("conv", "dw") and o.hw else (plan.h, plan.w)
+        if o.kind == "dw":
+            return 9 * o.c * plan.n * h * w, o.c * plan.n * h * w, 1
+        if o.kind == "bs":                                               # depthwise Conv2d + 1 or 2 Linear calls in one launch
+            nlin = 1 + (o.distill is not None)
+            return 9 * o.cout * plan.n * h * w + nlin * plan.n * h * h, o.cout * plan.n * h * w, 1
+        if o.kind == "conv" and o.bs_of is not None:                     # a BSConvU run as a dense 3x3: one Linear + one depthwise Conv2d
+            nlin = 1 + (o.post is not None) + (o.tail is not None)       # (+ the Linear(s) riding in its launch)
+            return 9 * o.cout * plan.n * h * w + nlin * plan.n * h * h, o.cout * plan.n * h * w, 1
+        if o.kind == "conv" and not o.counted:
+            return (1 + (o.post is not None)) * plan.n * h * h, 0, 0     # a Linear call (+ the one in its epilogue)
+        if o.kind == "apply":
+            return (2 + len(o.post or ())) * plan.n * plan.h * plan.h, 0, 0       # conv_f and conv4 are Linear here (+ those riding in the launch)
         return super()._complexity_terms(plan, o)

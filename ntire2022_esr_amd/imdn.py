@@ -16,7 +16,7 @@ Forward = 3 + 4*nb kernel launches (3 + 5*nb when nc != 64), no split/cat/add ke
   up       nc->out_nc*16 3x3 fused with PixelShuffle(4) -> NCHW output             basicblock.py:446-449
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, HipSRModel
+from .engine import INPUT, OUTPUT, HipSRModel, Tail
 
 
 class IMDN(HipSRModel):
@@ -88,7 +88,7 @@ class IMDN(HipSRModel):
                 # conv4 -> cat -> conv1x1 -> + x in one kernel: the 16 conv4 channels go from the 3x3's accumulators
                 # straight into the 1x1's K loop and never reach memory
                 plan.conv(p + 'conv4', r3, nxt, r, d, res=cur, res_mode=L.RES_PRE_ACT,
-                          tail=dict(w=p + 'conv1x1', cat=cat[0:3 * d], cat_c=3 * d, cout=nc))
+                          tail=Tail(p + 'conv1x1', cat[0:3 * d], 3 * d, 3 * d, nc))
             else:
                 plan.conv(p + 'conv4', r1, cs(3), r, d)
                 plan.conv(p + 'conv1x1', cat, nxt, 4 * d, nc, k=1, res=cur, res_mode=L.RES_PRE_ACT)

@@ -8,7 +8,7 @@ and the four block outputs as 56-wide slices of one 224-wide buffer, so neither 
 residual + LeakyReLU} x3, 3x3 50->25 + LeakyReLU, 1x1 c5 over the concat, ESA.
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, HipSRModel, Planar
+from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Planar, Post, Tail
 from .rlfn import FP, _lowres, _pad8
 
 
@@ -101,7 +101,7 @@ class RFDN(HipSRModel):
         fused_tail = (self.fuse_tail and plan.esize == 2 and fused_post and planar and 48 < nf <= 64 and DP == 32 and f <= 16 and FP == 16
                       and plan.n * ((plan.w + 15) // 16) * ((plan.h + 15) // 16) >= 256)
         head_d = plan.esize == 2 and fused_post
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, post=dict(w='B1.c1_d', dst=cs(0), cout=dc, act=L.ACT_LRELU) if head_d else None,
+        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, post=Post('B1.c1_d', cs(0), dc, L.ACT_LRELU) if head_d else None,
                   hilo=L.HILO_OUT if hl else 0)
         # ... and the other blocks' in the ESA apply launch that produces their input (esr_esa_desc.post[])
         apply_d = plan.esize == 2 and fused_post and bool(L.lib().esr_esa_apply_post_supported(nf, dc, 0))
@@ -113,9 +113,9 @@ class RFDN(HipSRModel):
             if fused_post:
                 # the distillation conv of r_j rides in the epilogue of the conv that produces r_j (block.py:150-160)
                 plan.conv(b + 'c1_r', cur, r1, nf, nf, **res(cur), **act,
-                          post=dict(w=b + 'c2_d', dst=cs(1), cout=dc, act=L.ACT_LRELU))
+                          post=Post(b + 'c2_d', cs(1), dc, L.ACT_LRELU))
                 plan.conv(b + 'c2_r', r1, r2, nf, nf, **res(r1), **act,
-                          post=dict(w=b + 'c3_d', dst=cs(2), cout=dc, act=L.ACT_LRELU))
+                          post=Post(b + 'c3_d', cs(2), dc, L.ACT_LRELU))
             else:
                 plan.conv(b + 'c1_r', cur, r1, nf, nf, **res(cur), **act)
                 plan.conv(b + 'c2_d', r1, cs(1), nf, dc, k=1, **act)
@@ -125,16 +125,15 @@ class RFDN(HipSRModel):
             if fused_tail:
                 # round 6 (ABI v12): c4 -> cat(d1, d2, d3, r4) -> c5 -> esa.conv1 in ONE launch (rfdb_tail_kernel; block.py:161-164, :117):
                 # r4 stays in registers, d1 .. d3 are read once, v and esa.conv1's map are the only stores
-                plan.conv(b + 'c4', r1, v, nf, dc, tail=dict(w=b + 'c5#tail', cat=Planar(cat.segs[:3]), cat_c=3 * DP, cat_c_alg=3 * dc, cout=nf,
-                                                             mid_act=L.ACT_LRELU),
-                          post=dict(w=b + 'esa.conv1', dst=c1, cout=f, act=L.ACT_NONE))
+                plan.conv(b + 'c4', r1, v, nf, dc, tail=Tail(b + 'c5#tail', Planar(cat.segs[:3]), 3 * DP, 3 * dc, nf, L.ACT_LRELU),
+                          post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
                 plan.conv(b + 'c4', r1, cs(3), nf, dc, **act)
             if fused_tail:
                 pass
             elif plan.esize == 2 and (nf + 15) // 16 in (3, 4) and f <= 16:
                 # 16-bit storage: esa.conv1 rides in c5's epilogue on the fp32 tile (one launch less per block)
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=dict(w=b + 'esa.conv1', dst=c1, cout=f, act=L.ACT_NONE))
+                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
                 plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
                 plan.conv(b + 'esa.conv1', v, c1, nf, f, k=1)
@@ -147,10 +146,10 @@ class RFDN(HipSRModel):
             if self.fuse_esa_lowres:
                 # the five launches above as one op of two (halo recompute; only the pooled map reaches memory)
                 plan.esa_lowres(mark, c1, la, lb, f, b + 'esa.conv2',
-                                [dict(kind=0, act=L.ACT_RELU, w=b + 'esa.conv_max'), dict(kind=0, act=L.ACT_RELU, w=b + 'esa.conv3'),
-                                 dict(kind=0, act=L.ACT_NONE, w=b + 'esa.conv3_')])
+                                [EsaLayer(0, L.ACT_RELU, b + 'esa.conv_max'), EsaLayer(0, L.ACT_RELU, b + 'esa.conv3'),
+                                 EsaLayer(0, L.ACT_NONE, b + 'esa.conv3_')])
             out = bcat.seg(k - 1) if bplanar else bcat[(k - 1) * P:k * P]
-            nxt_d = [dict(w=f'B{k + 1}.c1_d', dst=cs(0), cout=dc, act=L.ACT_LRELU, slope=0.05)] if (apply_d and k < 4) else None
+            nxt_d = [Post(f'B{k + 1}.c1_d', cs(0), dc, L.ACT_LRELU, slope=0.05)] if (apply_d and k < 4) else None
             plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lb, out, nf, f, post=nxt_d)
             cur = out
         plan.conv('c.0', bcat, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **act)
@@ -187,13 +186,13 @@ class RFDN(HipSRModel):
     def _counted_convs(self, plan, o):
         """logical channel counts for the padded-concat 1x1 convs (the reference sees 100 / 200 inputs)."""
         r = super()._counted_convs(plan, o)
-        if o["kind"] == "apply" and not self.esa_conv_f:
+        if o.kind == "apply" and not self.esa_conv_f:
             return r[1:]                         # no conv_f call in the reference graph
-        if o["kind"] == "conv" and o.get("tail") is not None and o["w"].endswith('.c4'):      # the fused block tail: c4, c5, esa.conv1
-            return [(o["cin"], o["cout"], 3, plan.npix, L.ACT_LRELU), (self.dc * 4, o["tail"]["cout"], 1, plan.npix, L.ACT_NONE),
-                    (o["tail"]["cout"], o["post"]["cout"], 1, plan.npix, L.ACT_NONE)]
-        if o["kind"] == "conv" and o["w"].endswith('.c5'):
-            return [(self.dc * 4, o["cout"], 1, plan.npix, o["act"])]
-        if o["kind"] == "conv" and o["w"] == 'c.0':
-            return [(self.nf * self.num_modules, o["cout"], 1, plan.npix, o["act"])]
+        if o.kind == "conv" and o.tail is not None and o.w.endswith('.c4'):      # the fused block tail: c4, c5, esa.conv1
+            return [(o.cin, o.cout, 3, plan.npix, L.ACT_LRELU), (self.dc * 4, o.tail.cout, 1, plan.npix, L.ACT_NONE),
+                    (o.tail.cout, o.post.cout, 1, plan.npix, L.ACT_NONE)]
+        if o.kind == "conv" and o.w.endswith('.c5'):
+            return [(self.dc * 4, o.cout, 1, plan.npix, o.act)]
+        if o.kind == "conv" and o.w == 'c.0':
+            return [(self.nf * self.num_modules, o.cout, 1, plan.npix, o.act)]
         return r

@@ -7,7 +7,7 @@ adds the block input AFTER the activation), the 1x1 c5, then ESA as 1x1 conv1 ->
 3x3 at ~H/6 -> one fused full-resolution tail (bilinear + conv_f + conv4 + sigmoid * x).
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, HipSRModel
+from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Post
 
 FP = L.ESA_FP
 
@@ -82,8 +82,7 @@ class RLFN_cut(HipSRModel):
                 # post2_*): u = lrelu(c3_r(..)) + x (team04_rlfn.py:117-119) is never stored, never rounded -- two launches
                 # and three tensor passes less per block, and the rounding that cost RLFN bf16 most of its PSNR budget is gone
                 plan.conv(b + 'c3_r', t2, None, mf, nf, res=cur, res_mode=L.RES_POST_ACT, **act,
-                          post=dict(w=b + 'c5', dst=v, cout=nf, act=L.ACT_NONE,
-                                    post2=dict(w=b + 'esa.conv1', dst=c1, cout=f)))
+                          post=Post(b + 'c5', v, nf, post2=Post(b + 'esa.conv1', c1, f)))
                 if self.fuse_chain and (mf + 15) // 16 == 3:
                     # ... and the three 3x3s as ONE launch: a layer-per-SIMD pipeline with t1 / t2 / u in LDS (esr_conv_chain_s16, round 5)
                     plan.chain(mark_c)
@@ -96,7 +95,7 @@ class RLFN_cut(HipSRModel):
             plan.maxpool7s3(lo2, lo3)
             plan.conv(b + 'esa.conv3', lo3, lo4, f, f, hw=(h3, w3))
             if self.fuse_esa_lowres:
-                plan.esa_lowres(mark, c1, lo3, lo4, f, b + 'esa.conv2', [dict(kind=0, act=L.ACT_NONE, w=b + 'esa.conv3')])
+                plan.esa_lowres(mark, c1, lo3, lo4, f, b + 'esa.conv2', [EsaLayer(0, L.ACT_NONE, b + 'esa.conv3')])
             plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lo4, nxt, nf, f)
             cur = nxt
             nxt = xb if cur is xa else xa

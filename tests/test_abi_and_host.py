@@ -156,13 +156,13 @@ def test_imdn_plan_shape():
     plan = Plan(2, 40, 56)
     m._build_plan(plan, 3)
     assert len(plan.ops) == 3 + 4 * 8
-    assert sum(o.get("tail") is not None for o in plan.ops) == 8
+    assert sum(o.tail is not None for o in plan.ops) == 8
     assert plan.total == 4 * 2 * 40 * 56 * (64 * 4 + 48 * 4)                  # bytes: fea, xa, xb, lr | cat (d1 d2 d3), r1, r2, r3
     blk = [bf for bf in plan.buffers if bf.blocked]
     # channel-blocked [n][c/8][h][w][8]: the IMDBlocks' x (ping-pong) and every "remaining" slice; fea, lr and cat stay NHWC
     assert [bf.name for bf in blk] == ["xa", "xb", "r1", "r2", "r3"]
     r3 = blk[-1]
-    assert all((o["dst1"] is r3) == o["w"].endswith("conv3.0") and (o["src"] is r3) == (o.get("tail") is not None) for o in plan.ops)
+    assert all((o.dst1 is r3) == o.w.endswith("conv3.0") and (o.src is r3) == (o.tail is not None) for o in plan.ops)
     m.winograd = False                                                          # the direct kernels read NHWC: only r3 stays blocked
     plan = Plan(2, 40, 56)
     m._build_plan(plan, 3)
@@ -176,7 +176,7 @@ def test_imdn_plan_shape():
     m32 = IMDN(nc=32)                                                          # no 16-channel distillation: unfused
     plan = Plan(1, 40, 56)
     m32._build_plan(plan, 3)
-    assert len(plan.ops) == 3 + 5 * 8 and all(o.get("tail") is None for o in plan.ops)
+    assert len(plan.ops) == 3 + 5 * 8 and all(o.tail is None for o in plan.ops)
     for nc in (16, 48):                                                        # 3/4 nc is not a whole number of 8-channel chunks
         with pytest.raises(NotImplementedError):
             IMDN(nc=nc)
@@ -585,14 +585,15 @@ def test_chain_descriptor_validation_and_rlfn_plan_without_gpu():
         m.fuse_chain = fuse
         plan = Plan(1, 64, 64, store)
         m._build_plan(plan, 3)
-        assert sum(o["kind"] == "chain" for o in plan.ops) == nchain, (store, fuse)
+        assert sum(o.kind == "chain" for o in plan.ops) == nchain, (store, fuse)
         for o in plan.ops:
-            if o["kind"] == "chain":
-                assert [s["w"].split(".")[-1] for s in o["replaces"]] == ["c1_r", "c2_r", "c3_r"] and o["replaces"][-1]["post"]["post2"] is not None
+            if o.kind == "chain":
+                assert [s.w.split(".")[-1] for s in o.replaces] == ["c1_r", "c2_r", "c3_r"] and o.replaces[-1].post.post2 is not None
         terms = [m._complexity_terms(plan, o) for o in plan.ops]
         flops, acts, nconv = (sum(t[i] for t in terms) for i in range(3))
         assert (float(flops), float(acts), int(nconv)) == (ref["flops"], ref["activations"], ref["num_conv"]), (store, fuse)
     m.fuse_chain = True
-    assert {"B1.c1_r", "B2.c2_r", "B4.c3_r"} <= m._s16_convs() if m.set_compute("bf16") else False
-    assert {"B1.c5", "B3.esa.conv1"} <= m._post_convs()
+    m.set_compute("bf16")._repack("cpu")              # the chain's convs and 1x1s get their 16-bit blobs
+    assert {"B1.c1_r#s16", "B2.c2_r#s16", "B4.c3_r#s16"} <= set(m._packed)
+    assert {"B1.c5#post", "B3.esa.conv1#post"} <= set(m._packed)
     m.set_compute("f32")

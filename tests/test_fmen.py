@@ -52,19 +52,19 @@ def test_plan_shape_with_and_without_the_fused_hfab(store, fuse):
             m._build_plan(plan, 3)
         return
     m._build_plan(plan, 3)
-    chains = [o for o in plan.ops if o["kind"] == "chain"]
+    chains = [o for o in plan.ops if o.kind == "chain"]
     s16 = store != "f32"
     # f32: 34 convs; 16-bit: + the input pack; fused: each body HFAB's four convs are one op
     assert len(plan.ops) == 34 + s16 - (12 if (s16 and fuse) else 0)
     if s16:                                   # bf16: the long skip x and lr_conv's output as hi + lo pairs
-        assert [(o["w"], o["hilo"]) for o in plan.ops if o["kind"] == "conv" and o["hilo"]] == [
+        assert [(o.w, o.hilo) for o in plan.ops if o.kind == "conv" and o.hilo] == [
             ("head#head", L.HILO_OUT), ("lr_conv", L.HILO_RES | L.HILO_OUT), ("tail.0", L.HILO_IN)]
     assert len(chains) == (4 if (s16 and fuse) else 0)
     for i, o in enumerate(chains):
-        assert o["gate"] and [s["w"] for s in o["replaces"]] == [f"hfabs.{i}.squeeze", f"hfabs.{i}.convs.0.conv1.rep_conv",
+        assert o.gate and [s.w for s in o.replaces] == [f"hfabs.{i}.squeeze", f"hfabs.{i}.convs.0.conv1.rep_conv",
                                                                   f"hfabs.{i}.convs.0.conv2.rep_conv", f"hfabs.{i}.excitate"]
-        assert o["replaces"][-1]["res_mode"] == L.RES_GATE and o["replaces"][0]["slope"] == 0.1
-    gates = [o for o in plan.ops if o["kind"] == "conv" and o["res_mode"] == L.RES_GATE]
+        assert o.replaces[-1].res_mode == L.RES_GATE and o.replaces[0].slope == 0.1
+    gates = [o for o in plan.ops if o.kind == "conv" and o.res_mode == L.RES_GATE]
     assert len(gates) == (1 if (s16 and fuse) else 5)                 # the warmup HFAB stays on per-layer launches
     nf_bufs = {b.pitch for b in plan.buffers if b.name in ("x.0", "x", "ha", "hb")}
     assert nf_bufs == {56}                                            # tight pitch in 16-bit, whole fp32 chunks (56) in fp32
@@ -84,7 +84,7 @@ def test_plan_shape_with_and_without_the_fused_hfab(store, fuse):
         assert hf[0]["write_bytes"] == npix * 50 * 2
         assert hf[0]["stored_bytes"] == npix * 2 * (56 + 56) + 4.0 * 9 * (50 * 16 + 2 * 16 * 16 + 16 * 50)
         for i, o in enumerate(plan.ops):
-            if o["kind"] == "chain":
+            if o.kind == "chain":
                 d = arr[i].chain
                 assert (d.n_layers, d.cin, d.cmid, d.cout, d.res_mode, d.post_cout) == (4, 50, 16, 50, L.RES_GATE, 56)
                 assert not d.post_wpacked and abs(d.slope - 0.1) < 1e-7

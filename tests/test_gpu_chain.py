@@ -116,7 +116,7 @@ def test_rlfn_with_chain_equals_without(compute, shape, strip_groups):
     m.fuse_chain = True
     y1 = m(x).clone()
     plan = m._plans[(shape[0], shape[1], shape[2], shape[3], torch.device(DEV))].plan
-    assert sum(o["kind"] == "chain" for o in plan.ops) == 4
+    assert sum(o.kind == "chain" for o in plan.ops) == 4
     m.fuse_chain = False
     y0 = m(x).clone()
     torch.cuda.synchronize()

@@ -37,7 +37,7 @@ print("calls logged:", n)
 plan = next(iter(m._plans.values())).plan
 ops = plan.ops
 def opname(k):
-    o = ops[k]; return f"{k}:{o['kind']}:{o.get('w', '')}"
+    o = ops[k]; return f"{k}:{o.kind}:{getattr(o, 'w', '')}"
 first = collections.Counter(); anydiff = 0
 for rnd in range(rounds):
     for i in range(10):

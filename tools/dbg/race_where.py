@@ -35,8 +35,8 @@ for rnd in range(rounds):
         call = 10 + rnd * 10 + i
         h, w = shapes[i]
         plan = [e.plan for e in m._ctxs[next(iter(m._ctxs))].plans.values() if (e.plan.h, e.plan.w) == (h, w)][0]
-        ap = [o for o in plan.ops if o["kind"] == "apply"]
-        pitch = ap[0]["dst"].pitch if hasattr(ap[0]["dst"], "pitch") else 48
+        ap = [o for o in plan.ops if o.kind == "apply"]
+        pitch = ap[0].dst.pitch if hasattr(ap[0].dst, "pitch") else 48
         nb = h * w * pitch * 2
         for k in range(4):
             ya = cap.view(64, 4, PER)[call % 64, k, :nb].view(torch.bfloat16).view(h, w, pitch).float()
