@@ -330,12 +330,22 @@ typedef struct esr_esa_desc {
  * w_dw = esr_pack_dw_f32.  Replaces esr_conv3x3s2_f32 + esr_maxpool7s3_f32 + 1..6 small esr_conv2d_f32 / esr_dwconv3x3_f32 launches
  * (which stay available): on one DIV2K image they were a third of a forward's launches for < 1 % of its arithmetic.
  */
+/*
+ * w_s2 == NULL -- EFDN's branch (models/team05_efdn/plainblock.py:124-150; csrc/esr_esa_pool7.hip, additive within ABI v12):
+ *     c3 = conv_23(cat(act(conv_2(v)), act(conv_3(v)))),   v = max_pool2d(c1_, 7, stride 7, padding 1)
+ * pooled straight from the conv1 map x (padding never wins), h7 = (h - 5) / 7 + 1 (likewise w7); `pooled` and `y` are [n][h7][w7][16] fp32.
+ * Exactly n_layers == 2: layer[0] kind 2 = the parallel pair of dense 3x3 / padding 1 convolutions, `w` = conv_2 and `w_dw` = conv_3
+ * (esr_pack_dense_f32(k = 3, 16, 16) each), its `act` on both; layer[1] kind 3 = the dense 3x3 over the pair's 2f-channel concat, `w` =
+ * esr_pack_dense_f32(k = 3, cin_p = 32, cout_p = 16) of the weights with conv_2's f input channels in rows 0 .. f-1 and conv_3's in rows
+ * 16 .. 16+f-1 (the slot order of a [.., 32] map holding the two outputs at channel offsets 0 and 16), its `act` behind it.  Acts: none,
+ * ReLU, LeakyReLU(0.05).  h or w < 5: ESR_ERR_TOO_SMALL.  Two launches; the concat and the pair's outputs never reach memory.
+ */
 #define ESR_ESA_MAX_LAYERS 3
 typedef struct esr_esa_layer {
-    int32_t kind;               /* 0: dense 3x3, 1: BSConvU */
+    int32_t kind;               /* 0: dense 3x3, 1: BSConvU, 2: parallel pair of dense 3x3s, 3: dense 3x3 over the pair's concat */
     int32_t act;                /* esr_act behind the layer */
     const void* w;
-    const void* w_dw;           /* kind 1 only */
+    const void* w_dw;           /* kind 1: the depthwise weights; kind 2: the pair's second 3x3 */
 } esr_esa_layer;
 typedef struct esr_esa_lowres_desc {
     int32_t n, h, w;            /* full-resolution dims of the conv1 map */
@@ -343,7 +353,7 @@ typedef struct esr_esa_lowres_desc {
     int32_t storage;            /* esr_storage of x */
     int32_t n_layers;
     esr_view x;                 /* pitch 16, coff 0 */
-    const void* w_s2;
+    const void* w_s2;           /* NULL: EFDN's stride-7 branch (above) */
     void* pooled;               /* scratch, n * h3 * w3 * 16 floats */
     void* y;                    /* result, n * h3 * w3 * 16 floats */
     esr_esa_layer layer[ESR_ESA_MAX_LAYERS];
@@ -352,6 +362,9 @@ int esr_esa_lowres_f32(const esr_esa_lowres_desc* d, void* hip_stream);
 
 int esr_conv3x3s2_f32(const esr_esa_desc* d, void* hip_stream);   /* x: [n][h][w][16] -> y: [n][h_lo][w_lo][16] */
 int esr_maxpool7s3_f32(const esr_esa_desc* d, void* hip_stream);  /* x: [n][h][w][16] -> y: [n][h_lo][w_lo][16] */
+/* F.max_pool2d(kernel_size=7, stride=7, padding=1) (team05_efdn/plainblock.py:143): x = the conv1 map [n][h][w][16] in `storage`, y = [n][h_lo][w_lo][16]
+ * fp32 with h_lo = (h - 5) / 7 + 1 (likewise w_lo); h or w < 5: ESR_ERR_TOO_SMALL.  The pooling of esr_esa_lowres_f32's w_s2 == NULL form alone. */
+int esr_maxpool7s7_f32(const esr_esa_desc* d, void* hip_stream);
 int esr_esa_apply_f32(const esr_esa_desc* d, void* hip_stream);
 
 /*
@@ -401,7 +414,8 @@ typedef enum esr_op_kind {
     ESR_OP_BSCONV = 5,
     ESR_OP_PACK_INPUT = 6,      /* esr_pack_input_s16 on esr_op.conv (ABI v5) */
     ESR_OP_ESA_LOWRES = 7,      /* esr_esa_lowres_f32 on esr_op.lo (ABI v7) */
-    ESR_OP_CONV_CHAIN = 8       /* esr_conv_chain_s16 on esr_op.chain (ABI v11) */
+    ESR_OP_CONV_CHAIN = 8,      /* esr_conv_chain_s16 on esr_op.chain (ABI v11) */
+    ESR_OP_MAXPOOL7S7 = 9       /* esr_maxpool7s7_f32 on esr_op.esa (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -503,7 +517,7 @@ typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
     esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV */
-    esr_esa_desc esa;           /* the three ESA kinds */
+    esr_esa_desc esa;           /* the four ESA kinds */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */
     esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11) */

@@ -20,6 +20,7 @@ NHWC, NCHW_IN, NCHW_SHUFFLE4 = 0, 1, 2
 BLOCKED_IN, BLOCKED_OUT1, BLOCKED_OUT0, BLOCKED_RES = 1, 2, 4, 8          # esr_conv_desc.blocked8 bits (ABI v6 / v9)
 HILO_IN, HILO_RES, HILO_OUT = 1, 2, 4                                     # esr_conv_desc.hilo bits (ABI v10)
 OP_CONV, OP_CONV3X3S2, OP_MAXPOOL7S3, OP_ESA_APPLY, OP_DWCONV, OP_BSCONV, OP_PACK_INPUT, OP_ESA_LOWRES, OP_CONV_CHAIN = 0, 1, 2, 3, 4, 5, 6, 7, 8
+OP_MAXPOOL7S7 = 9                                                         # EFDN's ESA pooling (esr_maxpool7s7_f32)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -135,7 +136,7 @@ EXPORTS = [
     "esr_conv2d_f32", "esr_conv_block_waves", "esr_run_ops", "esr_pack_input_s16",
     "esr_prof_create", "esr_run_ops_profiled", "esr_prof_collect", "esr_prof_destroy", "esr_prof_kernel_symbol",
     "esr_packed_dense_bytes", "esr_pack_dense_f32",
-    "esr_conv3x3s2_f32", "esr_maxpool7s3_f32", "esr_esa_apply_f32", "esr_esa_lowres_f32",
+    "esr_conv3x3s2_f32", "esr_maxpool7s3_f32", "esr_maxpool7s7_f32", "esr_esa_apply_f32", "esr_esa_lowres_f32",
     "esr_esa_apply_post_supported", "esr_packed_apply_post_bytes", "esr_pack_apply_post",
     "esr_packed_dw_bytes", "esr_pack_dw_f32", "esr_dwconv3x3_f32", "esr_bsconv_f32",
     "esr_tensor2uint_u8", "esr_sqerr_u8", "esr_channel_attention_f32",
@@ -207,7 +208,7 @@ def lib():
     L.esr_packed_dense_bytes.restype = sz
     L.esr_pack_dense_f32.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz]
     L.esr_pack_dense_f32.restype = ci
-    for fn in (L.esr_conv3x3s2_f32, L.esr_maxpool7s3_f32, L.esr_esa_apply_f32):
+    for fn in (L.esr_conv3x3s2_f32, L.esr_maxpool7s3_f32, L.esr_maxpool7s7_f32, L.esr_esa_apply_f32):
         fn.argtypes = [ctypes.POINTER(EsaDesc), vp]
         fn.restype = ci
     L.esr_esa_lowres_f32.argtypes = [ctypes.POINTER(EsaLowresDesc), vp]

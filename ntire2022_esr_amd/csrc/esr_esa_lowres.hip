@@ -472,6 +472,7 @@ size_t s2_lds()
 
 extern "C" int esr_esa_lowres_f32(const esr_esa_lowres_desc* d, void* hip_stream)
 {
+    if (d && !d->w_s2) return esr_esa_pool7_lowres(d, hip_stream);              // EFDN's stride-7 branch (esr_esa_pool7.hip)
     if (!d || !d->x.ptr || !d->w_s2 || !d->pooled || !d->y) return ESR_ERR_BAD_ARG;
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->f <= 0 || d->f > FP) return ESR_ERR_BAD_ARG;
     if (d->x.pitch != FP || d->x.coff) return ESR_ERR_BAD_ARG;

@@ -19,6 +19,9 @@ int esr_s16_block_waves(const esr_conv_desc* d);      // 4: two 4-wave blocks pe
 int esr_hfab_supported(const esr_chain_desc* d);
 int esr_hfab_s16(const esr_chain_desc* d, void* hip_stream);
 
+// esr_esa_pool7.hip: EFDN's ESA branch -- esr_esa_lowres_f32 with w_s2 == NULL (max_pool2d(7, 7, padding 1) + the parallel pair + conv_23)
+int esr_esa_pool7_lowres(const esr_esa_lowres_desc* d, void* hip_stream);
+
 // esr_wino.hip: Winograd F(2x2, 3x3) fp32 convolution (called by esr_conv2d_f32 when d->wino_wpacked is set and the shape qualifies)
 int esr_conv2d_wino(const esr_conv_desc* d, void* hip_stream);
 

@@ -358,7 +358,8 @@ class Tail:
 
 @dataclass
 class EsaLayer:
-    """A layer of the fused ESA branch (esr_esa_layer): kind 0 = dense 3x3 `w`, 1 = pointwise `w` + depthwise `w_dw`."""
+    """A layer of the fused ESA branch (esr_esa_layer): kind 0 = dense 3x3 `w`, 1 = pointwise `w` + depthwise `w_dw`, 2 = the parallel pair of
+    dense 3x3s `w` and `w_dw`, 3 = the dense 3x3 `w` over the pair's 2f-channel concat (EFDN)."""
     kind: int
     act: int
     w: str
@@ -610,7 +611,7 @@ class Conv(_Op):
         if not self.counted:
             return []
         npix = plan.npix if self.hw is None else plan.n * self.hw[0] * self.hw[1]
-        conv = (self.cin, self.cout, self.k, npix, self.act)
+        conv = (self.cin_alg, self.cout, self.k, npix, self.act)
         t = self.tail
         if t is not None:                                     # two nn.Conv2d calls of the reference in one launch
             return [conv[:4] + (t.mid_act,), (t.cat_c + self.cout, t.cout, 1, npix, self.act)]
@@ -746,9 +747,28 @@ class Pool(_Op):
 
 
 @dataclass
+class Pool7(_Op):
+    """EFDN's ESA pooling, max_pool2d(7, stride 7, padding 1) of the full-resolution conv1 map (esr_maxpool7s7_f32)"""
+    src: Buffer
+    dst: Buffer
+    kind = "pool7"
+
+    def encode(self, op, plan, base, weights):
+        op.kind = L.OP_MAXPOOL7S7
+        e = op.esa
+        e.n, e.h, e.w, e.h_lo, e.w_lo = plan.n, self.src.h, self.src.w, self.dst.h, self.dst.w
+        e.x, e.y = _view(self.src, base), _view(self.dst, base)
+        e.storage = L.STORE[plan.store]                       # reads the full-resolution conv1 map
+
+    def cost(self, plan, desc):
+        return _cost("pool7", f"esa_pool7_kernel<{L.STORE[plan.store]}>", 0, 0, 0, 0.0, float(plan.n * self.src.h * self.src.w * 16 * self.src.esize),
+                     float(plan.n * self.dst.h * self.dst.w * 16 * 4))
+
+
+@dataclass
 class Lowres(_Op):
-    """ESA's low-resolution branch as ONE op (esr_esa_lowres_f32) -- see Plan.esa_lowres.  w: conv2's weights; replaces: the ops it
-    stands for."""
+    """ESA's low-resolution branch as ONE op (esr_esa_lowres_f32) -- see Plan.esa_lowres.  w: conv2's weights (None: EFDN's stride-7 branch,
+    pooled straight from `src`); replaces: the ops it stands for."""
     src: Buffer
     pooled: Buffer
     dst: Buffer
@@ -763,7 +783,7 @@ class Lowres(_Op):
         d = op.lo
         d.n, d.h, d.w, d.f, d.storage, d.n_layers = plan.n, plan.h, plan.w, self.f, L.STORE[plan.store], len(self.layers)
         d.x = _view(self.src, base)
-        d.w_s2 = ctypes.c_void_p(weights[self.w].data_ptr())
+        d.w_s2 = ctypes.c_void_p(weights[self.w].data_ptr()) if self.w is not None else None
         d.pooled = ctypes.c_void_p(_addr(self.pooled, base))
         d.y = ctypes.c_void_p(_addr(self.dst, base))
         for l, ly in enumerate(self.layers):
@@ -771,10 +791,16 @@ class Lowres(_Op):
             d.layer[l].w = ctypes.c_void_p(weights[ly.w + DENSE].data_ptr())
             if ly.kind == 1:
                 d.layer[l].w_dw = ctypes.c_void_p(weights[ly.w_dw].data_ptr())
+            elif ly.kind == 2:                                # the pair's second 3x3
+                d.layer[l].w_dw = ctypes.c_void_p(weights[ly.w_dw + DENSE].data_ptr())
 
     def cost(self, plan, desc):                               # conv2 (s2) + pooling + the 3x3 layers behind it: two launches, only the pooled map in between
         src, dst, f = self.src, self.dst, self.f
         npl = plan.n * dst.h * dst.w
+        if self.w is None:                                    # EFDN: pooling of the full-resolution map, then the pair + conv_23 in one launch
+            flops = 2.0 * npl * (2 * 9 * f * f + 9 * 2 * f * f)
+            return _cost(self.layers[0].w, f"esa_pool7_kernel<{L.STORE[plan.store]}> + esa_pool7_branch_kernel", f, f, 3, flops,
+                         float(plan.n * src.h * src.w * f * src.esize + npl * f * 4), float(2 * npl * f * 4))
         h2, w2 = (src.h - 3) // 2 + 1, (src.w - 3) // 2 + 1
         flops = 2.0 * 9 * f * f * plan.n * h2 * w2
         for ly in self.layers:
@@ -972,10 +998,14 @@ class Plan:
     def maxpool7s3(self, src, dst):
         self.ops.append(Pool(src, dst))
 
+    def maxpool7s7(self, src, dst):
+        self.ops.append(Pool7(src, dst))
+
     def esa_lowres(self, mark, c1, pooled, dst, f, s2, layers):
         """ESA's low-resolution branch as ONE op (esr_esa_lowres_f32: two launches with halo recompute) in place of the ops appended
         since `mark = len(plan.ops)` -- conv3x3s2, maxpool7s3 and the 1..3 small 3x3 layers (RFDN / RLFN: dense convs, BSRN: pointwise +
-        depthwise pairs); those ops stay attached as `replaces`: the complexity counters and the algorithmic costs are theirs.
+        depthwise pairs); or, with s2 = None, EFDN's maxpool7s7, conv_2, conv_3 and conv_23 (layers: one kind-2 pair and one kind-3 layer);
+        those ops stay attached as `replaces`: the complexity counters and the algorithmic costs are theirs.
         layers: [EsaLayer, ...]"""
         sub = self.ops[mark:]
         del self.ops[mark:]
@@ -1296,10 +1326,12 @@ class HipSRModel(nn.Module):
         # shape has every op the network emits
         plan = Plan(1, 32, 32, store)
         self._build_plan(plan, self.in_nc)
-        s16, post, head, dense = set(), set(), set(), set()
+        s16, post, head, dense, dense_cat = set(), set(), set(), set(), set()
         for o in plan.ops:
             if o.kind == "lowres":                          # 3x3 / pointwise layers of the fused ESA branch: plain dense layout
-                dense.update(ly.w for ly in o.layers)
+                dense.update(ly.w for ly in o.layers if ly.kind != 3)
+                dense.update(ly.w_dw for ly in o.layers if ly.kind == 2)
+                dense_cat.update(ly.w for ly in o.layers if ly.kind == 3)
             if store == "f32":
                 continue
             if o.kind == "bs":                              # BSConvU: pointwise + distillation 1x1 weights as hi + lo blobs
@@ -1332,6 +1364,13 @@ class HipSRModel(nn.Module):
         for path in sorted(dense):
             leaf = self._leaf(path)
             packed[path + DENSE] = pack_dense(leaf.weight, leaf.bias, L.ESA_FP, L.ESA_FP).to(device)
+        for path in sorted(dense_cat):                  # a 3x3 over the pair's concat: the two halves' inputs at rows 0 and 16 (esr_esa_layer kind 3)
+            leaf = self._leaf(path)
+            w = leaf.weight.detach().to("cpu", torch.float32)
+            f = w.shape[1] // 2
+            w32 = torch.zeros(w.shape[0], 2 * L.ESA_FP, 3, 3)
+            w32[:, :f], w32[:, L.ESA_FP:L.ESA_FP + f] = w[:, :f], w[:, f:]
+            packed[path + DENSE] = pack_dense(w32, leaf.bias, 2 * L.ESA_FP, L.ESA_FP).to(device)
         for path in self._dw_specs:
             leaf = self._leaf(path)
             packed[path] = pack_dw(leaf.weight, leaf.bias).to(device)
