@@ -1144,9 +1144,7 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
     k.in_blk = (d->blocked8 & ESR_BLOCKED_IN) ? 1 : 0;
     k.y0_blk = (d->blocked8 & ESR_BLOCKED_OUT0) ? 1 : 0;
     k.res_blk = (d->blocked8 & ESR_BLOCKED_RES) ? 1 : 0;
-    if (d->blocked8 & ~(ESR_BLOCKED_IN | ESR_BLOCKED_OUT1 | ESR_BLOCKED_OUT0 | ESR_BLOCKED_RES)) return ESR_ERR_BAD_ARG;
-    // blocked out0 / res: only the fused IMDB tail (checked again where the tail shape is known), whole planes
-    if ((k.y0_blk || k.res_blk) && (!tail || store16)) return ESR_ERR_UNSUPPORTED;
+    // blocked out0 / res (the fused IMDB tail only, checked again where the tail shape is known): whole planes
     if (k.y0_blk && ((d->out0.pitch & 7) || (d->out0.coff & 7) || (double)d->h * d->w * d->out0.pitch * 4.0 >= 2147483647.0)) return ESR_ERR_UNSUPPORTED;
     if (k.res_blk && (d->res_mode != ESR_RES_PRE_ACT || (d->res.pitch & 7) || (d->res.coff & 7))) return ESR_ERR_UNSUPPORTED;
     if (k.y1_blk) {

@@ -883,120 +883,121 @@ static bool s16_res_is_input(const esr_conv_desc* d)
            d->res.pitch == d->in.pitch && d->res.coff == d->in.coff;
 }
 
-// conv48r_kernel's descriptors: a 3x3 over 48 physical input channels with 2 or 3 output tiles, at least one 16 x 32 tile per CU, no
-// residual from HBM, no split, no post chain (measured slower there), NHWC, one input tensor
-static bool conv48r_shape(const esr_conv_desc* d)
+// the magic division of a tile index (S16K.magic_x / magic_y) is exact while n * tiles_x * tiles_y * max(tiles_x, tiles_y) < 2^32
+static bool s16_magic_fits(const esr_conv_desc* d, int rows)
 {
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->ksize != 3 || nchunks != 3 || (nt != 2 && nt != 3) || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || d->post_wpacked || d->hilo) return false;
-    if (d->res_mode != ESR_RES_NONE && !s16_res_is_input(d)) return false;
-    if (d->split > 0 && d->split < d->cout) return false;
-    return true;
+    const long tx = (d->w + TILE - 1) / TILE, ty = (d->h + rows - 1) / rows;
+    return (double)d->n * tx * ty * (tx > ty ? tx : ty) < 4294967296.0;
 }
 
-static bool conv48rq_takes(const esr_conv_desc* d);
-
-// conv64m_kernel<.., 3, true>'s descriptors (round 6): ESDB's c{j}_r -- the merged BSConvU + input + border table + GELU over 48 channels, plain
-// (conv48r_kernel's shape) or fp16 with the next distillation Linear + GELU (conv48rq_kernel's shape) -- from 256 tiles of 16 x 16: the kernel's
-// OWN tile, so that a 256 x 256 image alone and the same image inside a batch take the same kernel (its accumulation order differs from
-// conv48r_kernel's / conv_s16_kernel's; tests/test_gpu_big.py::test_16bit_batch_equals_per_image)
-static bool esdb_r_takes(const esr_conv_desc* d)
+// k's grid of 16-pixel-wide tiles of `rows` rows, with its magic divisors
+static void s16_tile_grid(S16K& k, int rows)
 {
-    const int nt = esr_round_up(d->cout, 16) / 16;
-    if (!d->border_bias || d->act != ESR_ACT_GELU || !s16_res_is_input(d) || nt != 3) return false;
-    if ((long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) < 256) return false;
-    return d->post_wpacked ? (conv48rq_takes(d) && d->post_act == ESR_ACT_GELU) : conv48r_shape(d);
-}
-
-static bool conv48r_takes(const esr_conv_desc* d)
-{
-    return conv48r_shape(d) && (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 31) / 32) >= 256;
-}
-
-// conv64r_kernel's descriptors: a 3x3 over 64 physical input channels with 2 or 4 output tiles, at least one 16 x 16 tile per CU, no
-// residual from HBM, no split, no post chain, no border table, NHWC, one input tensor
-static bool conv64r_takes(const esr_conv_desc* d)
-{
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->ksize != 3 || nchunks != 4 || (nt != 2 && nt != 4) || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || d->post_wpacked || d->hilo || d->border_bias) return false;
-    if (d->act == ESR_ACT_GELU) return false;
-    if (d->res_mode != ESR_RES_NONE && !s16_res_is_input(d)) return false;
-    if (d->split > 0 && d->split < d->cout) return false;
-    return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256;
+    k.tiles_x = (k.W + TILE - 1) / TILE;
+    k.tiles_y = (k.H + rows - 1) / rows;
+    k.magic_x = k.tiles_x > 1 ? (unsigned)((0x100000000ull + k.tiles_x - 1) / k.tiles_x) : 0u;
+    k.magic_y = k.tiles_y > 1 ? (unsigned)((0x100000000ull + k.tiles_y - 1) / k.tiles_y) : 0u;
 }
 
 int s16_post_plan(const esr_conv_desc* d, int nt, int nchunks, int* pnt1, int* pnt2, int* post_lo, int* ring, size_t* lds);
 
-// conv48rp_kernel's descriptors: RLFB's c3_r -- 48 -> 48 (3 chunks, 3 tiles) with a residual from HBM that is not the input, the conv's
-// own result not stored, a post chain of 3 + 1 tiles without GELU -- from 256 tiles of 16 x 16.  Measured (tools/gpu_c48p.sh): one
-// 339 x 510 image 26 against conv_s16_kernel's 38.6 us, 0.219 against 0.265 ms at 32 x 256 x 256.
-static bool conv48rp_takes(const esr_conv_desc* d)
+// conv_s16_kernel's two-blocks-per-CU shape (4 waves, 16 x 16 tiles): the plain 3x3 with three output tiles whose weights fit half the
+// LDS, from 512 tiles (fewer tiles than resident blocks otherwise); on hi + lo pairs only a single image's head
+static bool s16_four_waves(const esr_conv_desc* d)
 {
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->ksize != 3 || nchunks != 3 || nt != 3 || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || !d->post_wpacked || !d->post2_wpacked) return false;
-    if (d->out0.ptr || d->border_bias || d->act == ESR_ACT_GELU || d->post_act == ESR_ACT_GELU) return false;
-    if (d->res_mode != ESR_RES_POST_ACT || s16_res_is_input(d)) return false;
+    const int nt = esr_round_up(d->cout, 16) / 16, nch = esr_round_up(d->cin, 16) / 16;
+    const long t16 = (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16);
+    const bool res_hbm = d->res_mode != ESR_RES_NONE && !s16_res_is_input(d);
+    if (d->ksize != 3 || nt != 3 || d->border_bias || d->post_wpacked || res_hbm || d->out_layout != ESR_NHWC || d->in_seg_stride != 0) return false;
+    if (d->hilo && !(d->hilo == ESR_HILO_OUT && nch == 1 && t16 < 4096)) return false;
+    return t16 >= 512 && s16_lds_bytes(nch, nt, 3, 4, RING_MIN, 1024) <= (size_t)LDS_LIMIT / 2;
+}
+
+// the kernels esr_conv2d_s16 chooses from (rfdb_tail_kernel aside: d->tail_wpacked selects it before the validation)
+enum class S16Path {
+    UNSUPPORTED,
+    C48RL,      // conv48rp_kernel<bf16, LRS>, 16 x 16 tiles
+    C64ML,      // conv64m_kernel<bf16, plain, HL>, 16 x 16 tiles
+    HILO_POST,  // conv_s16_kernel HILO with one post 1x1, 8 waves
+    HILO_4W,    // conv_s16_kernel HILO, 4 waves on 16 x 16 tiles
+    HILO,       // conv_s16_kernel HILO, 8 waves
+    C48RP,      // conv48rp_kernel, 16 x 16 tiles
+    C64M,       // conv64m_kernel, 16 x 16 tiles
+    C48RQ,      // conv48rq_kernel, 16 x 16 tiles
+    C64R,       // conv64r_kernel, 16 x 16 tiles
+    C48R16,     // conv48r_kernel on 16 x 16 tiles
+    C48R32,     // conv48r_kernel on 16 x 32 tiles
+    POST,       // conv_s16_kernel with a post chain, 8 waves
+    S16_4W,     // conv_s16_kernel, 4 waves on 16 x 16 tiles
+    S16,        // conv_s16_kernel, 8 waves on 16 x 32 tiles
+};
+
+// The kernel a descriptor that passed esr_conv2d_s16's validation runs on, the candidates in order of precedence.  The specialised
+// kernels (conv48r* / conv64*) all need a 3x3, NHWC output, one input tensor, no split, and at least one of their own tiles per CU: 256
+// of 16 x 16 (conv48r_kernel: of 16 x 32).  A candidate on 16 x 16 tiles is taken only while that grid fits the magic division, else the
+// next one is; `any_range` counts every grid as fitting (esr_s16_block_waves: the kernel's shape, not the launch).
+static S16Path s16_select(const esr_conv_desc* d, bool any_range)
+{
+    const int nt = esr_round_up(d->cout, 16) / 16, nch = esr_round_up(d->cin, 16) / 16;
+    const long tx = (d->w + TILE - 1) / TILE, t16 = (long)d->n * tx * ((d->h + 15) / 16), t32 = (long)d->n * tx * ((d->h + 31) / 32);
+    const bool fits16 = any_range || s16_magic_fits(d, 16);
+    const bool post = d->post_wpacked != nullptr, gelu = d->act == ESR_ACT_GELU, post_gelu = d->post_act == ESR_ACT_GELU;
+    const bool reg = d->ksize == 3 && d->out_layout == ESR_NHWC && d->in_seg_stride == 0 && !(d->split > 0 && d->split < d->cout);
+    const bool reg16 = reg && t16 >= 256 && fits16;
+    const bool res_in = s16_res_is_input(d), no_res_hbm = d->res_mode == ESR_RES_NONE || res_in;
+    // the post chain's fused variant, every post image resident in the storage's full precision (bf16: hi + lo)
     int pnt1 = 0, pnt2 = 0, post_lo = 0, ring = 0;
     size_t lds = 0;
-    if (s16_post_plan(d, nt, nchunks, &pnt1, &pnt2, &post_lo, &ring, &lds) != ESR_OK) return false;
-    if (pnt1 != 3 || pnt2 != 1 || post_lo != (d->storage == ESR_STORE_BF16 ? 1 : 0)) return false;
-    const long tx = (d->w + TILE - 1) / TILE;
-    return (long)d->n * tx * ((d->h + 15) / 16) >= 256;
-}
+    const bool planned = post && s16_post_plan(d, nt, nch, &pnt1, &pnt2, &post_lo, &ring, &lds) == ESR_OK;
+    const bool full_post = planned && post_lo == (d->storage == ESR_STORE_BF16 ? 1 : 0);
 
-// conv48rq_kernel's descriptors: a 3x3 over 48 physical input channels with three output tiles whose result is stored AND feeds one post 1x1 of
-// two output tiles (ESDB c{j}_r -> c{j+1}_d, team18_bsrn.py:150-163), no residual from HBM, fp16 storage (high-part post images only), from
-// 256 tiles of 16 x 16
-static bool conv48rq_takes(const esr_conv_desc* d)
-{
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->storage != ESR_STORE_F16 || d->ksize != 3 || nchunks != 3 || nt != 3 || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || d->hilo) return false;
-    if (!d->post_wpacked || d->post2_wpacked || !d->out0.ptr || (d->split > 0 && d->split < d->cout)) return false;
-    if (d->res_mode != ESR_RES_NONE && !s16_res_is_input(d)) return false;
-    int pnt1 = 0, pnt2 = 0, post_lo = 0, ring = 0;
-    size_t lds = 0;
-    if (s16_post_plan(d, nt, nchunks, &pnt1, &pnt2, &post_lo, &ring, &lds) != ESR_OK) return false;
-    if (pnt1 != 2 || pnt2 != 0 || post_lo != 0) return false;
-    return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256;
-}
-
-// conv64rq_kernel's descriptors: a 3x3 over 64 physical input channels with four output tiles whose result is stored AND feeds one post 1x1
-// of two output tiles (RFDB c{j}_r -> c{j+1}_d, rfdn_baseline/block.py:150-160), no residual from HBM, LeakyReLU / none, from 256 tiles of 16 x 16
-static bool conv64rq_takes(const esr_conv_desc* d)
-{
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->ksize != 3 || nchunks != 4 || nt != 4 || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || d->hilo || d->border_bias) return false;
-    if (!d->post_wpacked || d->post2_wpacked || !d->out0.ptr || (d->split > 0 && d->split < d->cout)) return false;
-    if (d->act == ESR_ACT_GELU || d->post_act == ESR_ACT_GELU) return false;
-    if (d->res_mode != ESR_RES_NONE && !s16_res_is_input(d)) return false;
-    int pnt1 = 0, pnt2 = 0, post_lo = 0, ring = 0;
-    size_t lds = 0;
-    if (s16_post_plan(d, nt, nchunks, &pnt1, &pnt2, &post_lo, &ring, &lds) != ESR_OK) return false;
-    if (pnt1 != 2 || pnt2 != 0 || post_lo != (d->storage == ESR_STORE_BF16 ? 1 : 0)) return false;
-    return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256;
-}
-
-// conv48rp_kernel<bf16, LRS>'s descriptors: the LR conv of a 48-channel network on hi + lo pairs -- 48 -> 48 (3 chunks, 3 tiles), residual pair
-// from HBM added before the activation, output pair, no post chain -- from 256 tiles of 16 x 16
-static bool conv48rl_takes(const esr_conv_desc* d)
-{
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->storage != ESR_STORE_BF16 || d->hilo != (ESR_HILO_RES | ESR_HILO_OUT) || d->hilo_stride <= 0) return false;
-    if (d->ksize != 3 || nchunks != 3 || nt != 3 || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || d->post_wpacked || d->border_bias) return false;
-    if (d->res_mode != ESR_RES_PRE_ACT || d->act == ESR_ACT_GELU || (d->split > 0 && d->split < d->cout)) return false;
-    return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256;
-}
-
-// conv64m_kernel<bf16, plain, HL>'s descriptors: the LR conv of a 64-channel network on hi + lo pairs (RFDN: LR_conv(out_B) + out_fea,
-// rfdn_baseline/RFDN.py:50-52) -- 64 -> 64 (4 chunks, 4 tiles), residual pair from HBM added before the activation, output pair, no post
-// chain -- from 256 tiles of 16 x 16
-static bool conv64ml_takes(const esr_conv_desc* d)
-{
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    if (d->storage != ESR_STORE_BF16 || d->hilo != (ESR_HILO_RES | ESR_HILO_OUT) || d->hilo_stride <= 0) return false;
-    if (d->ksize != 3 || nchunks != 4 || nt != 4 || d->out_layout != ESR_NHWC || d->in_seg_stride != 0 || d->post_wpacked || d->border_bias) return false;
-    if (d->res_mode != ESR_RES_PRE_ACT || !d->res.ptr || d->act == ESR_ACT_GELU || (d->split > 0 && d->split < d->cout)) return false;
-    return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256;
+    // conv48rp_kernel: RLFB's c3_r -- 48 -> 48 with a residual from HBM that is not the input, the conv's own result not stored, a post
+    // chain of 3 + 1 tiles without GELU.  Measured (tools/gpu_c48p.sh): one 339 x 510 image 26 against conv_s16_kernel's 38.6 us, 0.219
+    // against 0.265 ms at 32 x 256 x 256.  (Tested ahead of the hi + lo paths: the validation refuses hi + lo with a second post conv, and
+    // the shape query has always answered this kernel for such a descriptor.)
+    if (reg16 && nch == 3 && nt == 3 && full_post && pnt1 == 3 && pnt2 == 1 && !d->out0.ptr && !d->border_bias && !gelu && !post_gelu &&
+        d->res_mode == ESR_RES_POST_ACT)
+        return S16Path::C48RP;
+    if (d->hilo) {
+        // conv48rp_kernel<bf16, LRS> / conv64m_kernel<bf16, plain, HL>: the LR conv of a 48- / 64-channel network (RFDN: LR_conv(out_B) +
+        // out_fea, rfdn_baseline/RFDN.py:50-52) -- residual pair from HBM added before the activation, output pair, no post chain
+        const bool lr = d->storage == ESR_STORE_BF16 && d->hilo == (ESR_HILO_RES | ESR_HILO_OUT) && d->hilo_stride > 0 && reg16 && !post &&
+                        !d->border_bias && d->res_mode == ESR_RES_PRE_ACT && !gelu;
+        if (lr && nch == 3 && nt == 3) return S16Path::C48RL;
+        if (lr && nch == 4 && nt == 4 && d->res.ptr) return S16Path::C64ML;
+        // the head with block 1's first distillation 1x1 in its epilogue (RFDN: 4 main tiles, BSRN: 3; 2 post tiles) + the hi + lo store
+        if (post) return pnt1 == 2 ? S16Path::HILO_POST : S16Path::UNSUPPORTED;
+        // the head of a 48-channel network (16 input slots, hi + lo store) on single images: the two-blocks-per-CU shape (one 339 x 510
+        // image: 17.5 against 19.5 us; a batch of 32 is 12 % faster on the 8-wave shape)
+        if (nt == 3 && d->hilo == ESR_HILO_OUT && nch == 1 && t16 >= 512 && t16 < 4096 && fits16) return S16Path::HILO_4W;
+        return S16Path::HILO;
+    }
+    // conv48rq_kernel: a 48 -> 48 3x3 whose result is stored AND feeds one post 1x1 of two output tiles (ESDB c{j}_r -> c{j+1}_d,
+    // team18_bsrn.py:150-163), fp16 storage (high-part post images only)
+    const bool c48rq = reg16 && d->storage == ESR_STORE_F16 && nch == 3 && nt == 3 && d->out0.ptr && no_res_hbm && full_post && pnt1 == 2 && pnt2 == 0;
+    // ESDB's c{j}_r -- the merged BSConvU + input + border table + GELU over 48 channels, plain or as conv48rq_kernel's shape with a GELU
+    // post -- on conv64m_kernel's three-chunk form, from 256 tiles of the kernel's OWN 16 x 16: a 256 x 256 image alone and the same image
+    // inside a batch take the same kernel (tests/test_gpu_big.py::test_16bit_batch_equals_per_image)
+    const bool esdb_r = reg16 && nch == 3 && nt == 3 && d->border_bias && gelu && res_in && (!post || (c48rq && post_gelu));
+    // the 64-channel 3x3s (RFDB c{j}_r, c3_r, c4): no border table, no GELU; four output tiles on conv64m_kernel (with the next distillation
+    // 1x1 of two output tiles, stored result, rfdn_baseline/block.py:150-160), two on conv64r_kernel
+    const bool c64 = reg16 && nch == 4 && !d->border_bias && !gelu && no_res_hbm;
+    const bool c64rq = c64 && nt == 4 && d->out0.ptr && !post_gelu && full_post && pnt1 == 2 && pnt2 == 0;
+    const bool c64r = c64 && (nt == 2 || nt == 4) && !post;
+    if (esdb_r || c64rq || (c64r && nt == 4)) return S16Path::C64M;
+    if (c48rq) return S16Path::C48RQ;
+    if (c64r) return S16Path::C64R;
+    // conv48r_kernel: a 48-channel 3x3 with 2 or 3 output tiles; single images (fewer than 1024 tiles of 16 x 32, well inside the magic
+    // range) on 16 x 16 tiles.  A post chain stays on conv_s16_kernel: the PNT1 = 2 instantiation -- ESDB c{j}_r + the next distillation
+    // 1x1, two GELUs per pixel -- measured 0.396 against 0.368 ms at 32 x 270 x 480: with ONE wave per SIMD the ~380 VALU instructions of
+    // a row pair's epilogue have to fit the shadow of its 102 MFMAs exactly, conv_s16_kernel's second wave absorbs them
+    if (reg && nch == 3 && (nt == 2 || nt == 3) && !post && no_res_hbm && t32 >= 256) return t32 < 1024 ? S16Path::C48R16 : S16Path::C48R32;
+    if (post) return S16Path::POST;
+    // the plain 48-channel 3x3 (RLFB c1_r / c2_r): 46 KB of weights + a ring of three 11 KB stages fit 80 KB, so TWO 4-wave blocks share a
+    // CU -- their stage barriers are independent and one block's memory phase runs under the other's MFMAs (-2.5 % on the kernel, +1 %
+    // RLFN, A/B; 16 x 16 tiles carry more halo and the ring is the shortest, which is why it is not more)
+    if (s16_four_waves(d) && fits16) return S16Path::S16_4W;
+    return S16Path::S16;
 }
 
 // rfdb_tail_kernel's descriptors (ABI v12, esr_c64m.hip): a 3x3 over 64 physical input channels with <= 32 outputs whose rounded result is the
@@ -1024,9 +1025,7 @@ static bool rfdb_tail_takes(const esr_conv_desc* d)
     if (!d->post_out.ptr || (d->post_out.pitch & 7) || (d->post_out.coff & 7) || d->post_out.coff + esr_round_up(d->post_cout, 8) > d->post_out.pitch) return false;
     const double px = (double)d->h * d->w * 2.0, lim = 2147483647.0 - 1048576.0;
     if (px * d->in.pitch >= lim || px * d->tail_cat.pitch >= lim || px * d->out0.pitch >= lim || px * d->post_out.pitch >= lim) return false;
-    const long tx = (d->w + TILE - 1) / TILE, ty = (d->h + 15) / 16;
-    if ((long)d->n * tx * ty < 256) return false;
-    return (double)d->n * tx * ty * (tx > ty ? tx : ty) < 4294967296.0;
+    return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256 && s16_magic_fits(d, 16);
 }
 
 static int run_rfdb_tail(const esr_conv_desc* d, bool bf16, hipStream_t st)
@@ -1060,24 +1059,8 @@ static int run_rfdb_tail(const esr_conv_desc* d, bool bf16, hipStream_t st)
     k.p1_cout8 = esr_round_up(d->post_cout, 8);
     k.p1_slope = d->post_act == ESR_ACT_LRELU ? d->slope : (d->post_act == ESR_ACT_RELU ? 0.f : 1.f);
     k.out_layout = ESR_NHWC;
-    k.tiles_x = (d->w + TILE - 1) / TILE;
-    k.tiles_y = (d->h + 15) / 16;
-    k.magic_x = k.tiles_x > 1 ? (unsigned)((0x100000000ull + k.tiles_x - 1) / k.tiles_x) : 0u;
-    k.magic_y = k.tiles_y > 1 ? (unsigned)((0x100000000ull + k.tiles_y - 1) / k.tiles_y) : 0u;
+    s16_tile_grid(k, 16);
     return esr_launch_rfdb_tail(k, bf16, st);
-}
-
-// 1: conv48r_kernel / conv48rp_kernel (one 4-wave block per CU, weights in registers), 4: conv_s16_kernel's two-blocks-per-CU shape (4
-// waves, 16 x 16 tiles), 8: one 8-wave block per CU on 16 x 32 tiles
-int s16_block_waves(const esr_conv_desc* d)
-{
-    if (esdb_r_takes(d) || conv48r_takes(d) || conv48rp_takes(d) || conv64r_takes(d) || conv48rl_takes(d) || conv48rq_takes(d) || conv64rq_takes(d) || conv64ml_takes(d)) return 1;
-    const int nt = esr_round_up(d->cout, 16) / 16, nchunks = esr_round_up(d->cin, 16) / 16;
-    const bool res_hbm = d->res_mode != ESR_RES_NONE && !s16_res_is_input(d);
-    if (d->ksize != 3 || nt != 3 || d->border_bias || d->post_wpacked || res_hbm || d->out_layout != ESR_NHWC || d->in_seg_stride != 0) return 8;
-    if (d->hilo && !(d->hilo == ESR_HILO_OUT && nchunks == 1 && (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) < 4096)) return 8;   // hi + lo pairs: only a single image's head takes the 4-wave shape
-    if ((long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) < 512) return 8;           // fewer tiles than resident blocks
-    return s16_lds_bytes(nchunks, nt, 3, 4, RING_MIN, 1024) <= (size_t)LDS_LIMIT / 2 ? 4 : 8;
 }
 
 // decides how a descriptor with a post chain runs: fills the tile counts and whether the low-part images are resident;
@@ -1340,8 +1323,18 @@ extern "C" int esr_pack_input_s16(const esr_conv_desc* d, void* hip_stream)
     return esr_check_launch("pack_input_kernel launch");
 }
 
-// called by esr_conv2d_f32 (esr_hip.hip) for descriptors with 16-bit storage
-int esr_s16_block_waves(const esr_conv_desc* d) { return s16_block_waves(d); }
+// called by esr_conv_block_waves (esr_hip.hip) for descriptors with 16-bit storage: 1 for the specialised kernels (conv48r* / conv64*),
+// 4 for conv_s16_kernel's two-blocks-per-CU shape (4 waves, 16 x 16 tiles), 8 for one 8-wave block per CU on 16 x 32 tiles
+int esr_s16_block_waves(const esr_conv_desc* d)
+{
+    switch (s16_select(d, true)) {
+        case S16Path::C48RL: case S16Path::C64ML: case S16Path::C48RP: case S16Path::C64M:
+        case S16Path::C48RQ: case S16Path::C64R: case S16Path::C48R16: case S16Path::C48R32:
+            return 1;
+        default:
+            return s16_four_waves(d) ? 4 : 8;
+    }
+}
 
 int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
 {
@@ -1350,9 +1343,8 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     if (d->compute != (bf16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return ESR_ERR_BAD_ARG;   // operand type = storage type
     if (d->in_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;                                  // the NCHW head runs on conv_f32_kernel
     if (d->blocked8) return ESR_ERR_UNSUPPORTED;                                               // an fp32 feature
-    // ESR_RES_GATE: conv_s16_kernel's residual stages carry the gate operand.  Every specialised kernel's predicate (conv48r / conv48rp / conv48rq /
-    // conv64r / conv64rq / conv48rl / conv64ml / esdb_r / rfdb_tail) requires no residual, one that is the input (pre-activation) or a pre / post-
-    // activation one, so a gate never reaches them
+    // ESR_RES_GATE: conv_s16_kernel's residual stages carry the gate operand.  Every specialised kernel (s16_select, rfdb_tail_takes) requires
+    // no residual, one that is the input (pre-activation) or a pre / post-activation one, so a gate never reaches them
     if (d->res_mode == ESR_RES_GATE && (d->act != ESR_ACT_NONE || d->tail_wpacked || d->post_wpacked || d->hilo || d->border_bias || d->out_layout != ESR_NHWC))
         return ESR_ERR_UNSUPPORTED;
     if (d->tail_wpacked) return rfdb_tail_takes(d) ? run_rfdb_tail(d, bf16, static_cast<hipStream_t>(hip_stream)) : ESR_ERR_UNSUPPORTED;
@@ -1438,7 +1430,7 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     if (d->res_mode != ESR_RES_NONE && (double)d->h * d->w * d->res.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
     const int pairs = (d->ksize * d->ksize + 1) / 2;
 
-    S16K k;
+    S16K k{};
     k.x = static_cast<const char*>(d->in.ptr);
     k.wp = static_cast<const char*>(d->wpacked);
     k.bias = reinterpret_cast<const float*>(k.wp + (size_t)wchunks * pairs * nt * 1024);
@@ -1457,8 +1449,6 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     k.act = d->act;
     k.slope = d->act == ESR_ACT_LRELU ? d->slope : (d->act == ESR_ACT_RELU ? 0.f : 1.f);
     k.res_mode = d->res_mode;
-    k.res_in = 0;
-    k.nres = 0;
     if (s16_res_is_input(d)) {
         k.res_in = 1;                               // residual == input: added from the staged tile, no residual loads
         k.res_mode = ESR_RES_NONE;
@@ -1467,21 +1457,14 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     k.w_chunks = wchunks;
     k.hilo_out = (hilo & ESR_HILO_OUT) ? 1 : 0;
     k.res_lo_stride = (hilo & ESR_HILO_RES) ? d->hilo_stride : 0;
-    k.wm32 = nullptr; k.pm32 = nullptr; k.pbias1 = nullptr;
     if (k.hilo_out) {                                              // the low parts leave through the y1 stores
         k.y1 = k.y0 + d->hilo_stride;
         k.y1_pitch = k.y0_pitch;
         k.y1_coff = k.y0_coff + split;                             // (the kernel subtracts `split` from y1's channel offsets)
     }
     k.out_layout = d->out_layout;
-    k.tiles_x = (d->w + TILE - 1) / TILE;
-    k.tiles_y = (d->h + 31) / 32;
-    k.magic_x = k.tiles_x > 1 ? (unsigned)((0x100000000ull + k.tiles_x - 1) / k.tiles_x) : 0u;
-    k.magic_y = k.tiles_y > 1 ? (unsigned)((0x100000000ull + k.tiles_y - 1) / k.tiles_y) : 0u;
-    {
-        const double nt_all = (double)d->n * k.tiles_x * k.tiles_y;
-        if (nt_all * (k.tiles_x > k.tiles_y ? k.tiles_x : k.tiles_y) >= 4294967296.0) return ESR_ERR_UNSUPPORTED;   // magic division range
-    }
+    s16_tile_grid(k, 32);
+    if (!s16_magic_fits(d, 32)) return ESR_ERR_UNSUPPORTED;
     k.pw1 = static_cast<const char*>(d->post_wpacked); k.pw2 = static_cast<const char*>(d->post2_wpacked);
     k.py1 = static_cast<char*>(d->post_out.ptr); k.py2 = static_cast<char*>(d->post2_out.ptr);
     k.py1_pitch = d->post_out.pitch; k.py1_coff = d->post_out.coff; k.py2_pitch = d->post2_out.pitch; k.py2_coff = d->post2_out.coff;
@@ -1498,118 +1481,42 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
         k.seg_stride = d->hilo_stride;
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (hilo && conv48rl_takes(d)) {
-        S16K kp = k;
-        kp.tiles_y = (d->h + 15) / 16;
-        kp.magic_y = kp.tiles_y > 1 ? (unsigned)((0x100000000ull + kp.tiles_y - 1) / kp.tiles_y) : 0u;
-        const double nt_all = (double)d->n * kp.tiles_x * kp.tiles_y;
-        if (nt_all * (kp.tiles_x > kp.tiles_y ? kp.tiles_x : kp.tiles_y) < 4294967296.0) return esr_launch_conv48rp(kp, true, true, st);
-    }
-    if (hilo && conv64ml_takes(d)) {
-        S16K k4 = k;
-        k4.tiles_y = (d->h + 15) / 16;
-        k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-        k4.wm32 = k.wp + esr_m32_conv_offset(cin_phys, d->cout, 3);
-        const double nt_all = (double)d->n * k4.tiles_x * k4.tiles_y;
-        if (nt_all * (k4.tiles_x > k4.tiles_y ? k4.tiles_x : k4.tiles_y) < 4294967296.0) return esr_launch_conv64m(k4, true, false, true, st);
-    }
-    if (hilo && post) {
-        // the head with block 1's first distillation 1x1 in its epilogue (RFDN: 4 main tiles, BSRN: 3; 2 post tiles) + the hi + lo store
-        if (pnt2 != 0 || pnt1 != 2 || (nt != 3 && nt != 4)) return ESR_ERR_UNSUPPORTED;
-        if (nt == 3) return launch_s16<3, 3, S16_NW, true, false, 2, 0, true>(k, lds, st);
-        return launch_s16<4, 3, S16_NW, true, false, 2, 0, true>(k, lds, st);
-    }
-    if (hilo) {
-        const long t16 = (long)d->n * k.tiles_x * ((d->h + 15) / 16);
-        if (nt == 3 && hilo == ESR_HILO_OUT && wchunks == 1 && t16 >= 512 && t16 < 4096) {
-            // the head of a 48-channel network (16 input slots, hi + lo store) on single images: the two-blocks-per-CU shape on 16 x 16 tiles
-            // (one 339 x 510 image: 17.5 against 19.5 us; a batch of 32 is 12 % faster on the 8-wave shape)
-            S16K k4 = k;
-            k4.ring = RING_MIN;
-            k4.tiles_y = (d->h + 15) / 16;
-            k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-            const double nt_all = (double)d->n * k4.tiles_x * k4.tiles_y;
-            if (nt_all * (k4.tiles_x > k4.tiles_y ? k4.tiles_x : k4.tiles_y) < 4294967296.0)
-                return launch_s16<3, 3, 4, true, false, 0, 0, true>(k4, s16_lds_bytes(wchunks, nt, 3, 4, RING_MIN, 1024), st);
-        }
-        if (nt == 3) return launch_s16<3, 3, S16_NW, true, false, 0, 0, true>(k, lds, st);
-        return launch_s16<4, 3, S16_NW, true, false, 0, 0, true>(k, lds, st);
-    }
-    if (conv48rp_takes(d)) {
-        // RLFB c3_r (+ block input) -> c5 -> esa.conv1 on 16 x 16 tiles
-        S16K kp = k;
-        kp.tiles_y = (d->h + 15) / 16;
-        kp.magic_y = kp.tiles_y > 1 ? (unsigned)((0x100000000ull + kp.tiles_y - 1) / kp.tiles_y) : 0u;
-        const double nt_all = (double)d->n * kp.tiles_x * kp.tiles_y;
-        if (nt_all * (kp.tiles_x > kp.tiles_y ? kp.tiles_x : kp.tiles_y) < 4294967296.0)
-            return esr_launch_conv48rp(kp, bf16, false, st);
-    }
-    // round 6 (last): ESDB's c{j}_r -- the merged BSConvU + input + GELU over 48 channels, plain or (fp16) with the next distillation Linear + GELU --
-    // on conv64m_kernel's three-chunk form
-    const bool esdb_r = esdb_r_takes(d);
-    if (esdb_r || conv64rq_takes(d) || (conv64r_takes(d) && nt == 4)) {
-        // round 6: the 64 -> 64 3x3s (RFDB c1_r / c2_r with the next distillation 1x1, c3_r) on v_mfma_f32_32x32x16 (esr_c64m.hip)
-        S16K k4 = k;
-        k4.tiles_y = (d->h + 15) / 16;
-        k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-        k4.wm32 = k.wp + esr_m32_conv_offset(cin_phys, d->cout, 3);
-        if (post) {
-            k4.pm32 = k.pw1 + esr_m32_post_offset(d->cout, d->post_cout);
-            k4.pbias1 = reinterpret_cast<const float*>(k.pw1 + (size_t)2 * (esr_round_up(d->cout, 16) / 16) * (esr_round_up(d->post_cout, 16) / 16) * 1024);
-        }
-        const double nt_all = (double)d->n * k4.tiles_x * k4.tiles_y;
-        if (nt_all * (k4.tiles_x > k4.tiles_y ? k4.tiles_x : k4.tiles_y) < 4294967296.0) return esr_launch_conv64m(k4, bf16, post, false, st);
-    }
-    if (conv48rq_takes(d)) {
-        S16K k4 = k;
-        k4.tiles_y = (d->h + 15) / 16;
-        k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-        const double nt_all = (double)d->n * k4.tiles_x * k4.tiles_y;
-        if (nt_all * (k4.tiles_x > k4.tiles_y ? k4.tiles_x : k4.tiles_y) < 4294967296.0) return esr_launch_conv48rq(k4, st);
-    }
-    if (conv64r_takes(d)) {
-        S16K k4 = k;
-        k4.tiles_y = (d->h + 15) / 16;
-        k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-        const double nt_all = (double)d->n * k4.tiles_x * k4.tiles_y;
-        if (nt_all * (k4.tiles_x > k4.tiles_y ? k4.tiles_x : k4.tiles_y) < 4294967296.0) {
-            // (two output tiles -- RFDB's c4; four take conv64m_kernel above)
-            return esr_launch_conv64r(k4, bf16, st);
-        }
-    }
-    if (conv48r_takes(d)) {
-        // (a post chain stays on conv_s16_kernel: the PNT1 = 2 instantiation -- ESDB c{j}_r + the next distillation 1x1, two GELUs per
-        // pixel -- measured 0.396 against 0.368 ms at 32 x 270 x 480: with ONE wave per SIMD the ~380 VALU instructions of a row pair's
-        // epilogue have to fit the shadow of its 102 MFMAs exactly, conv_s16_kernel's second wave absorbs them)
-        const bool ext = k.border != nullptr || k.res_in || d->act == ESR_ACT_GELU;
-        if ((long)d->n * k.tiles_x * k.tiles_y < 1024) {
-            // small launches (single images): 16 x 16 tiles
-            S16K k4 = k;
-            k4.tiles_y = (d->h + 15) / 16;
-            k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-            return esr_launch_conv48r(k4, bf16, nt, ext, 4, st);
-        }
-        return esr_launch_conv48r(k, bf16, nt, ext, 8, st);
-    }
-    if (post) {
-        const bool gres = k.res_mode != ESR_RES_NONE;
-        return bf16 ? launch_s16_post<true>(d->ksize, nt, gres, pnt1, pnt2, k, lds, st)
-                    : launch_s16_post<false>(d->ksize, nt, gres, pnt1, pnt2, k, lds, st);
-    }
-    // the plain 48-channel 3x3 (RLFB c1_r / c2_r): 46 KB of weights + a ring of three 11 KB stages fit 80 KB, so TWO 4-wave blocks
-    // share a CU -- their stage barriers are independent and one block's memory phase runs under the other's MFMAs (-2.5 % on the
-    // kernel, +1 % RLFN, A/B; 16 x 16 tiles carry more halo and the ring is the shortest, which is why it is not more)
-    if (s16_block_waves(d) == 4) {
-        const size_t lds4 = s16_lds_bytes(nchunks, nt, 3, 4, RING_MIN, 1024);
-        {
-            S16K k4 = k;
-            k4.ring = RING_MIN;
-            k4.tiles_y = (d->h + 15) / 16;
-            k4.magic_y = k4.tiles_y > 1 ? (unsigned)((0x100000000ull + k4.tiles_y - 1) / k4.tiles_y) : 0u;
-            const double nt_all = (double)d->n * k4.tiles_x * k4.tiles_y;
-            if (nt_all * (k4.tiles_x > k4.tiles_y ? k4.tiles_x : k4.tiles_y) < 4294967296.0)
-                return bf16 ? launch_s16<3, 3, 4, true, false>(k4, lds4, st) : launch_s16<3, 3, 4, false, false>(k4, lds4, st);
-        }
+    S16K k16 = k;                                                  // the 16 x 16-tile paths (their grid fits: s16_select)
+    s16_tile_grid(k16, 16);
+    const size_t lds4 = s16_lds_bytes(wchunks, nt, 3, 4, RING_MIN, 1024);      // the 4-wave shape: no post chain, one input tensor
+    const bool ext48 = k.border != nullptr || k.res_in || d->act == ESR_ACT_GELU;   // conv48r_kernel's border / residual / GELU epilogue
+    switch (s16_select(d, false)) {
+        case S16Path::UNSUPPORTED: return ESR_ERR_UNSUPPORTED;
+        case S16Path::C48RL: return esr_launch_conv48rp(k16, true, true, st);
+        case S16Path::C64ML:
+            k16.wm32 = k.wp + esr_m32_conv_offset(cin_phys, d->cout, 3);
+            return esr_launch_conv64m(k16, true, false, true, st);
+        case S16Path::HILO_POST:
+            return nt == 3 ? launch_s16<3, 3, S16_NW, true, false, 2, 0, true>(k, lds, st) : launch_s16<4, 3, S16_NW, true, false, 2, 0, true>(k, lds, st);
+        case S16Path::HILO_4W:
+            k16.ring = RING_MIN;
+            return launch_s16<3, 3, 4, true, false, 0, 0, true>(k16, lds4, st);
+        case S16Path::HILO:
+            return nt == 3 ? launch_s16<3, 3, S16_NW, true, false, 0, 0, true>(k, lds, st) : launch_s16<4, 3, S16_NW, true, false, 0, 0, true>(k, lds, st);
+        case S16Path::C48RP: return esr_launch_conv48rp(k16, bf16, false, st);
+        case S16Path::C64M:
+            k16.wm32 = k.wp + esr_m32_conv_offset(cin_phys, d->cout, 3);
+            if (post) {
+                k16.pm32 = k.pw1 + esr_m32_post_offset(d->cout, d->post_cout);
+                k16.pbias1 = reinterpret_cast<const float*>(k.pw1 + (size_t)2 * nt * (esr_round_up(d->post_cout, 16) / 16) * 1024);
+            }
+            return esr_launch_conv64m(k16, bf16, post, false, st);
+        case S16Path::C48RQ: return esr_launch_conv48rq(k16, st);
+        case S16Path::C64R: return esr_launch_conv64r(k16, bf16, st);
+        case S16Path::C48R16: return esr_launch_conv48r(k16, bf16, nt, ext48, 4, st);
+        case S16Path::C48R32: return esr_launch_conv48r(k, bf16, nt, ext48, 8, st);
+        case S16Path::POST:
+            return bf16 ? launch_s16_post<true>(d->ksize, nt, k.res_mode != ESR_RES_NONE, pnt1, pnt2, k, lds, st)
+                        : launch_s16_post<false>(d->ksize, nt, k.res_mode != ESR_RES_NONE, pnt1, pnt2, k, lds, st);
+        case S16Path::S16_4W:
+            k16.ring = RING_MIN;
+            return bf16 ? launch_s16<3, 3, 4, true, false>(k16, lds4, st) : launch_s16<3, 3, 4, false, false>(k16, lds4, st);
+        case S16Path::S16: break;
     }
     if (d->ksize == 3) return bf16 ? launch_s16_res<3, true>(nt, k, lds, st) : launch_s16_res<3, false>(nt, k, lds, st);
     return bf16 ? launch_s16_res<1, true>(nt, k, lds, st) : launch_s16_res<1, false>(nt, k, lds, st);

@@ -513,6 +513,22 @@ def test_block_shape_query_cpu():
                post_wpacked=fake(0x3000), post2_wpacked=fake(0x4000), post_cout=46, post2_cout=16)
     assert waves(32, 256, 256, 48, 46, **c3r) == 1 and waves(1, 339, 510, 48, 46, **c3r) == 1 and waves(1, 128, 128, 48, 46, **c3r) == 8
     assert waves(1, 339, 510, 48, 46, out0=L.View(fake(0x5000), 48, 0), **c3r) == 8          # its own result stored too: conv_s16_kernel
+    # a 3x3 whose stored result also feeds one post 1x1 of two output tiles: conv48rq_kernel (fp16 only) / conv64m_kernel (no GELU)
+    q = dict(out0=L.View(fake(0x5000), 64, 0), post_wpacked=fake(0x3000), post_cout=32)
+    assert waves(32, 256, 256, 48, 48, store="f16", **q) == 1 and waves(32, 256, 256, 48, 48, store="bf16", **q) == 8
+    assert waves(32, 256, 256, 64, 64, store="bf16", **q) == 1 and waves(32, 256, 256, 64, 64, store="bf16", post_act=L.ACT_GELU, **q) == 8
+    # ESDB's c{j}_r (border table + GELU + residual == input): conv64m_kernel from 256 tiles of 16 x 16, where conv48r_kernel needs 16 x 32
+    esdb = dict(store="bf16", act=L.ACT_GELU, border_bias=fake(0x6000), res_mode=L.RES_PRE_ACT, inp=L.View(fake(0x2000), 48, 0),
+                res=L.View(fake(0x2000), 48, 0))
+    assert waves(1, 256, 256, 48, 48, **esdb) == 1 and waves(1, 256, 240, 48, 48, **esdb) == 8
+    # the LR conv on hi + lo pairs (residual pair from HBM): conv48rp_kernel<bf16, LRS> / conv64m_kernel<.., HL>, which needs the residual
+    lr = dict(store="bf16", hilo=L.HILO_RES | L.HILO_OUT, hilo_stride=1 << 20, res_mode=L.RES_PRE_ACT, res=L.View(fake(0x1000), 64, 0))
+    assert waves(32, 256, 256, 48, 48, **lr) == 1 and waves(1, 128, 128, 48, 48, **lr) == 8
+    assert waves(32, 256, 256, 64, 64, **lr) == 1 and waves(32, 256, 256, 64, 64, **dict(lr, res=L.View(None, 64, 0))) == 8
+    # a single image's 48-channel hi + lo head (16 input slots): the two-blocks-per-CU shape; a batch stays on the 8-wave one
+    assert waves(1, 339, 510, 3, 48, store="bf16", hilo=L.HILO_OUT) == 4 and waves(32, 256, 256, 3, 48, store="bf16", hilo=L.HILO_OUT) == 8
+    # conv48rp_kernel's shape beyond the 16 x 16 tiles' magic-division range still reports that kernel (the launch takes conv_s16_kernel)
+    assert waves(16, 256, 65536, 48, 46, **c3r) == 1
     assert lib.esr_conv_block_waves(None) == 0
 
 
