@@ -361,13 +361,10 @@ __global__ __launch_bounds__(256, 2) void bsconv_kernel(const BsK p)
 template <int NTP, int NTD, int ST>
 int launch_bs(const BsK& k, size_t lds, hipStream_t st)
 {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bsconv_kernel<NTP, NTD, ST>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&bsconv_kernel<NTP, NTD, ST>), 160 * 1024, "bsconv_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 512 ? ntiles : 512;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_2_PER_CU);
     esr_note_kernel("bsconv_kernel<%d, %d, %d>", NTP, NTD, ST);
     hipLaunchKernelGGL((bsconv_kernel<NTP, NTD, ST>), dim3(grid), dim3(256), lds, st, k);
     return esr_check_launch("bsconv_kernel launch");

@@ -31,7 +31,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include <utility>
 #include <type_traits>
 
@@ -643,19 +642,10 @@ int launch_conv64m(const S16K& k, hipStream_t st)
 {
     constexpr int LDS = (POST ? M_LDS_POST : M_LDS_PLAIN) + (GB ? 3072 : 0);
     static_assert(LDS <= LDS_LIMIT, "LDS map");
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv64m_kernel<BF16, POST, HL, NCH, GB>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(conv64m_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&conv64m_kernel<BF16, POST, HL, NCH, GB>), LDS, "conv64m_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_1_PER_CU);
     // (the symbol as rocprofv3 prints it -- every template argument, defaulted ones included: tools/pmc_traffic.py joins on it)
     esr_note_kernel("conv64m_kernel<%s, %s, %s, %d, %s>", esr_tf(BF16), esr_tf(POST), esr_tf(HL), NCH, esr_tf(GB));
     hipLaunchKernelGGL((conv64m_kernel<BF16, POST, HL, NCH, GB>), dim3(grid), dim3(256), LDS, st, k);
@@ -1006,19 +996,10 @@ __global__ __launch_bounds__(256, 1) void rfdb_tail_kernel(const S16K p)
 template <bool BF16, int NCH, bool GB>
 int launch_rfdb_tail(const S16K& k, hipStream_t st)
 {
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rfdb_tail_kernel<BF16, NCH, GB>), hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(rfdb_tail_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&rfdb_tail_kernel<BF16, NCH, GB>), T_LDS, "rfdb_tail_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_1_PER_CU);
     esr_note_kernel("rfdb_tail_kernel<%s, %d, %s>", esr_tf(BF16), NCH, esr_tf(GB));
     hipLaunchKernelGGL((rfdb_tail_kernel<BF16, NCH, GB>), dim3(grid), dim3(256), T_LDS, st, k);
     return esr_check_launch("rfdb_tail_kernel launch");
@@ -1036,9 +1017,6 @@ int esr_launch_rfdb_tail(const S16K& k, bool bf16, hipStream_t st)
     if (k.nchunks != 4 || k.border || k.act == ESR_ACT_GELU) return ESR_ERR_UNSUPPORTED;
     return bf16 ? launch_rfdb_tail<true, 4, false>(k, st) : launch_rfdb_tail<false, 4, false>(k, st);
 }
-
-namespace {
-}  // namespace
 
 int esr_launch_conv64m(const S16K& k, bool bf16, bool post, bool hl, hipStream_t st)
 {
@@ -1096,36 +1074,6 @@ size_t esr_m32_post_offset(int cin, int cout)
 // (output channel 32 half + i), element j:
 //   ks = 2 s + u (s = 0 .. 2, u = 0 | 1): slot 16 u + 8 h + j of segment s -- the B operand is 16 bytes of the segment's pixel as stored;
 //   ks = 6 + t (t = 0 | 1): channel 8 (2 t + (j >> 2)) + 4 h + (j & 3) of the 3x3's result -- the B operand is two of its D blocks, rounded
-namespace {
-inline uint16_t m_to16(double v, int compute)
-{
-    if (compute == ESR_COMPUTE_BF16) {
-        const float f = (float)v;
-        uint32_t u;
-        memcpy(&u, &f, 4);
-        if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    }
-    const _Float16 h = (_Float16)(float)v;
-    uint16_t r;
-    memcpy(&r, &h, 2);
-    return r;
-}
-inline double m_from16(uint16_t h, int compute)
-{
-    if (compute == ESR_COMPUTE_BF16) {
-        const uint32_t u = (uint32_t)h << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    }
-    _Float16 v;
-    memcpy(&v, &h, 2);
-    return (double)(float)v;
-}
-}  // namespace
-
 extern "C" size_t esr_packed_tail_s16_bytes(int nseg, int seg_c, int mid_c, int cout)
 {
     if (nseg != 3 || seg_c <= 0 || seg_c > 32 || mid_c <= 0 || mid_c > 32 || cout <= 0 || cout > 64) return 0;
@@ -1156,8 +1104,8 @@ extern "C" int esr_pack_tail_s16(const float* w, const float* bias, int nseg, in
                         }
                         if (col < 0 || oc >= cout) continue;
                         const double wv = w[(size_t)oc * kin + col];
-                        const uint16_t hi = m_to16(wv, compute);
-                        const uint16_t lo = m_to16(wv - m_from16(hi, compute), compute);
+                        const uint16_t hi = esr_host_to16((float)wv, compute);
+                        const uint16_t lo = esr_host_to16((float)(wv - esr_host_from16(hi, compute)), compute);
                         const size_t e = (size_t)(32 * h + i) * 8 + j;
                         o[(size_t)((ks * 2 + half) * 2 + 0) * 512 + e] = hi;
                         o[(size_t)((ks * 2 + half) * 2 + 1) * 512 + e] = lo;

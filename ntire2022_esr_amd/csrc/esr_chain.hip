@@ -30,7 +30,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 
 #include "esr_s16_dev.h"
 
@@ -652,18 +651,9 @@ int launch_rlfb_chain(const ChainK& k, hipStream_t st)
 {
     constexpr int LDS = ChGeo<G>::LDS + CH_TRACE_LDS;
     static_assert(LDS <= LDS_LIMIT, "rings fit the LDS");
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rlfb_chain_kernel<BF16, G>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(rlfb_chain_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
-    const int grid = k.njobs < 256 ? k.njobs : 256;
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&rlfb_chain_kernel<BF16, G>), LDS, "rlfb_chain_kernel")) return rc;
+    const int grid = esr_persistent_grid(k.njobs, ESR_BLOCKS_1_PER_CU);
     esr_note_kernel("rlfb_chain_kernel<%s, %d>", esr_tf(BF16), G);
     hipLaunchKernelGGL((rlfb_chain_kernel<BF16, G>), dim3(grid), dim3(64 * CH_NW), LDS, st, k);
     return esr_check_launch("rlfb_chain_kernel launch");

@@ -602,34 +602,6 @@ int launch_esa_mfma(const EsaK& k, int np0, int np1, hipStream_t st)
     return esr_check_launch("esa_apply_mfma_kernel launch");
 }
 
-// 16-bit rounding on the host (RNE), as the kernels' conversions
-static unsigned short host_to16(float f, int storage)
-{
-    if (storage == ESR_STORE_BF16) {
-        unsigned u;
-        memcpy(&u, &f, 4);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (unsigned short)(u >> 16);
-    }
-    const _Float16 h = (_Float16)f;
-    unsigned short r;
-    memcpy(&r, &h, 2);
-    return r;
-}
-static float host_from16(unsigned short h, int storage)
-{
-    if (storage == ESR_STORE_BF16) {
-        const unsigned u = (unsigned)h << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    }
-    _Float16 v;
-    memcpy(&v, &h, 2);
-    return (float)v;
-}
-
 // ---- depthwise 3x3, zero padding, fused residual / activation -------------------------------------
 // thread = (pixel, quad of 4 channels); weights [tap][cp] + bias[cp] in LDS.  Memory-bound: the 9 taps of a
 // pixel are served from L1/L2 (each input float4 is read by 9 neighbouring threads).
@@ -888,8 +860,8 @@ int esr_pack_apply_post(const float* w0, const float* b0, const float* w1, const
                     for (int j = 0; j < 8; ++j) {
                         const int oc = chan(t, l & 15), ic = 32 * q + 8 * (l >> 4) + j;
                         const float w = (oc < cout0 && ic < cin) ? w0[(size_t)oc * cin + ic] : 0.f;
-                        const unsigned short hi = host_to16(w, storage);
-                        img[((size_t)((lo * nt0 + t) * np + q) * 64 + l) * 8 + j] = lo ? host_to16(w - host_from16(hi, storage), storage) : hi;
+                        const unsigned short hi = esr_host_to16(w, storage);
+                        img[((size_t)((lo * nt0 + t) * np + q) * 64 + l) * 8 + j] = lo ? esr_host_to16(w - esr_host_from16(hi, storage), storage) : hi;
                     }
     unsigned short* img1 = img + (size_t)2 * nt0 * np * 512;
     for (int lo = 0; lo < lo1; ++lo)
@@ -900,8 +872,8 @@ int esr_pack_apply_post(const float* w0, const float* b0, const float* w1, const
                         // k slot (kq, j): the high (j < 4) / low (j >= 4) part of the lane's value j & 3 of post 0's tile T
                         const int oc = chan(t, l & 15), ic = chan(T, 4 * (l >> 4) + (j & 3));
                         const float w = (oc < cout1 && ic < cout0) ? w1[(size_t)oc * cout0 + ic] : 0.f;
-                        const unsigned short hi = host_to16(w, storage);
-                        const unsigned short v = lo == 0 ? hi : (j < 4 ? host_to16(w - host_from16(hi, storage), storage) : (unsigned short)0);
+                        const unsigned short hi = esr_host_to16(w, storage);
+                        const unsigned short v = lo == 0 ? hi : (j < 4 ? esr_host_to16(w - esr_host_from16(hi, storage), storage) : (unsigned short)0);
                         img1[((size_t)((lo * nt1 + t) * nt0 + T) * 64 + l) * 8 + j] = (storage == ESR_STORE_F16 && j >= 4) ? (unsigned short)0 : v;
                     }
     float* bias = reinterpret_cast<float*>(img1 + (size_t)lo1 * nt1 * nt0 * 512);

@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
-#include <atomic>
 
 #include "esr_internal.h"
 
@@ -454,19 +453,9 @@ __global__ __launch_bounds__(256) void esa_chain_kernel(const ChainK p)
     }
 }
 
+// conv2 tile + input patch; > 64 KB for fp32 storage (the launcher opts in: esr_lds_optin)
 template <int ST>
-size_t s2_lds()
-{
-    // conv2 tile + input patch; > 64 KB for fp32 storage: the attribute is set once per device (as esr_s16.hip does)
-    const size_t bytes = CT * CT * FP * sizeof(float) + S2In<ST>::BYTES;
-    static std::atomic<unsigned> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !attr_set[dev].load(std::memory_order_relaxed)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&esa_s2pool_kernel<ST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess)
-            attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
-    return bytes;
-}
+constexpr size_t s2_lds() { return CT * CT * FP * sizeof(float) + S2In<ST>::BYTES; }
 
 }  // namespace
 
@@ -495,6 +484,10 @@ extern "C" int esr_esa_lowres_f32(const esr_esa_lowres_desc* d, void* hip_stream
     const dim3 grid((unsigned)(d->n * tx * ty));
     const float* w0 = static_cast<const float*>(d->w_s2);
     float* pooled = static_cast<float*>(d->pooled);
+    if (d->storage == ESR_STORE_F32) {
+        static esr_lds_optin_flags optin;
+        if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&esa_s2pool_kernel<ESR_STORE_F32>), (int)s2_lds<ESR_STORE_F32>(), "esa_s2pool_kernel")) return rc;
+    }
     switch (d->storage) {
         case ESR_STORE_F32: esr_note_kernel("esa_s2pool_kernel<0>"); hipLaunchKernelGGL(esa_s2pool_kernel<ESR_STORE_F32>, grid, dim3(256), s2_lds<ESR_STORE_F32>(), st, d->x.ptr, w0, pooled, d->h, d->w, H2, W2, H3, W3, tx, ty); break;
         case ESR_STORE_BF16: esr_note_kernel("esa_s2pool16_kernel<1>"); hipLaunchKernelGGL(esa_s2pool16_kernel<ESR_STORE_BF16>, grid, dim3(256), 0, st, d->x.ptr, w0, pooled, d->h, d->w, H3, W3, tx, ty); break;

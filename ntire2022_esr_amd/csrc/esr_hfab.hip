@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
-#include <atomic>
 
 #include "esr_s16_dev.h"
 
@@ -225,18 +224,9 @@ __global__ __launch_bounds__(64 * HF_NW, 1) void hfab_kernel(const HfabK p)
 template <bool BF16, int NCH>
 int launch_hfab(const HfabK& k, hipStream_t st)
 {
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hfab_kernel<BF16, NCH>), hipFuncAttributeMaxDynamicSharedMemorySize, HF_LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(hfab_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
-    const int grid = k.ntiles < 256 ? k.ntiles : 256;      // one block per CU (LDS), persistent over the tiles
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&hfab_kernel<BF16, NCH>), HF_LDS, "hfab_kernel")) return rc;
+    const int grid = esr_persistent_grid(k.ntiles, ESR_BLOCKS_1_PER_CU);      // one block per CU (LDS), persistent over the tiles
     esr_note_kernel("hfab_kernel<%s, %d>", esr_tf(BF16), NCH);
     hipLaunchKernelGGL((hfab_kernel<BF16, NCH>), dim3(grid), dim3(64 * HF_NW), HF_LDS, st, k);
     return esr_check_launch("hfab_kernel launch");

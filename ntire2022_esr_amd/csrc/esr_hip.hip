@@ -40,7 +40,6 @@ namespace {
 constexpr int TILE = 16;      // output tile edge (pixels)
 constexpr int CHUNK = 8;      // input channels per K stage
 constexpr int THREADS = 256;
-constexpr int MAX_RESIDENT_BLOCKS = 512;   // 256 CUs x 2 blocks (LDS: 75 KB per block)
 
 struct ConvK {
     const float* x;
@@ -792,9 +791,6 @@ thread_local char g_err[256] = "";
 thread_local char g_kname[256] = "";       // device symbol(s) of the op being run (esr_note_kernel)
 thread_local bool g_ktrace = false;
 
-inline void set_err(const char* what, hipError_t e) { esr_set_err(what, e); }
-inline int round_up(int v, int m) { return esr_round_up(v, m); }
-
 // Which conv_f32_kernel variant a launch takes: 8-wave blocks on 16x32-pixel tiles (one per CU) for large 3x3 NHWC
 // launches, else 4-wave blocks on 16x16 tiles (two per CU).  The eight waves share one weight stage, so a SIMD issues a
 // third fewer staging instructions per MFMA (they, not the MFMA pipe, bound this kernel: DESIGN.md).
@@ -818,7 +814,7 @@ int launch_conv(const ConvK& k, hipStream_t st)
         const int ntall = k.N * k.tiles_x * tall_y;
         ConvK kk = k;
         kk.tiles_y = tall_y;
-        const int grid = ntall < 256 ? ntall : 256;
+        const int grid = esr_persistent_grid(ntall, ESR_BLOCKS_1_PER_CU);
         esr_note_kernel("conv_f32_kernel<%d, %d, %s, 8, 0, %d, %s>", NT, KS, esr_tf(IN_NCHW), (NT == 4 && kk.wp3) ? 2 : 0, esr_tf(NT == 4 && !kk.wp3 && kk.y1_blk));
         if (NT == 4 && kk.wp3)
             hipLaunchKernelGGL((conv_f32_kernel<NT, KS, IN_NCHW, CAN_TALL ? 8 : 4, 0, (CAN_TALL && NT == 4) ? 2 : 0>), dim3(grid), dim3(512), 0, st, kk);
@@ -827,24 +823,14 @@ int launch_conv(const ConvK& k, hipStream_t st)
         else
             hipLaunchKernelGGL((conv_f32_kernel<NT, KS, IN_NCHW, CAN_TALL ? 8 : 4>), dim3(grid), dim3(512), 0, st, kk);
         esr_graph_note_io(st, kk.x, offsetof(ConvK, x), kk.y0, offsetof(ConvK, y0));
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_err("conv_f32_kernel (tall) launch", e);
-            return ESR_ERR_LAUNCH;
-        }
-        return ESR_OK;
+        return esr_check_launch("conv_f32_kernel (tall) launch");
     }
-    const int grid = ntiles < MAX_RESIDENT_BLOCKS ? ntiles : MAX_RESIDENT_BLOCKS;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_2_PER_CU);
     esr_note_kernel("conv_f32_kernel<%d, %d, %s, 4, 0, 0, %s>", NT, KS, esr_tf(IN_NCHW), esr_tf(CAN_TALL && NT == 4 && k.y1_blk));
     if (CAN_TALL && NT == 4 && k.y1_blk) hipLaunchKernelGGL((conv_f32_kernel<NT, KS, IN_NCHW, 4, 0, 0, CAN_TALL && NT == 4>), dim3(grid), dim3(THREADS), 0, st, k);
     else hipLaunchKernelGGL((conv_f32_kernel<NT, KS, IN_NCHW, 4>), dim3(grid), dim3(THREADS), 0, st, k);
     esr_graph_note_io(st, k.x, offsetof(ConvK, x), k.y0, offsetof(ConvK, y0));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_err("conv_f32_kernel launch", e);
-        return ESR_ERR_LAUNCH;
-    }
-    return ESR_OK;
+    return esr_check_launch("conv_f32_kernel launch");
 }
 
 // IMDBlock's own shape (48 -> 16 3x3, 3 x 16 concat channels, 64 outputs, no or a pre-activation residual) takes imdb_tail_kernel
@@ -859,31 +845,21 @@ inline bool imdb_tail_shape(const ConvK& k)
 int launch_conv_tail(const ConvK& k, hipStream_t st)
 {
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < MAX_RESIDENT_BLOCKS ? ntiles : MAX_RESIDENT_BLOCKS;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_2_PER_CU);
     if (imdb_tail_shape(k)) {
         ConvK kk = k;
         kk.res_mode = ESR_RES_NONE;                 // folded into the 1x1's accumulators: the epilogue adds nothing
         kk.tiles_y = (k.H + 4 * IT_NW - 1) / (4 * IT_NW);      // 16 x 32 pixel tiles, one 8-wave block per CU
         const int nt32 = k.N * kk.tiles_x * kk.tiles_y;
-        const int g32 = nt32 < 256 ? nt32 : 256;
+        const int g32 = esr_persistent_grid(nt32, ESR_BLOCKS_1_PER_CU);
         esr_note_kernel("imdb_tail_kernel<%s>", esr_tf(k.res_mode == ESR_RES_PRE_ACT));
         if (k.res_mode == ESR_RES_PRE_ACT) hipLaunchKernelGGL((imdb_tail_kernel<true>), dim3(g32), dim3(64 * IT_NW), 0, st, kk);
         else hipLaunchKernelGGL((imdb_tail_kernel<false>), dim3(g32), dim3(64 * IT_NW), 0, st, kk);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_err("imdb_tail_kernel launch", e);
-            return ESR_ERR_LAUNCH;
-        }
-        return ESR_OK;
+        return esr_check_launch("imdb_tail_kernel launch");
     }
     esr_note_kernel("conv_f32_kernel<1, 3, false, 4, 4, 0, false>");
     hipLaunchKernelGGL((conv_f32_kernel<1, 3, false, 4, 4>), dim3(grid), dim3(THREADS), 0, st, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_err("conv_f32_kernel (1x1 tail) launch", e);
-        return ESR_ERR_LAUNCH;
-    }
-    return ESR_OK;
+    return esr_check_launch("conv_f32_kernel (1x1 tail) launch");
 }
 
 template <int KS, bool IN_NCHW>
@@ -926,6 +902,22 @@ int esr_check_launch(const char* what)
     return ESR_OK;
 }
 
+int esr_lds_optin(esr_lds_optin_flags& flags, const void* kernel, int bytes, const char* name)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
+    if (flags.set[dev].load(std::memory_order_relaxed)) return ESR_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        char what[128];
+        snprintf(what, sizeof(what), "hipFuncSetAttribute(%s, MaxDynamicSharedMemorySize)", name);
+        esr_set_err(what, e);
+        return ESR_ERR_LAUNCH;
+    }
+    flags.set[dev].store(1u, std::memory_order_relaxed);
+    return ESR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
@@ -953,8 +945,8 @@ const char* esr_build_info(void) { return "gfx950 f32:v_mfma_f32_16x16x4_f32 (Wi
 size_t esr_packed_conv_bytes(int cin_phys, int cout, int ksize)
 {
     if (cin_phys <= 0 || cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
-    const size_t nt = (size_t)round_up(cout, 16) / 16;
-    const size_t nchunks = (size_t)round_up(cin_phys, CHUNK) / CHUNK;
+    const size_t nt = (size_t)esr_round_up(cout, 16) / 16;
+    const size_t nchunks = (size_t)esr_round_up(cin_phys, CHUNK) / CHUNK;
     return (nchunks * ksize * ksize * nt * 128 + nt * 16) * sizeof(float);
 }
 
@@ -974,7 +966,7 @@ int esr_pack_conv_f32(const float* w, const float* bias, int cin, int cout, int 
     if (!cin_map && cin_phys < cin) return ESR_ERR_BAD_ARG;
     const size_t need = esr_packed_conv_bytes(cin_phys, cout, ksize);
     if (need == 0 || out_bytes < need) return ESR_ERR_BAD_ARG;
-    const int nt = round_up(cout, 16) / 16, taps = ksize * ksize;
+    const int nt = esr_round_up(cout, 16) / 16, taps = ksize * ksize;
     float* o = static_cast<float*>(out);
     memset(o, 0, need);
     for (int s = 0; s < cin_phys; ++s) {
@@ -987,7 +979,7 @@ int esr_pack_conv_f32(const float* w, const float* bias, int cin, int cout, int 
                 o[pack_index(nt, taps, s, tap, oc, &j)] = w[((size_t)oc * cin + c) * taps + tap];
             }
     }
-    float* bo = o + (size_t)(round_up(cin_phys, CHUNK) / CHUNK) * taps * nt * 128;
+    float* bo = o + (size_t)(esr_round_up(cin_phys, CHUNK) / CHUNK) * taps * nt * 128;
     if (bias)
         for (int oc = 0; oc < cout; ++oc) bo[oc] = bias[oc];
     return ESR_OK;
@@ -998,7 +990,7 @@ int esr_unpack_conv_f32(const void* packed, size_t bytes, int cin, int cout, int
 {
     if (!packed || !w || cin <= 0 || cout <= 0 || (ksize != 1 && ksize != 3)) return ESR_ERR_BAD_ARG;
     if (bytes < esr_packed_conv_bytes(cin_phys, cout, ksize)) return ESR_ERR_BAD_ARG;
-    const int nt = round_up(cout, 16) / 16, taps = ksize * ksize;
+    const int nt = esr_round_up(cout, 16) / 16, taps = ksize * ksize;
     const float* o = static_cast<const float*>(packed);
     memset(w, 0, sizeof(float) * (size_t)cout * cin * taps);
     for (int s = 0; s < cin_phys; ++s) {
@@ -1011,7 +1003,7 @@ int esr_unpack_conv_f32(const void* packed, size_t bytes, int cin, int cout, int
             }
     }
     if (bias) {
-        const float* bo = o + (size_t)(round_up(cin_phys, CHUNK) / CHUNK) * taps * nt * 128;
+        const float* bo = o + (size_t)(esr_round_up(cin_phys, CHUNK) / CHUNK) * taps * nt * 128;
         for (int oc = 0; oc < cout; ++oc) bias[oc] = bo[oc];
     }
     return ESR_OK;
@@ -1022,8 +1014,8 @@ int esr_conv_block_waves(const esr_conv_desc* d)
     if (!d || d->cin <= 0 || d->cout <= 0) return 0;
     if (d->storage != ESR_STORE_F32 && d->in_layout == ESR_NHWC) return esr_s16_block_waves(d);      // conv_s16_kernel: 8-wave blocks, or two of 4
     const bool in_nchw = d->in_layout == ESR_NCHW_IN;
-    const int cin_phys = in_nchw ? CHUNK : round_up(d->cin, CHUNK);
-    return conv_block_waves(d->ksize, in_nchw, round_up(d->cout, 16) / 16, cin_phys / CHUNK, d->n, d->h, d->w);
+    const int cin_phys = in_nchw ? CHUNK : esr_round_up(d->cin, CHUNK);
+    return conv_block_waves(d->ksize, in_nchw, esr_round_up(d->cout, 16) / 16, cin_phys / CHUNK, d->n, d->h, d->w);
 }
 
 int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
@@ -1050,10 +1042,10 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
         // the network head with 16-bit activations downstream: fp32 NCHW input (exact), fp32 MFMA, 16-bit NHWC store
         if (d->out_layout != ESR_NHWC || d->res_mode != ESR_RES_NONE || d->tail_wpacked || d->post_wpacked) return ESR_ERR_UNSUPPORTED;
         if (d->split > 0 && d->split < d->cout) return ESR_ERR_UNSUPPORTED;
-        if ((d->out0.pitch & 7) || (d->out0.coff & 7) || d->out0.coff + round_up(d->cout, 8) > d->out0.pitch) return ESR_ERR_BAD_ARG;
+        if ((d->out0.pitch & 7) || (d->out0.coff & 7) || d->out0.coff + esr_round_up(d->cout, 8) > d->out0.pitch) return ESR_ERR_BAD_ARG;
     }
     if (!in_nchw && ((d->in.pitch & 3) || (d->in.coff & 3))) return ESR_ERR_BAD_ARG;
-    const int cin_phys = in_nchw ? CHUNK : round_up(d->cin, CHUNK);
+    const int cin_phys = in_nchw ? CHUNK : esr_round_up(d->cin, CHUNK);
     if (!in_nchw && d->in.coff + cin_phys > d->in.pitch) return ESR_ERR_BAD_ARG;   // chunk reads stay inside the pixel
     // fused 1x1 tail: the epilogue fields describe the 1x1's output
     const bool tail = d->tail_wpacked != nullptr;
@@ -1073,15 +1065,15 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
                                d->res.pitch == d->in.pitch && d->res.coff == d->in.coff;
         if (d->res_mode != ESR_RES_NONE && !res_is_in) return ESR_ERR_UNSUPPORTED;
         if (d->split > 0 && d->split < d->cout) return ESR_ERR_UNSUPPORTED;
-        const int pc4 = round_up(d->post_cout, 4);
+        const int pc4 = esr_round_up(d->post_cout, 4);
         if (!d->post_out.ptr || (d->post_out.pitch & 3) || (d->post_out.coff & 3) || d->post_out.coff + pc4 > d->post_out.pitch)
             return ESR_ERR_BAD_ARG;
         if ((double)d->n * d->h * d->w * d->post_out.pitch >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
         // the 1x1 reads the conv's output as 8-channel chunks when it has to run as a launch of its own (small shapes)
-        if (d->out0.coff + round_up(d->cout, CHUNK) > d->out0.pitch) return ESR_ERR_BAD_ARG;
+        if (d->out0.coff + esr_round_up(d->cout, CHUNK) > d->out0.pitch) return ESR_ERR_BAD_ARG;
     }
     const int ecout = tail ? d->tail_cout : d->cout;          // channels the epilogue stores
-    const int cout4 = round_up(ecout, 4);
+    const int cout4 = esr_round_up(ecout, 4);
     int split = d->split <= 0 ? cout4 : d->split;
     if (split >= ecout) split = cout4;
     if (split & 3) return ESR_ERR_BAD_ARG;
@@ -1118,7 +1110,7 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
     if ((d->blocked8 & (ESR_BLOCKED_OUT0 | ESR_BLOCKED_RES)) && (!tail || store16)) return ESR_ERR_UNSUPPORTED;
     if (d->wino_wpacked && !store16 && esr_wino_supported(d)) return esr_conv2d_wino(d, hip_stream);
 
-    const int nt = round_up(d->cout, 16) / 16;
+    const int nt = esr_round_up(d->cout, 16) / 16;
     const int taps = d->ksize * d->ksize;
     ConvK k;
     k.out16 = store16 ? d->storage : 0;
@@ -1178,13 +1170,13 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
             return esr_conv2d_f32(&b, hip_stream);
         }
         k.wp3 = static_cast<const float*>(d->post_wpacked);
-        const int pnt = round_up(d->post_cout, 16) / 16;
+        const int pnt = esr_round_up(d->post_cout, 16) / 16;
         if (pnt != 2) return ESR_ERR_UNSUPPORTED;              // post_cout in (16, 32]
-        k.bias3 = k.wp3 + (size_t)(round_up(d->cout, CHUNK) / CHUNK) * pnt * 128;
+        k.bias3 = k.wp3 + (size_t)(esr_round_up(d->cout, CHUNK) / CHUNK) * pnt * 128;
         k.y2 = static_cast<float*>(d->post_out.ptr);
-        k.y2_pitch = d->post_out.pitch; k.y2_coff = d->post_out.coff; k.y2_cout4 = round_up(d->post_cout, 4);
+        k.y2_pitch = d->post_out.pitch; k.y2_coff = d->post_out.coff; k.y2_cout4 = esr_round_up(d->post_cout, 4);
         k.post_act = d->post_act;
-        k.post_nch8 = round_up(d->cout, CHUNK) / CHUNK;
+        k.post_nch8 = esr_round_up(d->cout, CHUNK) / CHUNK;
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     if (tail) {
@@ -1240,7 +1232,7 @@ int esr_prof_create(int n_ops, int max_passes, esr_profiler** out)
     for (size_t i = 0; i < n; ++i) {
         const hipError_t e = hipEventCreate(&p->ev[i]);
         if (e != hipSuccess) {
-            set_err("hipEventCreate", e);
+            esr_set_err("hipEventCreate", e);
             for (size_t j = 0; j < i; ++j) (void)hipEventDestroy(p->ev[j]);
             delete[] p->ev;
             delete[] p->sym;
@@ -1299,7 +1291,7 @@ int esr_prof_collect(esr_profiler* p, double* ms_sum, int n_ops, int* passes)
             float ms = 0.f;
             const hipError_t e = hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
             if (e != hipSuccess) {
-                set_err("hipEventElapsedTime", e);
+                esr_set_err("hipEventElapsedTime", e);
                 return ESR_ERR_LAUNCH;
             }
             ms_sum[i] += ms;

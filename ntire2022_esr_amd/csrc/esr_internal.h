@@ -1,10 +1,57 @@
 // shared by the translation units of libesr_hip.so (not part of the public ABI)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <atomic>
 #include "esr_hip.h"
 
 void esr_set_err(const char* what, hipError_t e);
 int esr_check_launch(const char* what);
+
+// Opt-in of one kernel instantiation to more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute
+// belongs to the (device, instantiation) pair: one process may drive several GPUs (engine contexts are keyed by device), so a launcher
+// keeps one `static esr_lds_optin_flags` per instantiation and calls esr_lds_optin before it launches.  Relaxed atomics: a racing
+// thread at worst sets the same value twice.  A failure is recorded as "hipFuncSetAttribute(<name>, MaxDynamicSharedMemorySize)"
+// and returns ESR_ERR_LAUNCH.
+constexpr int MAX_DEVICES = 64;
+struct esr_lds_optin_flags { std::atomic<unsigned> set[MAX_DEVICES]; };
+int esr_lds_optin(esr_lds_optin_flags& flags, const void* kernel, int bytes, const char* name);
+
+// Persistent launches: min(work items, resident blocks).  The LDS footprint of a kernel decides how many of its blocks a CU holds.
+constexpr int ESR_BLOCKS_1_PER_CU = 256, ESR_BLOCKS_2_PER_CU = 512;      // 256 CUs
+static inline int esr_persistent_grid(int ntiles, int cap) { return ntiles < cap ? ntiles : cap; }
+
+// fp32 -> bf16 / fp16 and back on the host, as the kernels' conversions: round to nearest even, a NaN is quietened.  THE rounding of
+// every weight packer (a fused kernel is bit-identical to the launches it replaces only if their packers round alike).  `fmt` is an
+// ESR_COMPUTE_* or an ESR_STORE_* value: the two enums agree on the 16-bit formats.
+static_assert((int)ESR_COMPUTE_BF16 == (int)ESR_STORE_BF16 && (int)ESR_COMPUTE_F16 == (int)ESR_STORE_F16, "esr_host_to16: one fmt for both enums");
+static inline uint16_t esr_host_to16(float f, int fmt)
+{
+    uint16_t r;
+    if (fmt == ESR_COMPUTE_BF16) {
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);       // NaN
+        u += 0x7fffu + ((u >> 16) & 1u);
+        return (uint16_t)(u >> 16);
+    }
+    const _Float16 h = (_Float16)f;        // host compiler: IEEE RNE
+    memcpy(&r, &h, 2);
+    return r;
+}
+static inline float esr_host_from16(uint16_t h, int fmt)
+{
+    if (fmt == ESR_COMPUTE_BF16) {
+        const uint32_t u = (uint32_t)h << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    }
+    _Float16 v;
+    memcpy(&v, &h, 2);
+    return (float)v;
+}
 // Records the device symbol of the launch that follows, as rocprofv3 prints it -- only while esr_run_ops_profiled runs (a bench /
 // profile leg names its kernels by the symbol that really ran: esr_prof_kernel_symbol).  printf-style.
 void esr_note_kernel(const char* fmt, ...);

@@ -14,7 +14,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include <utility>
 #include <type_traits>
 
@@ -1239,19 +1238,10 @@ template <bool BF16, bool LRS = false>
 int launch_conv48rp(const S16K& k, hipStream_t st)
 {
     constexpr int LDS = LRS ? 2 * (31 * 1024 + 2 * 24576) : 2 * 31 * 1024 + 2 * 24576 + 2 * 9 * 1024 + 2 * 3 * 1024;
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv48rp_kernel<BF16, LRS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(conv48rp_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&conv48rp_kernel<BF16, LRS>), LDS, "conv48rp_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_1_PER_CU);
     esr_note_kernel("conv48rp_kernel<%s, %s>", esr_tf(BF16), esr_tf(LRS));
     hipLaunchKernelGGL((conv48rp_kernel<BF16, LRS>), dim3(grid), dim3(256), LDS, st, k);
     return esr_check_launch("conv48rp_kernel launch");
@@ -1263,19 +1253,10 @@ int launch_conv48r_fx(const S16K& k, hipStream_t st)
     // [two input stages][RW = 4: 45 KB where the weight blob is staged][border table]
     constexpr int STAGES = RW == 8 ? 2 * 58 * 1024 : 2 * 31 * 1024 + 15 * NT * 1024;
     const int LDS = STAGES + ((EXT && k.border) ? NT * 1024 : 0);
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv48r_kernel<BF16, NT, EXT, RW, FX>), hipFuncAttributeMaxDynamicSharedMemorySize, STAGES + NT * 1024);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(conv48r_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&conv48r_kernel<BF16, NT, EXT, RW, FX>), STAGES + NT * 1024, "conv48r_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_1_PER_CU);
     esr_note_kernel("conv48r_kernel<%s, %d, %s, %d, %d>", esr_tf(BF16), NT, esr_tf(EXT), RW, FX);
     hipLaunchKernelGGL((conv48r_kernel<BF16, NT, EXT, RW, FX>), dim3(grid), dim3(256), LDS, st, k);
     return esr_check_launch("conv48r_kernel launch");
@@ -1298,19 +1279,10 @@ int launch_conv48rq_fx(const S16K& k, hipStream_t st)
 {
     // [two input stages][45 KB where the weight blob is staged][border table][post images: hi (+ lo)]
     constexpr int LDS = 2 * 31 * 1024 + 45 * 1024 + 3 * 1024 + (BF16 ? 2 : 1) * 6 * 1024;
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv48rq_kernel<BF16, FX>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(conv48rq_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&conv48rq_kernel<BF16, FX>), LDS, "conv48rq_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_1_PER_CU);
     esr_note_kernel("conv48rq_kernel<%s, %d>", esr_tf(BF16), FX);
     hipLaunchKernelGGL((conv48rq_kernel<BF16, FX>), dim3(grid), dim3(256), LDS, st, k);
     return esr_check_launch("conv48rq_kernel launch");
@@ -1330,19 +1302,10 @@ int launch_conv64r(const S16K& k, hipStream_t st)
     // [stage 0][stage 1 | the weight blob as staged, chunk 3 (NT = 4) resident behind stage 1]
     constexpr int STAGE = 51 * 1024, BLOB = 4 * 5 * NT * 1024;
     constexpr int LDS = STAGE + (BLOB > STAGE ? BLOB : STAGE);
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv64r_kernel<BF16, NT, EXT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(conv64r_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&conv64r_kernel<BF16, NT, EXT>), LDS, "conv64r_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = esr_persistent_grid(ntiles, ESR_BLOCKS_1_PER_CU);
     esr_note_kernel("conv64r_kernel<%s, %d, %s>", esr_tf(BF16), NT, esr_tf(EXT));
     hipLaunchKernelGGL((conv64r_kernel<BF16, NT, EXT>), dim3(grid), dim3(256), LDS, st, k);
     return esr_check_launch("conv64r_kernel launch");

@@ -36,7 +36,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include <utility>
 #include <type_traits>
 
@@ -796,23 +795,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_s16_kernel(cons
 template <int NT, int KS, int NW, bool BF16, bool GRES, int PNT1 = 0, int PNT2 = 0, bool HILO = false>
 int launch_s16(const S16K& k, size_t lds, hipStream_t st)
 {
-    // the attribute belongs to the (device, instantiation) pair: one process may drive several GPUs (engine contexts are keyed by
-    // device).  Relaxed atomics: a racing thread at worst sets the same value twice.
-    static std::atomic<unsigned> attr_set[MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return ESR_ERR_LAUNCH;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s16_kernel<NT, KS, NW, BF16, GRES, PNT1, PNT2, HILO>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
-        if (e != hipSuccess) {
-            esr_set_err("hipFuncSetAttribute(conv_s16_kernel, MaxDynamicSharedMemorySize)", e);
-            return ESR_ERR_LAUNCH;
-        }
-        attr_set[dev].store(1u, std::memory_order_relaxed);
-    }
+    static esr_lds_optin_flags optin;
+    if (const int rc = esr_lds_optin(optin, reinterpret_cast<const void*>(&conv_s16_kernel<NT, KS, NW, BF16, GRES, PNT1, PNT2, HILO>), LDS_LIMIT, "conv_s16_kernel")) return rc;
     const int ntiles = k.N * k.tiles_x * k.tiles_y;
-    const int cap = NW == 4 ? 512 : 256;                   // one block per CU (LDS; NW = 4: two), persistent over the tiles
-    const int grid = ntiles < cap ? ntiles : cap;
+    // one block per CU (LDS; NW = 4: two), persistent over the tiles
+    const int grid = esr_persistent_grid(ntiles, NW == 4 ? ESR_BLOCKS_2_PER_CU : ESR_BLOCKS_1_PER_CU);
     // (rocprofv3 prints every template argument, defaulted ones included)
     esr_note_kernel("conv_s16_kernel<%d, %d, %d, %s, %s, %d, %d, %s>", NT, KS, NW, esr_tf(BF16), esr_tf(GRES), PNT1, PNT2, esr_tf(HILO));
     hipLaunchKernelGGL((conv_s16_kernel<NT, KS, NW, BF16, GRES, PNT1, PNT2, HILO>), dim3(grid), dim3(64 * NW), lds, st, k);
@@ -1090,37 +1077,6 @@ int s16_post_plan(const esr_conv_desc* d, int nt, int nchunks, int* pnt1, int* p
     return ESR_ERR_UNSUPPORTED;
 }
 
-inline uint16_t f32_to_bf16(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);       // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float bf16_to_f32(uint16_t h)
-{
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-inline uint16_t f32_to_f16(float f)
-{
-    const _Float16 h = (_Float16)f;        // host compiler: IEEE RNE
-    uint16_t r;
-    memcpy(&r, &h, 2);
-    return r;
-}
-inline float f16_to_f32(uint16_t h)
-{
-    _Float16 v;
-    memcpy(&v, &h, 2);
-    return (float)v;
-}
-inline uint16_t to16(double v, int compute) { return compute == ESR_COMPUTE_BF16 ? f32_to_bf16((float)v) : f32_to_f16((float)v); }
-inline double from16(uint16_t h, int compute) { return compute == ESR_COMPUTE_BF16 ? bf16_to_f32(h) : f16_to_f32(h); }
-
 // element index of (physical slot s, tap slot ts in {0..2*pairs-1}, output channel oc) in the weight image
 inline size_t s16_index(int nt, int pairs, int s, int ts, int oc)
 {
@@ -1165,8 +1121,8 @@ int esr_pack_conv_s16(const float* w, const float* bias, int cin, int cout, int 
             const float* wf = w + ((size_t)oc * cin + c) * taps;
             if (ksize == 1) {
                 // w = hi + lo: the second tap slot of the pair carries the rounding residual of the first
-                const uint16_t hi = to16(wf[0], compute);
-                const uint16_t lo = to16((double)wf[0] - from16(hi, compute), compute);
+                const uint16_t hi = esr_host_to16(wf[0], compute);
+                const uint16_t lo = esr_host_to16((float)((double)wf[0] - esr_host_from16(hi, compute)), compute);
                 o[s16_index(nt, pairs, s, 0, oc)] = hi;
                 o[s16_index(nt, pairs, s, 1, oc)] = lo;
             } else {
@@ -1175,8 +1131,8 @@ int esr_pack_conv_s16(const float* w, const float* bias, int cin, int cout, int 
                 double e = 0.0;
                 for (int tap = 0; tap < taps; ++tap) {
                     const double t = (double)wf[tap] + e;
-                    const uint16_t q = to16(t, compute);
-                    e = t - from16(q, compute);
+                    const uint16_t q = esr_host_to16((float)t, compute);
+                    e = t - esr_host_from16(q, compute);
                     o[s16_index(nt, pairs, s, tap, oc)] = q;
                     // the same value in v_mfma_f32_32x32x16's fragment order (esr_c64m.hip): fragment (chunk, tap, half), lane 32 h + i, slot j
                     if (om) om[(((((size_t)(s / 16) * 9 + tap) * (nt >= 3 ? 2 : 1) + oc / 32) * 64 + ((s % 16) / 8) * 32 + oc % 32) * 8) + s % 8] = q;
@@ -1215,8 +1171,8 @@ int esr_pack_post_s16(const float* w, const float* bias, int cin, int cout, int 
     for (int o = 0; o < cout; ++o)
         for (int c = 0; c < cin; ++c) {
             const float wv = w[(size_t)o * cin + c];
-            const uint16_t h = to16(wv, compute);
-            const uint16_t l = to16((double)wv - from16(h, compute), compute);
+            const uint16_t h = esr_host_to16(wv, compute);
+            const uint16_t l = esr_host_to16((float)((double)wv - esr_host_from16(h, compute)), compute);
             const size_t base = ((((size_t)(c / 16) * ot + o / 16) * 64 + ((c % 16) / 4) * 16 + o % 16) * 8) + (c % 4);
             hi[base] = h;
             hi[base + 4] = h;
@@ -1260,8 +1216,8 @@ int esr_unpack_conv_s16(const void* packed, size_t bytes, int cin, int cout, int
         if (c < 0) continue;
         for (int oc = 0; oc < cout; ++oc)
             for (int tap = 0; tap < taps; ++tap) {
-                double v = from16(o[s16_index(nt, pairs, s, tap, oc)], compute);
-                if (ksize == 1) v += from16(o[s16_index(nt, pairs, s, 1, oc)], compute);
+                double v = esr_host_from16(o[s16_index(nt, pairs, s, tap, oc)], compute);
+                if (ksize == 1) v += esr_host_from16(o[s16_index(nt, pairs, s, 1, oc)], compute);
                 w[((size_t)oc * cin + c) * taps + tap] = (float)v;       // the EFFECTIVE weight the kernel multiplies by
             }
     }

@@ -96,7 +96,6 @@ constexpr int TILE = 16;            // output tile width (pixels) = one MFMA's p
 constexpr int RING_MIN = 3, RING_MAX = 8;   // input stages in LDS (as many as fit next to the resident weights)
 constexpr unsigned OOB = 0x80000000u;
 constexpr int LDS_LIMIT = 160 * 1024;
-constexpr int MAX_DEVICES = 64;     // per-device launch attributes (launch_s16)
 constexpr int S16_NW = 8;           // waves per tile
 
 template <bool BF16>

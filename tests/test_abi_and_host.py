@@ -94,6 +94,17 @@ def test_descriptor_validation_without_gpu():
     assert lib.esr_conv2d_f32(ctypes.byref(d), None) == -1          # chunked reads would leave the pixel
     assert lib.esr_run_ops(None, 1, None) == -1
     assert lib.esr_packed_conv_bytes(64, 64, 2) == 0
+    if torch.cuda.device_count() == 0:
+        # a VALID descriptor on a host without a GPU: the launch itself fails, and esr_check_launch reports it under the launcher's
+        # name (only here: with a GPU the launch would run, on these host pointers)
+        d.inp.coff = 0
+        lib.esr_last_hip_error.restype = ctypes.c_char_p
+        assert lib.esr_conv2d_f32(ctypes.byref(d), None) == -3          # ESR_ERR_LAUNCH
+        assert lib.esr_last_hip_error().startswith(b"conv_f32_kernel launch: "), lib.esr_last_hip_error()
+        # 16-bit storage: the LDS opt-in comes first and has no device to ask
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = L.STORE["bf16"]
+        assert lib.esr_conv2d_f32(ctypes.byref(d), None) == -3
 
 
 def test_hilo_descriptor_validation_without_gpu():

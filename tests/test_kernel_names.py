@@ -62,3 +62,46 @@ def test_noted_kernel_names_carry_every_template_argument():
     for must in ("conv64m_kernel", "rfdb_tail_kernel", "rlfb_chain_kernel", "wino8_f32_kernel", "wino_f32_kernel", "imdb_tail_kernel",
                  "conv_s16_kernel", "conv_f32_kernel", "esa_apply_mfma_kernel", "pack_input_kernel"):
         assert must in seen, must
+
+
+def _body(text, signature):
+    """the brace-balanced body that follows `signature` in `text`, as a (start, end) span"""
+    at = text.index(signature)
+    start = text.index("{", at)
+    depth = 0
+    for i in range(start, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        if depth == 0:
+            return start, i + 1
+    raise AssertionError(signature)
+
+
+def test_launch_boilerplate_has_one_definition():
+    """The host code around a launch was copied from launcher to launcher and the copies drifted (a per-process flag where the LDS opt-in
+    is per device, a swallowed error, a NaN rounded differently by one packer).  Each piece now has ONE definition -- esr_lds_optin and
+    esr_check_launch (esr_hip.hip), esr_lds_optin_flags and esr_host_to16 (esr_internal.h) -- and this test keeps a new launcher from
+    bringing a copy back.  Text with comments stripped; string literals are blanked as well where a CALL is counted (the opt-in's error
+    message names the call it reports)."""
+    src = dict(_sources(strip=True))
+    code = {f: re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', t) for f, t in src.items()}
+
+    def sites(texts, needle):
+        return [(f, m.start()) for f, t in texts.items() for m in re.finditer(needle, t)]
+
+    # one opt-in to more than 64 KB of dynamic LDS: the call inside esr_lds_optin
+    lo, hi = _body(code["esr_hip.hip"], "int esr_lds_optin(esr_lds_optin_flags& flags")
+    calls = sites(code, r"hipFuncSetAttribute\s*\(")
+    assert len(calls) == 1 and calls[0][0] == "esr_hip.hip" and lo < calls[0][1] < hi, calls
+    lo, hi = _body(src["esr_hip.hip"], "int esr_lds_optin(esr_lds_optin_flags& flags")
+    assert all(f == "esr_hip.hip" and lo < at < hi for f, at in sites(src, r"hipFuncSetAttribute\s*\(")), "named outside esr_lds_optin"
+    # one launch check
+    lo, hi = _body(src["esr_hip.hip"], "int esr_check_launch(const char* what)")
+    got = sites(src, r"hipGetLastError")
+    assert got and all(f == "esr_hip.hip" and lo < at < hi for f, at in got), got
+    # one host rounding to bf16 (the constant of its round-to-nearest-even add)
+    got = sites(src, r"0x7fffu\b")
+    assert len(got) == 1 and got[0][0] == "esr_internal.h", got
+    # one per-device flag array: the helper's type
+    lo, hi = _body(src["esr_internal.h"], "struct esr_lds_optin_flags")
+    got = sites(src, r"std::atomic<\s*unsigned\s*>\s*\w*\s*\[")
+    assert len(got) == 1 and got[0][0] == "esr_internal.h" and lo < got[0][1] < hi, got
