@@ -1,6 +1,7 @@
 """Single-op entry points over the C ABI (used by the parity tests and by callers that
 want one fused convolution rather than a whole network).  Tensors are torch CUDA tensors;
 only their data_ptr()/stream cross the boundary."""
+import contextlib
 import ctypes
 
 import torch
@@ -17,12 +18,68 @@ def _view(t, coff=0):
 _STORE_OF = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
 
 
+def _provided(t, what, like, shape, cmin, gran):
+    """A caller-provided output is checked as the tensor the op would allocate in its place: device and dtype of `like`, contiguous,
+    leading dims `shape`, a pixel pitch of at least `cmin` channels in multiples of the storage granule `gran`.  Returns t."""
+    if not isinstance(t, torch.Tensor) or t.device != like.device:
+        raise L.EsrError(f"{what}: must be a tensor on {like.device}")
+    if t.dtype != like.dtype:
+        raise L.EsrError(f"{what}: dtype {t.dtype}, the op stores {like.dtype}")
+    if not t.is_contiguous() or tuple(t.shape[:-1]) != tuple(shape):
+        raise L.EsrError(f"{what}: must be a contiguous [{', '.join(str(v) for v in shape)}, pitch] tensor, got {tuple(t.shape)}")
+    if t.shape[-1] % gran or t.shape[-1] < cmin:
+        raise L.EsrError(f"{what}: pitch {t.shape[-1]} must be a multiple of {gran} and hold {cmin} channels")
+    return t
+
+
+_TRACE = None       # kernel_trace(): the list that collects device symbols
+
+
+@contextlib.contextmanager
+def kernel_trace():
+    """TEST-ONLY diagnostics (tests/test_gpu_bounds.py); the engine and the models never enter it.  Inside the block every op of this module
+    that has an esr_op kind runs as a one-op list through esr_run_ops_profiled -- which dispatches to the same launcher the direct call
+    enters -- and the device symbol(s) it launched ("conv64m_kernel<true, false, false, 4, false>", ...; esr_prof_kernel_symbol) are
+    appended to the list the block yields: how a test asserts WHICH kernel a launcher selected.  Same launches, same results; two HIP
+    events and one stream synchronisation per op on top.  The list is a module global: one thread at a time, not re-entrant across
+    threads."""
+    global _TRACE
+    prev, _TRACE = _TRACE, []
+    try:
+        yield _TRACE
+    finally:
+        _TRACE = prev
+
+
+def _launch(fn, what, d, stream, kind=None, field=None):
+    """one C ABI call fn(&d, stream) -- also for a descriptor a caller filled in by hand (the tests do, for entry points without a wrapper
+    here); under kernel_trace() as a one-op list through the profiler, which records the device symbol"""
+    lib = L.lib()
+    if _TRACE is None or kind is None:
+        L.check(getattr(lib, fn)(ctypes.byref(d), ctypes.c_void_p(stream)), what)
+        return
+    op = L.Op()
+    op.kind = kind
+    setattr(op, field, d)
+    prof = ctypes.c_void_p()
+    L.check(lib.esr_prof_create(1, 1, ctypes.byref(prof)), "esr_prof_create")
+    try:
+        L.check(lib.esr_run_ops_profiled(ctypes.byref(op), 1, ctypes.c_void_p(stream), prof), what)
+        buf = ctypes.create_string_buffer(256)
+        L.check(lib.esr_prof_kernel_symbol(prof, 0, buf, 256), "esr_prof_kernel_symbol")
+        _TRACE.append(buf.value.decode())
+    finally:
+        # the profiler's events are recorded on THIS stream (0: the default stream)
+        (torch.cuda.ExternalStream(stream) if stream else torch.cuda.default_stream()).synchronize()
+        lib.esr_prof_destroy(prof)
+
+
 def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.RES_NONE,
            in_nchw=False, shuffle_out=False, out=None, out_coff=0, in_coff=0, cin=None,
            split=0, out1=None, out1_coff=0, res_coff=0, packed=None, cin_map=None, store=None,
            tail_weight=None, tail_bias=None, tail_cat=None, tail_cat_coff=0, tail_mid_act=L.ACT_NONE,
            post_weight=None, post_bias=None, post_act=L.ACT_NONE, post2_weight=None, post2_bias=None, store_main=True,
-           border=None, blocked_in=False, blocked_out1=False, wino=False, hilo=0):
+           border=None, blocked_in=False, blocked_out1=False, wino=False, hilo=0, post_out=None, post2_out=None):
     """Fused conv (k=1|3, stride 1, same padding) on the current stream.
 
     x       NHWC [N,H,W,pitch] (channels [in_coff, in_coff+cin) are read) or NCHW fp32 if in_nchw.  The dtype of an NHWC
@@ -33,6 +90,9 @@ def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.
     post_*  esr_conv_desc.post_*: post_weight [pc, cout(, 1, 1)] applied to this conv's activated output; returns (y, post).
             16-bit storage: applied to the finished fp32 result (residual included); post2_weight [pc2, pc] chains a second 1x1
             on the first (returns (y, post, post2)); store_main=False does not store y (returns None in its place)
+    post_out / post2_out   caller-provided NHWC [N,H,W,pitch] tensors for the two 1x1 results (default: freshly allocated zeros of pitch
+            round_up(channels, granule)); same dtype and device as the op's storage, pitch a multiple of the granule (4 fp32 / 8 16-bit)
+            that holds the channels, written from channel 0; EsrError otherwise
     border  esr_conv_desc.border_bias: fp32 [16, round_up(cout, 16)] table added by outside-mask (16-bit storage only)
     blocked_in / blocked_out1   esr_conv_desc.blocked8: x / out1 is a channel-blocked fp32 tensor [N, C/8, H, W, 8]
     hilo    esr_conv_desc.hilo (bf16, 3x3, 33..64 output channels): L.HILO_IN -- x is a contiguous [2, N, H, W, P] pair (value = x[0] + x[1]:
@@ -159,28 +219,38 @@ def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.
     if post_weight is not None:
         pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
         keep2 = (pack_post_s16(pw, post_bias, st) if s16 else pack_conv(pw, post_bias)).to(x.device)
-        yp = torch.zeros((n, h, w, (pw.shape[0] + gran - 1) // gran * gran), dtype=odt, device=x.device)
+        pcs = (pw.shape[0] + gran - 1) // gran * gran
+        yp = torch.zeros((n, h, w, pcs), dtype=odt, device=x.device) if post_out is None else \
+            _provided(post_out, "conv2d: post_out", torch.empty(0, dtype=odt, device=x.device), (n, h, w), pcs, gran)
         d.post_wpacked, d.post_out = ctypes.c_void_p(keep2.data_ptr()), _view(yp)
         d.post_cout, d.post_act = pw.shape[0], post_act
         if post2_weight is not None:
             keep3 = pack_post_s16(post2_weight, post2_bias, st).to(x.device)
-            yp2 = torch.zeros((n, h, w, (post2_weight.shape[0] + 7) // 8 * 8), dtype=odt, device=x.device)
+            pcs2 = (post2_weight.shape[0] + 7) // 8 * 8
+            yp2 = torch.zeros((n, h, w, pcs2), dtype=odt, device=x.device) if post2_out is None else \
+                _provided(post2_out, "conv2d: post2_out", torch.empty(0, dtype=odt, device=x.device), (n, h, w), pcs2, 8)
             d.post2_wpacked, d.post2_out, d.post2_cout = ctypes.c_void_p(keep3.data_ptr()), _view(yp2), post2_weight.shape[0]
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(lib.esr_conv2d_f32(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_conv2d_f32")
+    if (post_out is not None and post_weight is None) or (post2_out is not None and post2_weight is None):
+        raise L.EsrError("conv2d: post_out / post2_out without the post weights")
+    _launch("esr_conv2d_f32", "esr_conv2d_f32", d, stream, L.OP_CONV, "conv")
     if yp is None:
         return y
     return (y, yp) if yp2 is None else (y, yp, yp2)
 
 
 def conv_chain(x, weights, biases, post_weight=None, post_bias=None, post2_weight=None, post2_bias=None, *, act=L.ACT_LRELU, slope=0.05,
-               res_mode=L.RES_POST_ACT, post_act=L.ACT_NONE, cin=None, out=None):
+               res_mode=L.RES_POST_ACT, post_act=L.ACT_NONE, cin=None, out=None, v_out=None, c1_out=None):
     """esr_conv_chain_s16 (ABI v11): a residual block's chain of 3x3 convolutions in ONE launch on a 16-bit NHWC tensor x [N, H, W, P]
     (RLFB.forward, team04_rlfn.py:109-122): t = x; t = act(conv_i(t)) for all but the last 3x3; u = act(conv_n(t)) + x;
     v = post_act(post_weight . u + post_bias) -> stored; c1 = post2_weight . v_fp32 + post2_bias -> stored.  Returns (v, c1).
     weights: list of OIHW fp32 3x3 weights, biases: list of fp32 biases (or None).
     res_mode=L.RES_GATE is FMEN's HFAB (team03_fmen.py:60-73; four 3x3s, no post weights): t = act(conv_i(t)) for the first three,
-    y = sigmoid(conv_4(t)) * x, returned as an NHWC tensor of x's pitch (or stored into `out`, same geometry); `cin` channels of x are read."""
+    y = sigmoid(conv_4(t)) * x, returned as an NHWC tensor of x's pitch (or stored into `out`, same geometry); `cin` channels of x are read.
+    `out` is checked like every caller-provided output (x's dtype and device, contiguous [N, H, W, pitch >= x's pitch in multiples of 8]):
+    a tensor that fails the check used to reach the kernel unchecked and now raises EsrError.
+    v_out / c1_out (RLFB form): caller-provided NHWC [N, H, W, pitch] tensors of x's dtype and device for v (pitch a multiple of 16 holding
+    the first 1x1's channels) and c1 (a multiple of 8 holding the second's); default: freshly allocated zeros.  EsrError otherwise."""
     if res_mode == L.RES_GATE:
         return _hfab(x, weights, biases, act=act, slope=slope, cin=cin, out=out)
     if not x.is_cuda:
@@ -205,14 +275,15 @@ def conv_chain(x, weights, biases, post_weight=None, post_bias=None, post2_weigh
     pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
     p1 = pack_post_s16(pw, post_bias, st).to(x.device)
     p2 = pack_post_s16(post2_weight, post2_bias, st).to(x.device)
-    v = torch.zeros((n, h, w, (pw.shape[0] + 15) // 16 * 16), dtype=x.dtype, device=x.device)
-    c1 = torch.zeros((n, h, w, (post2_weight.shape[0] + 7) // 8 * 8), dtype=x.dtype, device=x.device)
+    vc, cc = (pw.shape[0] + 15) // 16 * 16, (post2_weight.shape[0] + 7) // 8 * 8
+    v = torch.zeros((n, h, w, vc), dtype=x.dtype, device=x.device) if v_out is None else _provided(v_out, "conv_chain: v_out", x, (n, h, w), vc, 16)
+    c1 = torch.zeros((n, h, w, cc), dtype=x.dtype, device=x.device) if c1_out is None else _provided(c1_out, "conv_chain: c1_out", x, (n, h, w), cc, 8)
     d.post_wpacked, d.post_out, d.post_cout, d.post_act = ctypes.c_void_p(p1.data_ptr()), _view(v), pw.shape[0], post_act
     d.post2_wpacked, d.post2_out, d.post2_cout = ctypes.c_void_p(p2.data_ptr()), _view(c1), post2_weight.shape[0]
     if not lib.esr_conv_chain_supported(ctypes.byref(d)):
         raise L.EsrError("conv_chain: no kernel for this shape (esr_conv_chain_supported)")
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(lib.esr_conv_chain_s16(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_conv_chain_s16")
+    _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, stream, L.OP_CONV_CHAIN, "chain")
     return v, c1
 
 
@@ -236,13 +307,13 @@ def _hfab(x, weights, biases, *, act, slope, cin, out):
         blob = pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device)
         keep.append(blob)
         d.wpacked[i] = blob.data_ptr()
-    y = torch.zeros((n, h, w, pitch), dtype=x.dtype, device=x.device) if out is None else out
+    y = torch.zeros((n, h, w, pitch), dtype=x.dtype, device=x.device) if out is None else _provided(out, "conv_chain: out", x, (n, h, w), pitch, 8)
     d.post_out = _view(y)
     d.post_cout = min((d.cout + 15) // 16 * 16, y.shape[-1])      # the pad channels of the last chunk too, as the per-layer store (zeros)
     if not lib.esr_conv_chain_supported(ctypes.byref(d)):
         raise L.EsrError("conv_chain: no kernel for this shape (esr_conv_chain_supported)")
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(lib.esr_conv_chain_s16(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_conv_chain_s16")
+    _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, stream, L.OP_CONV_CHAIN, "chain")
     return y
 
 
@@ -253,10 +324,11 @@ def _hilo_pair(t, what, strides):
     strides.append(t.stride(0) * t.element_size())
 
 
-def tensor2uint_device(img_sr, data_range, nonfinite=None):
+def tensor2uint_device(img_sr, data_range, nonfinite=None, *, out=None):
     """utils_image.tensor2uint on the GPU: [1,C,H,W] (or [C,H,W]) fp32 -> HWC uint8 tensor on the same device.
     nonfinite: optional 1-element int32 DEVICE tensor (caller-zeroed) that the kernel ORs 1 into when the image holds an Inf / NaN
-    (esr_tensor2uint_u8_chk) -- the harness's overflow check without a full-size isfinite pass."""
+    (esr_tensor2uint_u8_chk) -- the harness's overflow check without a full-size isfinite pass.
+    out: caller-provided contiguous uint8 [H, W, C] tensor on the same device (default: a fresh one); EsrError otherwise."""
     if not img_sr.is_cuda:
         raise L.EsrError("tensor2uint_device: tensor must live on the GPU")
     t = img_sr.detach()
@@ -265,7 +337,10 @@ def tensor2uint_device(img_sr, data_range, nonfinite=None):
         t = t[0]
     t = t.contiguous().float()
     c, h, w = t.shape
-    out = torch.empty((h, w, c), dtype=torch.uint8, device=t.device)
+    if out is None:
+        out = torch.empty((h, w, c), dtype=torch.uint8, device=t.device)
+    elif out.dtype != torch.uint8 or out.device != t.device or tuple(out.shape) != (h, w, c) or not out.is_contiguous():
+        raise L.EsrError(f"tensor2uint_device: out must be a contiguous uint8 [{h}, {w}, {c}] tensor on {t.device}")
     stream = torch.cuda.current_stream(t.device).cuda_stream
     if nonfinite is not None:
         assert nonfinite.is_cuda and nonfinite.dtype == torch.int32 and nonfinite.numel() == 1
@@ -277,10 +352,12 @@ def tensor2uint_device(img_sr, data_range, nonfinite=None):
     return out
 
 
-def ssim_sum_device(a_u8, b_u8, border=0):
+def ssim_sum_device(a_u8, b_u8, border=0, *, partials=None):
     """calculate_ssim's numerator on the GPU (utils/utils_image.py:509-554, esr_ssim_u8): the SSIM map of two HWC (or HW) uint8 CUDA
     tensors summed over the 'valid' region of the border-cropped image and all channels, as a 0-dim float64 DEVICE tensor (no host
-    synchronisation), and the number of map elements it was summed over.  ssim = sum / count."""
+    synchronisation), and the number of map elements it was summed over.  ssim = sum / count.
+    partials: caller-provided float64 [esr_ssim_partials(h, w, c, border)] tensor on the same device for the per-block sums (every entry is
+    written; default: a fresh one); EsrError otherwise."""
     if a_u8.shape != b_u8.shape:
         raise ValueError('Input images must have the same dimensions.')
     a, b = a_u8.contiguous(), b_u8.contiguous()
@@ -291,7 +368,10 @@ def ssim_sum_device(a_u8, b_u8, border=0):
     n = int(L.lib().esr_ssim_partials(h, w, c, border))
     if n == 0:
         raise L.EsrError(f"ssim_device: a {h}x{w} image cropped by {border} is smaller than the 11x11 window")
-    partials = torch.empty(n, dtype=torch.float64, device=a.device)
+    if partials is None:
+        partials = torch.empty(n, dtype=torch.float64, device=a.device)
+    elif partials.dtype != torch.float64 or partials.device != a.device or tuple(partials.shape) != (n,) or not partials.is_contiguous():
+        raise L.EsrError(f"ssim_sum_device: partials must be a contiguous float64 [{n}] tensor on {a.device}")
     stream = torch.cuda.current_stream(a.device).cuda_stream
     L.check(L.lib().esr_ssim_u8(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), h, w, c, border,
                                 ctypes.c_void_p(partials.data_ptr()), n, ctypes.c_void_p(stream)), "esr_ssim_u8")
@@ -305,13 +385,19 @@ def ssim_device(a_u8, b_u8, border=0):
     return float(s.item()) / count
 
 
-def sqerr_device(a_u8, b_u8, border=0):
+def sqerr_device(a_u8, b_u8, border=0, *, out=None):
     """sum over the border-cropped region of (a - b)^2 for two HWC uint8 CUDA tensors as a 1-element int64 DEVICE tensor:
-    no host synchronisation (the harness pipeline reads it when the image retires)."""
+    no host synchronisation (the harness pipeline reads it when the image retires).
+    out: caller-provided 1-element int64 tensor on the same device (default: a fresh one); EsrError otherwise."""
     a, b = a_u8.contiguous(), b_u8.contiguous()
     h, w = a.shape[:2]
     c = a.shape[2] if a.dim() == 3 else 1
-    acc = torch.empty(1, dtype=torch.int64, device=a.device)
+    if out is None:
+        acc = torch.empty(1, dtype=torch.int64, device=a.device)
+    elif out.dtype != torch.int64 or out.device != a.device or out.numel() != 1:
+        raise L.EsrError(f"sqerr_device: out must be a 1-element int64 tensor on {a.device}")
+    else:
+        acc = out
     stream = torch.cuda.current_stream(a.device).cuda_stream
     L.check(L.lib().esr_sqerr_u8(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), h, w, c, border,
                                  ctypes.c_void_p(acc.data_ptr()), ctypes.c_void_p(stream)), "esr_sqerr_u8")
@@ -338,10 +424,12 @@ def psnr_device(a_u8, b_u8, border=0):
 
 
 def bsconv(x, pw_weight, pw_bias, dw_weight, dw_bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.RES_NONE,
-           in_coff=0, cin=None, d_weight=None, d_bias=None, d_act=L.ACT_NONE):
+           in_coff=0, cin=None, d_weight=None, d_bias=None, d_act=L.ACT_NONE, out=None, d_out=None):
     """BSConvU in one launch (esr_bsconv_f32): act(dw3x3(pw1x1(x)) [+ res]); returns y, or (y, distilled) when the
     distillation 1x1 `d_weight` [d_cout, cin] is given.  x: NHWC [N,H,W,pitch] fp32 / bfloat16 / float16 (the storage
-    type of the op: res and the outputs have the same dtype); pw_weight [c, cin]; dw_weight [c,1,3,3]."""
+    type of the op: res and the outputs have the same dtype); pw_weight [c, cin]; dw_weight [c,1,3,3].
+    out / d_out: caller-provided NHWC [N,H,W,pitch] tensors for y / the distilled output (x's dtype and device, pitch a multiple of 4 that
+    holds the channels, written from channel 0; EsrError otherwise); default: freshly allocated zeros."""
     from .engine import pack_dw
     if not x.is_cuda:
         raise L.EsrError("bsconv: tensors must live on the GPU; there is no CPU fallback")
@@ -361,8 +449,11 @@ def bsconv(x, pw_weight, pw_bias, dw_weight, dw_bias, *, act=L.ACT_NONE, slope=0
     d.n, d.h, d.w, d.cin, d.c = n, h, w, cin, c
     d.act, d.slope, d.res_mode = act, slope, res_mode
     d.inp = _view(x, in_coff)
-    y = torch.zeros((n, h, w, (c + 3) // 4 * 4), dtype=x.dtype, device=x.device)
+    y = torch.zeros((n, h, w, (c + 3) // 4 * 4), dtype=x.dtype, device=x.device) if out is None else \
+        _provided(out, "bsconv: out", x, (n, h, w), (c + 3) // 4 * 4, 4)
     d.out = _view(y)
+    if d_out is not None and d_weight is None:
+        raise L.EsrError("bsconv: d_out without d_weight")
     if res is not None:
         d.res = _view(res)
     d.pw_packed, d.dw_packed = ctypes.c_void_p(keep[0].data_ptr()), ctypes.c_void_p(keep[1].data_ptr())
@@ -370,17 +461,21 @@ def bsconv(x, pw_weight, pw_bias, dw_weight, dw_bias, *, act=L.ACT_NONE, slope=0
     if d_weight is not None:
         dco = d_weight.shape[0]
         keep.append(pk(d_weight, d_bias))
-        yd = torch.zeros((n, h, w, (dco + 3) // 4 * 4), dtype=x.dtype, device=x.device)
+        yd = torch.zeros((n, h, w, (dco + 3) // 4 * 4), dtype=x.dtype, device=x.device) if d_out is None else \
+            _provided(d_out, "bsconv: d_out", x, (n, h, w), (dco + 3) // 4 * 4, 4)
         d.d_packed, d.d_cout, d.d_act, d.d_out = ctypes.c_void_p(keep[2].data_ptr()), dco, d_act, _view(yd)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(lib.esr_bsconv_f32(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_bsconv_f32")
+    _launch("esr_bsconv_f32", "esr_bsconv_f32", d, stream, L.OP_BSCONV, "bs")
     return y if yd is None else (y, yd)
 
 
-def channel_attention(x, w1, b1, w2, b2, *, contrast=False, nchw=False, out=None):
+def channel_attention(x, w1, b1, w2, b2, *, contrast=False, nchw=False, out=None, coff=0, out_coff=0):
     """CALayer / CCALayer (esr_channel_attention_f32): y = x * sigmoid(W2 . relu(W1 . s + b1) + b2) with s = mean over H, W
     (contrast=False, models/basicblock.py:333-348) or std + mean (contrast=True, models/team05_efdn/plainblock.py:106-122).
-    x: NHWC [N,H,W,pitch] (fp32 / bf16 / fp16) or, with nchw=True, NCHW fp32 [N,C,H,W]; w1 [cr, c(,1,1)], w2 [c, cr(,1,1)]."""
+    x: NHWC [N,H,W,pitch] (fp32 / bf16 / fp16) or, with nchw=True, NCHW fp32 [N,C,H,W]; w1 [cr, c(,1,1)], w2 [c, cr(,1,1)].
+    coff / out_coff (NHWC): first channel of the slice of x that is read / of `out` that is written (multiples of 4; the slice is
+    round_up(c, 4) channels wide and must fit the pitch: the library returns ESR_ERR_BAD_ARG otherwise).  `out`: caller-provided tensor of
+    x's dtype, device and leading dims (NHWC: any pitch that is a multiple of 4 and holds the slice; NCHW: x's shape); default zeros_like(x)."""
     from .engine import pack_dense
     if not x.is_cuda:
         raise L.EsrError("channel_attention: tensors must live on the GPU; there is no CPU fallback")
@@ -391,28 +486,39 @@ def channel_attention(x, w1, b1, w2, b2, *, contrast=False, nchw=False, out=None
     else:
         n, h, w, _ = x.shape
     keep = [pack_dense(w1.reshape(cr, c, 1, 1), b1, c, cr).to(x.device), pack_dense(w2.reshape(c, cr, 1, 1), b2, cr, c4).to(x.device)]
-    y = torch.zeros_like(x) if out is None else out
+    if nchw and (coff or out_coff):
+        raise L.EsrError("channel_attention: channel offsets are for NHWC views")
+    if out is None:
+        y = torch.zeros_like(x)
+    elif nchw:
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+            raise L.EsrError("channel_attention: an NCHW `out` has x's shape, dtype and device")
+        y = out
+    else:
+        y = _provided(out, "channel_attention: out", x, (n, h, w), out_coff + c4, 4)
     stats = torch.empty(n * 2 * c4, dtype=torch.float64, device=x.device)
     d = L.CaDesc()
     d.n, d.h, d.w, d.c, d.cr, d.contrast = n, h, w, c, cr, int(contrast)
     d.layout = L.NCHW_IN if nchw else L.NHWC
     d.storage = L.STORE[_STORE_OF[x.dtype]]
-    d.x = L.View(ctypes.c_void_p(x.data_ptr()), 0 if nchw else x.shape[-1], 0)
-    d.y = L.View(ctypes.c_void_p(y.data_ptr()), 0 if nchw else y.shape[-1], 0)
+    d.x = L.View(ctypes.c_void_p(x.data_ptr()), 0 if nchw else x.shape[-1], coff)
+    d.y = L.View(ctypes.c_void_p(y.data_ptr()), 0 if nchw else y.shape[-1], out_coff)
     d.w1, d.w2, d.stats = keep[0].data_ptr(), keep[1].data_ptr(), stats.data_ptr()
     stream = torch.cuda.current_stream(x.device).cuda_stream
     L.check(L.lib().esr_channel_attention_f32(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_channel_attention_f32")
     return y
 
 
-def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False):
+def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False, post_out=None):
     """ESA's full-resolution tail in one launch (esr_esa_apply_f32): y = x * sigmoid(conv4(bilinear(c3 -> HxW) + conv_f(c1)))
     (models/rfdn_baseline/block.py:124-129).  x: NHWC [N,H,W,pitch] (fp32 / bf16 / fp16 storage), c channels = w4.shape[0];
     c1: NHWC [N,H,W,16] of the same dtype (conv1's output, f = wf.shape[0] <= 16 channels, pads zero); c3: fp32 NHWC [N,h_lo,w_lo,16];
     wf [f,f(,1,1)], w4 [c,f(,1,1)].
     post (16-bit storage): one or two dicts(weight [cout, cin(,1,1)], bias, act, slope, res) -- 1x1 convolutions evaluated in the same
     launch (esr_esa_desc.post[]): the first on y as stored (+ res, NHWC of x's dtype), the second on the first's fp32 result.  Returns
-    (y, [out0(, out1)]) then; skip_y: y is not stored."""
+    (y, [out0(, out1)]) then; skip_y: y is not stored.
+    post_out: a list with one caller-provided NHWC [N,H,W,pitch] tensor per post (x's dtype and device, pitch a multiple of 8 that holds the
+    post's channels, written from channel 0; EsrError otherwise); default: freshly allocated zeros."""
     from .engine import pack_apply_post, pack_dense
     if not x.is_cuda:
         raise L.EsrError("esa_apply: tensors must live on the GPU; there is no CPU fallback")
@@ -427,6 +533,8 @@ def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False):
     d.x, d.y = _view(x), _view(y)
     d.c1, d.c3, d.w0, d.w1 = c1.data_ptr(), c3.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr()
     outs = []
+    if post_out is not None and (not post or len(post_out) != len(post)):
+        raise L.EsrError("esa_apply: post_out needs one tensor per post")
     if post:
         p0, p1 = post[0], (post[1] if len(post) > 1 else None)
         keep.append(pack_apply_post(p0["weight"], p0.get("bias"), None if p1 is None else p1["weight"], None if p1 is None else p1.get("bias"),
@@ -435,7 +543,8 @@ def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False):
         d.skip_y = 1 if skip_y else 0
         for k, t in enumerate(post):
             co = t["weight"].shape[0]
-            o = torch.zeros(n, h, w, (co + 7) // 8 * 8, dtype=x.dtype, device=x.device)
+            o = torch.zeros(n, h, w, (co + 7) // 8 * 8, dtype=x.dtype, device=x.device) if post_out is None else \
+                _provided(post_out[k], f"esa_apply: post_out[{k}]", x, (n, h, w), (co + 7) // 8 * 8, 8)
             outs.append(o)
             pp = d.post[k]
             pp.cout, pp.act, pp.slope = co, t.get("act", L.ACT_NONE), t.get("slope", 0.05)
@@ -443,7 +552,7 @@ def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False):
             if t.get("res") is not None:
                 pp.res_mode, pp.res = L.RES_PRE_ACT, _view(t["res"])
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    L.check(L.lib().esr_esa_apply_f32(ctypes.byref(d), ctypes.c_void_p(stream)), "esr_esa_apply_f32")
+    _launch("esr_esa_apply_f32", "esr_esa_apply_f32", d, stream, L.OP_ESA_APPLY, "esa")
     return (y, outs) if post else y
 
 

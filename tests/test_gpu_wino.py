@@ -239,8 +239,9 @@ def test_wino8_is_the_kernel_that_ran():
 
 @pytest.mark.parametrize("n,h,w", [(4, 256, 256), (1, 37, 29), (2, 5, 3), (3, 130, 70)])
 def test_wino8_blocked_input(n, h, w):
-    """channel-blocked INPUT [N, C/8, H, W, 8] (esr_conv_desc.blocked8 & ESR_BLOCKED_IN: IMDBlock's r1 / r2 since round 4) -- every size goes
-    to wino8_f32_kernel (wino_f32_kernel cannot read it); bit-identical to the NHWC input through the same kernel family"""
+    """channel-blocked INPUT [N, C/8, H, W, 8] (esr_conv_desc.blocked8 & ESR_BLOCKED_IN: IMDBlock's r1 / r2 since round 4) -- both Winograd
+    kernels read it (pix_floats / chunk_stride; wino8_f32_kernel from 4096 strips of 4 x 16, wino_f32_kernel below); bit-identical to the
+    NHWC input through the same kernel family"""
     from ntire2022_esr_amd import ops
     dev = _dev()
     g = torch.Generator().manual_seed(31 + h)
