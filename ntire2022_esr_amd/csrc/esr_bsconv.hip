@@ -404,26 +404,25 @@ extern "C" int esr_bsconv_f32(const esr_bsconv_desc* d, void* hip_stream)
     const bool s16 = d->storage == ESR_STORE_BF16 || d->storage == ESR_STORE_F16;
     if (d->storage != ESR_STORE_F32 && !s16) return ESR_ERR_BAD_ARG;
     const int cin_phys = esr_round_up(d->cin, 8), cp = esr_round_up(d->c, 4);
-    if ((d->in.pitch & 3) || (d->in.coff & 3) || d->in.coff + cin_phys > d->in.pitch) return ESR_ERR_BAD_ARG;
-    if (s16 && ((d->in.pitch & 7) || (d->in.coff & 7))) return ESR_ERR_BAD_ARG;          // 16-byte B fragments
-    if ((d->out.pitch & 3) || (d->out.coff & 3) || d->out.coff + cp > d->out.pitch) return ESR_ERR_BAD_ARG;
-    if (d->res_mode != ESR_RES_NONE && (!d->res.ptr || (d->res.pitch & 3) || (d->res.coff & 3) || d->res.coff + cp > d->res.pitch))
-        return ESR_ERR_BAD_ARG;
+    if (!esr_view_fits(d->in, 4, cin_phys)) return ESR_ERR_BAD_ARG;
+    if (s16 && !esr_view_aligned(d->in, 8)) return ESR_ERR_BAD_ARG;                      // 16-byte B fragments
+    if (!esr_view_fits(d->out, 4, cp)) return ESR_ERR_BAD_ARG;
+    if (d->res_mode != ESR_RES_NONE && !esr_view_ok(d->res, 4, cp)) return ESR_ERR_BAD_ARG;
     const int ntp = esr_round_up(d->c, 16) / 16;
     int ntd = 0, dc4 = 0;
     if (d->d_packed) {
         if (d->d_cout <= 0 || d->d_cout > 32) return ESR_ERR_UNSUPPORTED;
         dc4 = esr_round_up(d->d_cout, 4);
         ntd = esr_round_up(d->d_cout, 16) / 16;
-        if (!d->d_out.ptr || (d->d_out.pitch & 3) || (d->d_out.coff & 3) || d->d_out.coff + dc4 > d->d_out.pitch) return ESR_ERR_BAD_ARG;
+        if (!esr_view_ok(d->d_out, 4, dc4)) return ESR_ERR_BAD_ARG;
     }
     {
         const double px_all = (double)d->n * d->h * d->w;
         int maxpitch = d->in.pitch > d->out.pitch ? d->in.pitch : d->out.pitch;
         if (d->res_mode != ESR_RES_NONE && d->res.pitch > maxpitch) maxpitch = d->res.pitch;
         if (d->d_packed && d->d_out.pitch > maxpitch) maxpitch = d->d_out.pitch;
-        if (px_all * maxpitch >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
-        if ((double)d->h * d->w * d->in.pitch * 4.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+        if (!esr_fits_raw(px_all, maxpitch, 1)) return ESR_ERR_UNSUPPORTED;
+        if (!esr_fits_raw((double)d->h * d->w, d->in.pitch, 4)) return ESR_ERR_UNSUPPORTED;
     }
     BsK k;
     k.x = d->in.ptr; k.res = d->res.ptr;

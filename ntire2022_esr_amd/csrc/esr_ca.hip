@@ -204,10 +204,7 @@ extern "C" int esr_channel_attention_f32(const esr_ca_desc* d, void* hip_stream)
     if (!nchw && d->layout != ESR_NHWC) return ESR_ERR_BAD_ARG;
     const int c4 = esr_round_up(d->c, 4);
     if (nchw && d->storage != ESR_STORE_F32) return ESR_ERR_UNSUPPORTED;
-    if (!nchw) {
-        if ((d->x.pitch & 3) || (d->x.coff & 3) || d->x.coff + c4 > d->x.pitch) return ESR_ERR_BAD_ARG;
-        if ((d->y.pitch & 3) || (d->y.coff & 3) || d->y.coff + c4 > d->y.pitch) return ESR_ERR_BAD_ARG;
-    }
+    if (!nchw && (!esr_view_fits(d->x, 4, c4) || !esr_view_fits(d->y, 4, c4))) return ESR_ERR_BAD_ARG;
     if ((double)d->n * d->h * d->w * (nchw ? d->c : (d->x.pitch > d->y.pitch ? d->x.pitch : d->y.pitch)) >= 9.0e18) return ESR_ERR_UNSUPPORTED;
     CaK k;
     k.x = d->x.ptr; k.y = d->y.ptr;

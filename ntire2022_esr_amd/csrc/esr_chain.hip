@@ -716,10 +716,8 @@ int esr_conv_chain_s16(const esr_chain_desc* d, void* hip_stream)
     for (int i = 0; i < 3; ++i)
         if (!d->wpacked[i]) return ESR_ERR_BAD_ARG;
     if (!esr_conv_chain_supported(d)) return ESR_ERR_UNSUPPORTED;
-    if ((d->in.pitch & 7) || (d->in.coff & 7) || d->in.coff + 48 > d->in.pitch) return ESR_ERR_BAD_ARG;
     const int p1c8 = esr_round_up(d->post_cout, 8), p2c8 = esr_round_up(d->post2_cout, 8);
-    if ((d->post_out.pitch & 7) || (d->post_out.coff & 7) || d->post_out.coff + p1c8 > d->post_out.pitch) return ESR_ERR_BAD_ARG;
-    if ((d->post2_out.pitch & 7) || (d->post2_out.coff & 7) || d->post2_out.coff + p2c8 > d->post2_out.pitch) return ESR_ERR_BAD_ARG;
+    if (!esr_view_fits(d->in, 8, 48) || !esr_view_fits(d->post_out, 8, p1c8) || !esr_view_fits(d->post2_out, 8, p2c8)) return ESR_ERR_BAD_ARG;
     ChainK k;
     memset(&k, 0, sizeof(k));
     k.x = static_cast<const char*>(d->in.ptr);
@@ -730,8 +728,8 @@ int esr_conv_chain_s16(const esr_chain_desc* d, void* hip_stream)
     k.in_pitch = d->in.pitch; k.in_coff = d->in.coff;
     k.y1_pitch = d->post_out.pitch; k.y1_coff = d->post_out.coff; k.y2_pitch = d->post2_out.pitch; k.y2_coff = d->post2_out.coff;
     k.p1_cout8 = p1c8; k.p2_cout8 = p2c8;
-    k.slope = d->act == ESR_ACT_LRELU ? d->slope : (d->act == ESR_ACT_RELU ? 0.f : 1.f);
-    k.p1_slope = d->post_act == ESR_ACT_LRELU ? d->slope : (d->post_act == ESR_ACT_RELU ? 0.f : 1.f);
+    k.slope = esr_act_slope(d->act, d->slope);
+    k.p1_slope = esr_act_slope(d->post_act, d->slope);
     int g = 2;
     {
         int sx2, sy2, rs2, sx3, sy3, rs3;
@@ -743,7 +741,7 @@ int esr_conv_chain_s16(const esr_chain_desc* d, void* hip_stream)
     }
     k.WS = g == 3 ? ChGeo<3>::WS : ChGeo<2>::WS;
     const double jobs = (double)d->n * k.SX * k.SY;
-    if (jobs >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+    if (jobs >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
     k.njobs = (int)jobs;
 #ifdef ESR_CHAIN_TRACE
     k.trace = g_chain_trace;

@@ -735,11 +735,8 @@ int esr_dwconv3x3_f32(const esr_conv_desc* d, void* hip_stream)
     if (d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;
     if (d->res_mode == ESR_RES_GATE) return ESR_ERR_UNSUPPORTED;           // the gate epilogue: esr_conv2d_f32 only
     const int cp = esr_round_up(d->cin, 4);
-    if ((d->in.pitch & 3) || (d->in.coff & 3) || d->in.coff + cp > d->in.pitch) return ESR_ERR_BAD_ARG;
-    if ((d->out0.pitch & 3) || (d->out0.coff & 3) || d->out0.coff + cp > d->out0.pitch) return ESR_ERR_BAD_ARG;
-    if (d->res_mode != ESR_RES_NONE &&
-        (!d->res.ptr || (d->res.pitch & 3) || (d->res.coff & 3) || d->res.coff + cp > d->res.pitch))
-        return ESR_ERR_BAD_ARG;
+    if (!esr_view_fits(d->in, 4, cp) || !esr_view_fits(d->out0, 4, cp)) return ESR_ERR_BAD_ARG;
+    if (d->res_mode != ESR_RES_NONE && !esr_view_ok(d->res, 4, cp)) return ESR_ERR_BAD_ARG;
     DwK k;
     k.x = d->in.ptr; k.wp = static_cast<const float*>(d->wpacked);
     k.res = d->res.ptr; k.y = d->out0.ptr;
@@ -890,13 +887,11 @@ int esr_esa_apply_f32(const esr_esa_desc* d, void* hip_stream)
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->c > 64 || d->f <= 0 || d->f > FP) return ESR_ERR_BAD_ARG;
     if (d->h_lo <= 0 || d->w_lo <= 0) return ESR_ERR_TOO_SMALL;
     const int cp4 = esr_round_up(d->c, 4);
-    if ((d->x.pitch & 3) || (d->x.coff & 3) || d->x.coff + cp4 > d->x.pitch) return ESR_ERR_BAD_ARG;
-    if ((d->y.pitch & 3) || (d->y.coff & 3) || d->y.coff + cp4 > d->y.pitch) return ESR_ERR_BAD_ARG;
+    if (!esr_view_fits(d->x, 4, cp4) || !esr_view_fits(d->y, 4, cp4)) return ESR_ERR_BAD_ARG;
     if (d->storage != ESR_STORE_F32) {
         // 16-bit storage moves 8 channels (16 bytes) per lane: granules of 8, padded channels are read and written as zeros
         const int cp8 = esr_round_up(d->c, 8);
-        if ((d->x.pitch & 7) || (d->x.coff & 7) || d->x.coff + cp8 > d->x.pitch) return ESR_ERR_BAD_ARG;
-        if ((d->y.pitch & 7) || (d->y.coff & 7) || d->y.coff + cp8 > d->y.pitch) return ESR_ERR_BAD_ARG;
+        if (!esr_view_fits(d->x, 8, cp8) || !esr_view_fits(d->y, 8, cp8)) return ESR_ERR_BAD_ARG;
     }
     EsaK k;
     k.x = d->x.ptr; k.c1 = d->c1;
@@ -907,7 +902,7 @@ int esr_esa_apply_f32(const esr_esa_desc* d, void* hip_stream)
     k.sh = (float)d->h_lo / (float)d->h;      // ATen area_pixel_compute_scale: float(in) / out
     k.sw = (float)d->w_lo / (float)d->w;
     const long long npix = (long long)d->n * d->h * d->w;
-    if (npix >= 2147483647LL) return ESR_ERR_UNSUPPORTED;                 // 32-bit pixel indices inside the kernels
+    if (npix >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;                  // 32-bit pixel indices inside the kernels
     // post chain (ABI v8)
     int np0 = 0, np1 = 0;
     k.pimg = nullptr; k.pres = nullptr; k.pout0 = nullptr; k.pout1 = nullptr;
@@ -918,26 +913,25 @@ int esr_esa_apply_f32(const esr_esa_desc* d, void* hip_stream)
         const esr_esa_post& p0 = d->post[0];
         const esr_esa_post& p1 = d->post[1];
         if (p0.cout <= 0 || p0.cout > 64 || p1.cout < 0 || p1.cout > 32) return ESR_ERR_UNSUPPORTED;
-        auto view_ok = [](const esr_view& v, int c8) { return v.ptr && !(v.pitch & 7) && !(v.coff & 7) && v.coff + c8 <= v.pitch; };
         auto act_ok = [](int a) { return a == ESR_ACT_NONE || a == ESR_ACT_LRELU || a == ESR_ACT_RELU || a == ESR_ACT_GELU; };
         k.p0_c8 = esr_round_up(p0.cout, 8);
-        if (!view_ok(p0.out, k.p0_c8) || !act_ok(p0.act)) return ESR_ERR_BAD_ARG;
+        if (!esr_view_ok(p0.out, 8, k.p0_c8) || !act_ok(p0.act)) return ESR_ERR_BAD_ARG;
         if (p0.res_mode != ESR_RES_NONE && p0.res_mode != ESR_RES_PRE_ACT) return ESR_ERR_UNSUPPORTED;
-        if (p0.res_mode == ESR_RES_PRE_ACT && !view_ok(p0.res, k.p0_c8)) return ESR_ERR_BAD_ARG;
+        if (p0.res_mode == ESR_RES_PRE_ACT && !esr_view_ok(p0.res, 8, k.p0_c8)) return ESR_ERR_BAD_ARG;
         np0 = (p0.cout + 31) / 32;
         k.pimg = static_cast<const unsigned short*>(d->post_w);
         k.pout0 = p0.out.ptr; k.pout0_pitch = p0.out.pitch; k.pout0_coff = p0.out.coff;
         k.p0_res = p0.res_mode == ESR_RES_PRE_ACT;
         if (k.p0_res) { k.pres = p0.res.ptr; k.pres_pitch = p0.res.pitch; k.pres_coff = p0.res.coff; }
         k.p0_act = p0.act;
-        k.p0_slope = p0.act == ESR_ACT_LRELU ? p0.slope : (p0.act == ESR_ACT_RELU ? 0.f : 1.f);
+        k.p0_slope = esr_act_slope(p0.act, p0.slope);
         if (p1.cout > 0) {
             k.p1_c8 = esr_round_up(p1.cout, 8);
-            if (!view_ok(p1.out, k.p1_c8) || !act_ok(p1.act) || p1.res_mode != ESR_RES_NONE) return ESR_ERR_BAD_ARG;
+            if (!esr_view_ok(p1.out, 8, k.p1_c8) || !act_ok(p1.act) || p1.res_mode != ESR_RES_NONE) return ESR_ERR_BAD_ARG;
             np1 = (p1.cout + 31) / 32;
             k.pout1 = p1.out.ptr; k.pout1_pitch = p1.out.pitch; k.pout1_coff = p1.out.coff;
             k.p1_act = p1.act;
-            k.p1_slope = p1.act == ESR_ACT_LRELU ? p1.slope : (p1.act == ESR_ACT_RELU ? 0.f : 1.f);
+            k.p1_slope = esr_act_slope(p1.act, p1.slope);
         }
         k.skip_y = d->skip_y ? 1 : 0;
         if (!esa_post_variant((cp4 + 31) / 32, np0, np1)) return ESR_ERR_UNSUPPORTED;

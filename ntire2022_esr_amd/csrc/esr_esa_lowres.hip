@@ -480,7 +480,7 @@ extern "C" int esr_esa_lowres_f32(const esr_esa_lowres_desc* d, void* hip_stream
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int tx = (W3 + PT - 1) / PT, ty = (H3 + PT - 1) / PT;
-    if ((long long)d->n * tx * ty >= 2147483647LL) return ESR_ERR_UNSUPPORTED;
+    if ((long long)d->n * tx * ty >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)(d->n * tx * ty));
     const float* w0 = static_cast<const float*>(d->w_s2);
     float* pooled = static_cast<float*>(d->pooled);

@@ -203,7 +203,7 @@ bool act_ok(int a) { return a == ESR_ACT_NONE || a == ESR_ACT_RELU || a == ESR_A
 int launch_pool7(const void* x, float* y, int storage, int n, int h, int w, int h7, int w7, hipStream_t st)
 {
     const long long npix = (long long)n * h7 * w7;
-    if ((npix + 63) / 64 >= 2147483647LL) return ESR_ERR_UNSUPPORTED;
+    if ((npix + 63) / 64 >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)((npix + 63) / 64));
     switch (storage) {
         case ESR_STORE_F32: esr_note_kernel("esa_pool7_kernel<0>"); hipLaunchKernelGGL(esa_pool7_kernel<ESR_STORE_F32>, grid, dim3(256), 0, st, x, y, n, h, w, h7, w7); break;
@@ -230,7 +230,7 @@ int esr_esa_pool7_lowres(const esr_esa_lowres_desc* d, void* hip_stream)
     Pool7K k;
     k.H7 = H7; k.W7 = W7;
     k.tiles_x = (W7 + OT - 1) / OT; k.tiles_y = (H7 + OT - 1) / OT;
-    if ((long long)d->n * k.tiles_x * k.tiles_y >= 2147483647LL) return ESR_ERR_UNSUPPORTED;
+    if ((long long)d->n * k.tiles_x * k.tiles_y >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     float* pooled = static_cast<float*>(d->pooled);
     int rc = launch_pool7(d->x.ptr, pooled, d->storage, d->n, d->h, d->w, H7, W7, st);

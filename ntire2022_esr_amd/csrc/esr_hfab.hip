@@ -254,8 +254,7 @@ int esr_hfab_s16(const esr_chain_desc* d, void* hip_stream)
         if (!d->wpacked[i]) return ESR_ERR_BAD_ARG;
     if (!esr_hfab_supported(d)) return ESR_ERR_UNSUPPORTED;
     const int cout8 = esr_round_up(d->post_cout, 8);
-    if ((d->in.pitch & 7) || (d->in.coff & 7) || d->in.coff + esr_round_up(d->cin, 8) > d->in.pitch) return ESR_ERR_BAD_ARG;
-    if ((d->post_out.pitch & 7) || (d->post_out.coff & 7) || d->post_out.coff + cout8 > d->post_out.pitch) return ESR_ERR_BAD_ARG;
+    if (!esr_view_fits(d->in, 8, esr_round_up(d->cin, 8)) || !esr_view_fits(d->post_out, 8, cout8)) return ESR_ERR_BAD_ARG;
     HfabK k;
     memset(&k, 0, sizeof(k));
     k.x = static_cast<const char*>(d->in.ptr);
@@ -270,7 +269,7 @@ int esr_hfab_s16(const esr_chain_desc* d, void* hip_stream)
     k.tiles_x = (d->w + HF_T - 1) / HF_T;
     k.tiles_y = (d->h + HF_T - 1) / HF_T;
     const double nt = (double)d->n * k.tiles_x * k.tiles_y;
-    if (nt >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+    if (nt >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
     k.ntiles = (int)nt;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const bool bf16 = d->storage == ESR_STORE_BF16;

@@ -838,8 +838,8 @@ inline bool imdb_tail_shape(const ConvK& k)
 {
     if (k.nchunks != IT_NCH || k.cat_chunks != IT_CAT || k.cout_store != 64) return false;
     if (k.res_mode != ESR_RES_NONE && k.res_mode != ESR_RES_PRE_ACT) return false;
-    const double px = (double)k.H * k.W * 4.0;
-    return px * k.in_pitch < 2147483647.0 && px * k.cat_pitch < 2147483647.0 && (k.res_mode == ESR_RES_NONE || px * k.res_pitch < 2147483647.0);
+    const double px = (double)k.H * k.W;
+    return esr_fits_raw(px, k.in_pitch, 4) && esr_fits_raw(px, k.cat_pitch, 4) && (k.res_mode == ESR_RES_NONE || esr_fits_raw(px, k.res_pitch, 4));
 }
 
 int launch_conv_tail(const ConvK& k, hipStream_t st)
@@ -1042,33 +1042,27 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
         // the network head with 16-bit activations downstream: fp32 NCHW input (exact), fp32 MFMA, 16-bit NHWC store
         if (d->out_layout != ESR_NHWC || d->res_mode != ESR_RES_NONE || d->tail_wpacked || d->post_wpacked) return ESR_ERR_UNSUPPORTED;
         if (d->split > 0 && d->split < d->cout) return ESR_ERR_UNSUPPORTED;
-        if ((d->out0.pitch & 7) || (d->out0.coff & 7) || d->out0.coff + esr_round_up(d->cout, 8) > d->out0.pitch) return ESR_ERR_BAD_ARG;
+        if (!esr_view_fits(d->out0, 8, esr_round_up(d->cout, 8))) return ESR_ERR_BAD_ARG;
     }
-    if (!in_nchw && ((d->in.pitch & 3) || (d->in.coff & 3))) return ESR_ERR_BAD_ARG;
     const int cin_phys = in_nchw ? CHUNK : esr_round_up(d->cin, CHUNK);
-    if (!in_nchw && d->in.coff + cin_phys > d->in.pitch) return ESR_ERR_BAD_ARG;   // chunk reads stay inside the pixel
+    if (!in_nchw && !esr_view_fits(d->in, 4, cin_phys)) return ESR_ERR_BAD_ARG;   // chunk reads stay inside the pixel
     // fused 1x1 tail: the epilogue fields describe the 1x1's output
     const bool tail = d->tail_wpacked != nullptr;
     if (tail) {
         if (d->ksize != 3 || in_nchw || d->out_layout != ESR_NHWC || d->cout > 16) return ESR_ERR_UNSUPPORTED;
         if (d->tail_cat_c <= 0 || (d->tail_cat_c & 15) || d->tail_cat_c + 16 > 16 * TAIL_C16) return ESR_ERR_UNSUPPORTED;
         if (d->tail_cout <= 48 || d->tail_cout > 64) return ESR_ERR_UNSUPPORTED;
-        if (!d->tail_cat.ptr || (d->tail_cat.pitch & 3) || (d->tail_cat.coff & 3) || d->tail_cat.coff + d->tail_cat_c > d->tail_cat.pitch)
-            return ESR_ERR_BAD_ARG;
+        if (!esr_view_ok(d->tail_cat, 4, d->tail_cat_c)) return ESR_ERR_BAD_ARG;
     }
     const bool post = d->post_wpacked != nullptr;
     if (post) {
         if (tail || d->ksize != 3 || in_nchw || d->out_layout != ESR_NHWC || d->cout <= 48 || d->cout > 64 ||
             d->post_cout <= 0 || d->post_cout > 32)
             return ESR_ERR_UNSUPPORTED;
-        const bool res_is_in = d->res_mode == ESR_RES_PRE_ACT && d->cin == d->cout && d->res.ptr == d->in.ptr &&
-                               d->res.pitch == d->in.pitch && d->res.coff == d->in.coff;
-        if (d->res_mode != ESR_RES_NONE && !res_is_in) return ESR_ERR_UNSUPPORTED;
+        if (d->res_mode != ESR_RES_NONE && !esr_res_is_input(d, 1)) return ESR_ERR_UNSUPPORTED;
         if (d->split > 0 && d->split < d->cout) return ESR_ERR_UNSUPPORTED;
-        const int pc4 = esr_round_up(d->post_cout, 4);
-        if (!d->post_out.ptr || (d->post_out.pitch & 3) || (d->post_out.coff & 3) || d->post_out.coff + pc4 > d->post_out.pitch)
-            return ESR_ERR_BAD_ARG;
-        if ((double)d->n * d->h * d->w * d->post_out.pitch >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+        if (!esr_view_ok(d->post_out, 4, esr_round_up(d->post_cout, 4))) return ESR_ERR_BAD_ARG;
+        if (!esr_fits_raw((double)d->n * d->h * d->w, d->post_out.pitch, 1)) return ESR_ERR_UNSUPPORTED;
         // the 1x1 reads the conv's output as 8-channel chunks when it has to run as a launch of its own (small shapes)
         if (d->out0.coff + esr_round_up(d->cout, CHUNK) > d->out0.pitch) return ESR_ERR_BAD_ARG;
     }
@@ -1080,19 +1074,12 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
     if (d->out_layout == ESR_NCHW_SHUFFLE4) {
         if (ecout % 16) return ESR_ERR_UNSUPPORTED;
     } else if (d->out_layout == ESR_NHWC) {
-        if ((d->out0.pitch & 3) || (d->out0.coff & 3) || d->out0.coff + split > d->out0.pitch) return ESR_ERR_BAD_ARG;
-        if (split < cout4) {
-            if (!d->out1.ptr || (d->out1.pitch & 3) || (d->out1.coff & 3) ||
-                d->out1.coff + (cout4 - split) > d->out1.pitch)
-                return ESR_ERR_BAD_ARG;
-        }
+        if (!esr_view_fits(d->out0, 4, split)) return ESR_ERR_BAD_ARG;
+        if (split < cout4 && !esr_view_ok(d->out1, 4, cout4 - split)) return ESR_ERR_BAD_ARG;
     } else {
         return ESR_ERR_BAD_ARG;
     }
-    if (d->res_mode != ESR_RES_NONE) {
-        if (!d->res.ptr || (d->res.pitch & 3) || (d->res.coff & 3) || d->res.coff + cout4 > d->res.pitch)
-            return ESR_ERR_BAD_ARG;
-    }
+    if (d->res_mode != ESR_RES_NONE && !esr_view_ok(d->res, 4, cout4)) return ESR_ERR_BAD_ARG;
     // 32-bit element offsets inside the kernel; per-image raw buffers < 2 GiB (OOB offset 0x80000000)
     {
         const double px_all = (double)d->n * d->h * d->w, px_img = (double)d->h * d->w;
@@ -1100,8 +1087,8 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
         if (d->out_layout == ESR_NHWC) maxpitch = maxpitch > d->out0.pitch ? maxpitch : d->out0.pitch;
         if (d->out_layout == ESR_NHWC && d->out1.ptr) maxpitch = maxpitch > d->out1.pitch ? maxpitch : d->out1.pitch;
         if (d->res_mode != ESR_RES_NONE) maxpitch = maxpitch > d->res.pitch ? maxpitch : d->res.pitch;
-        if (px_all * maxpitch >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
-        if (px_img * (in_nchw ? d->cin : d->in.pitch) * 4.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+        if (!esr_fits_raw(px_all, maxpitch, 1)) return ESR_ERR_UNSUPPORTED;
+        if (!esr_fits_raw(px_img, in_nchw ? d->cin : d->in.pitch, 4)) return ESR_ERR_UNSUPPORTED;
     }
 
     // channel-blocked views: the bits are validated BEFORE the Winograd dispatch (which knows IN / OUT1 only: anything else would run
@@ -1137,16 +1124,16 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
     k.y0_blk = (d->blocked8 & ESR_BLOCKED_OUT0) ? 1 : 0;
     k.res_blk = (d->blocked8 & ESR_BLOCKED_RES) ? 1 : 0;
     // blocked out0 / res (the fused IMDB tail only, checked again where the tail shape is known): whole planes
-    if (k.y0_blk && ((d->out0.pitch & 7) || (d->out0.coff & 7) || (double)d->h * d->w * d->out0.pitch * 4.0 >= 2147483647.0)) return ESR_ERR_UNSUPPORTED;
-    if (k.res_blk && (d->res_mode != ESR_RES_PRE_ACT || (d->res.pitch & 7) || (d->res.coff & 7))) return ESR_ERR_UNSUPPORTED;
+    const double px = (double)d->h * d->w;
+    if (k.y0_blk && (!esr_view_aligned(d->out0, 8) || !esr_fits_raw(px, d->out0.pitch, 4))) return ESR_ERR_UNSUPPORTED;
+    if (k.res_blk && (d->res_mode != ESR_RES_PRE_ACT || !esr_view_aligned(d->res, 8))) return ESR_ERR_UNSUPPORTED;
     if (k.y1_blk) {
-        if (d->out_layout != ESR_NHWC || tail || post || store16 || split >= cout4 || d->ksize != 3 || in_nchw || d->cout <= 48 || d->cout > 64 || (d->out1.pitch & 7) || (d->out1.coff & 7) || (split & 7) ||
-            (double)d->h * d->w * d->out1.pitch * 4.0 >= 2147483647.0)
+        if (d->out_layout != ESR_NHWC || tail || post || store16 || split >= cout4 || d->ksize != 3 || in_nchw || d->cout <= 48 || d->cout > 64 || !esr_view_aligned(d->out1, 8) || (split & 7) ||
+            !esr_fits_raw(px, d->out1.pitch, 4))
             return ESR_ERR_UNSUPPORTED;
     }
-    if (k.in_blk && (!tail || in_nchw || (d->in.pitch & 7) || (d->in.coff & 7))) return ESR_ERR_UNSUPPORTED;
-    if (!tail && d->ksize == 3 && !in_nchw && d->res_mode == ESR_RES_PRE_ACT && d->cin == d->cout &&
-        d->res.ptr == d->in.ptr && d->res.pitch == d->in.pitch && d->res.coff == d->in.coff) {
+    if (k.in_blk && (!tail || in_nchw || !esr_view_aligned(d->in, 8))) return ESR_ERR_UNSUPPORTED;
+    if (!tail && d->ksize == 3 && !in_nchw && esr_res_is_input(d, 1)) {
         k.res_in = 1;                               // residual == input: added from the staged input tile inside the K loop
         k.res_mode = ESR_RES_NONE;
     }
@@ -1186,10 +1173,7 @@ int esr_conv2d_f32(const esr_conv_desc* d, void* hip_stream)
         k.cat = static_cast<const float*>(d->tail_cat.ptr);
         k.cat_pitch = d->tail_cat.pitch; k.cat_coff = d->tail_cat.coff;
         k.mid_act = d->tail_mid_act;
-        {
-            const double px_all = (double)d->n * d->h * d->w;
-            if (px_all * d->tail_cat.pitch >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
-        }
+        if (!esr_fits_raw((double)d->n * d->h * d->w, d->tail_cat.pitch, 1)) return ESR_ERR_UNSUPPORTED;
         if ((k.in_blk || k.y0_blk || k.res_blk) && !imdb_tail_shape(k)) return ESR_ERR_UNSUPPORTED;      // only imdb_tail_kernel knows the blocked layouts
         return launch_conv_tail(k, st);
     }

@@ -58,6 +58,32 @@ void esr_note_kernel(const char* fmt, ...);
 static inline const char* esr_tf(bool b) { return b ? "true" : "false"; }
 static inline int esr_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// THE acceptance tests of a declared tensor view (tests/test_view_validation.py sweeps every launcher's).  `granule` is 4 channels for
+// fp32 views (16-byte lanes) and 8 for 16-bit ones, a power of two; `channels` is what the kernel touches from coff on -- the stored
+// count rounded up to the granule, or less than the K chunks under the tight pitch (esr_conv2d_s16).  _aligned: pitch and coff are whole
+// granules; _fits: and the slice lies inside the pixel; _ok: and the pointer is set (where no earlier check has looked at it)
+static inline bool esr_view_aligned(const esr_view& v, int granule) { return !(v.pitch & (granule - 1)) && !(v.coff & (granule - 1)); }
+static inline bool esr_view_fits(const esr_view& v, int granule, int channels) { return esr_view_aligned(v, granule) && v.coff + channels <= v.pitch; }
+static inline bool esr_view_ok(const esr_view& v, int granule, int channels) { return v.ptr && esr_view_fits(v, granule, channels); }
+
+// Raw buffers address 2 GiB: the byte size of ONE IMAGE of a view the kernel reads or writes through a buffer resource
+// (pixels x pitch x element size) stays below it, as does whatever a kernel holds in a 32-bit int -- element offsets over the whole
+// batch (esr_fits_raw with elem_bytes = 1), tile, job and pixel counts (ESR_INDEX_LIMIT)
+constexpr double ESR_RAW_LIMIT = 2147483647.0;
+constexpr long long ESR_INDEX_LIMIT = 2147483647LL;
+static inline bool esr_fits_raw(double pixels, int pitch, int elem_bytes) { return pixels * pitch * elem_bytes < ESR_RAW_LIMIT; }
+
+// "the residual is the input": a pre-activation residual over the view the conv reads, which the kernel then adds from its staged input
+// tile.  `chunk`: the channel counts agree after rounding up to it -- 16 for the 16-bit kernels (K chunks), 1 for the fp32 ones
+static inline bool esr_res_is_input(const esr_conv_desc* d, int chunk)
+{
+    return d->res_mode == ESR_RES_PRE_ACT && esr_round_up(d->cin, chunk) == esr_round_up(d->cout, chunk) && d->res.ptr == d->in.ptr &&
+           d->res.pitch == d->in.pitch && d->res.coff == d->in.coff;
+}
+
+// the slope a kernel's max(v, slope * v) epilogue takes: LeakyReLU's own, 0 for ReLU, 1 for every other activation (identity)
+static inline float esr_act_slope(int act, float slope) { return act == ESR_ACT_LRELU ? slope : (act == ESR_ACT_RELU ? 0.f : 1.f); }
+
 // esr_s16.hip: NHWC convolution on 16-bit storage (called by esr_conv2d_f32 when d->storage != ESR_STORE_F32)
 int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream);
 int esr_s16_block_waves(const esr_conv_desc* d);      // 4: two 4-wave blocks per CU (16 x 16 tiles), 8: one 8-wave block (16 x 32)

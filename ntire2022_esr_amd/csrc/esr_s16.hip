@@ -863,13 +863,6 @@ size_t s16_lds_bytes(int nchunks, int nt, int ksize, int nw, int ring, size_t po
     return (size_t)nchunks * pairs * nt * 1024 + post_bytes + (size_t)ring * npieces * 1024;
 }
 
-// residual == input of a 3x3 with as many output as input chunks: taken from the staged tile (S16K.res_in), not from HBM
-static bool s16_res_is_input(const esr_conv_desc* d)
-{
-    return d->ksize == 3 && d->res_mode == ESR_RES_PRE_ACT && esr_round_up(d->cin, 16) == esr_round_up(d->cout, 16) && d->res.ptr == d->in.ptr &&
-           d->res.pitch == d->in.pitch && d->res.coff == d->in.coff;
-}
-
 // the magic division of a tile index (S16K.magic_x / magic_y) is exact while n * tiles_x * tiles_y * max(tiles_x, tiles_y) < 2^32
 static bool s16_magic_fits(const esr_conv_desc* d, int rows)
 {
@@ -894,7 +887,7 @@ static bool s16_four_waves(const esr_conv_desc* d)
 {
     const int nt = esr_round_up(d->cout, 16) / 16, nch = esr_round_up(d->cin, 16) / 16;
     const long t16 = (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16);
-    const bool res_hbm = d->res_mode != ESR_RES_NONE && !s16_res_is_input(d);
+    const bool res_hbm = d->res_mode != ESR_RES_NONE && !(d->ksize == 3 && esr_res_is_input(d, 16));
     if (d->ksize != 3 || nt != 3 || d->border_bias || d->post_wpacked || res_hbm || d->out_layout != ESR_NHWC || d->in_seg_stride != 0) return false;
     if (d->hilo && !(d->hilo == ESR_HILO_OUT && nch == 1 && t16 < 4096)) return false;
     return t16 >= 512 && s16_lds_bytes(nch, nt, 3, 4, RING_MIN, 1024) <= (size_t)LDS_LIMIT / 2;
@@ -931,7 +924,7 @@ static S16Path s16_select(const esr_conv_desc* d, bool any_range)
     const bool post = d->post_wpacked != nullptr, gelu = d->act == ESR_ACT_GELU, post_gelu = d->post_act == ESR_ACT_GELU;
     const bool reg = d->ksize == 3 && d->out_layout == ESR_NHWC && d->in_seg_stride == 0 && !(d->split > 0 && d->split < d->cout);
     const bool reg16 = reg && t16 >= 256 && fits16;
-    const bool res_in = s16_res_is_input(d), no_res_hbm = d->res_mode == ESR_RES_NONE || res_in;
+    const bool res_in = d->ksize == 3 && esr_res_is_input(d, 16), no_res_hbm = d->res_mode == ESR_RES_NONE || res_in;
     // the post chain's fused variant, every post image resident in the storage's full precision (bf16: hi + lo)
     int pnt1 = 0, pnt2 = 0, post_lo = 0, ring = 0;
     size_t lds = 0;
@@ -1006,19 +999,17 @@ static bool rfdb_tail_takes(const esr_conv_desc* d)
     if (d->split > 0 && d->split < d->tail_cout) return false;
     if (!d->post_wpacked || d->post2_wpacked || d->post_cout < 1 || d->post_cout > 16) return false;
     if (d->post_act != ESR_ACT_NONE && d->post_act != ESR_ACT_LRELU && d->post_act != ESR_ACT_RELU) return false;
-    if (!d->in.ptr || (d->in.pitch & 7) || (d->in.coff & 7) || d->in.coff + esr_round_up(d->cin, 8) > d->in.pitch) return false;     // (tight pitch: esr_conv2d_s16)
-    if (!d->tail_cat.ptr || (d->tail_cat.pitch & 7) || (d->tail_cat.coff & 7) || d->tail_cat.coff + 32 > d->tail_cat.pitch || d->tail_seg_stride16 <= 0) return false;
-    if (!d->out0.ptr || (d->out0.pitch & 7) || (d->out0.coff & 7) || d->out0.coff + esr_round_up(d->tail_cout, 8) > d->out0.pitch) return false;
-    if (!d->post_out.ptr || (d->post_out.pitch & 7) || (d->post_out.coff & 7) || d->post_out.coff + esr_round_up(d->post_cout, 8) > d->post_out.pitch) return false;
-    const double px = (double)d->h * d->w * 2.0, lim = 2147483647.0 - 1048576.0;
+    if (!esr_view_ok(d->in, 8, esr_round_up(d->cin, 8))) return false;                       // (tight pitch: esr_conv2d_s16)
+    if (!esr_view_ok(d->tail_cat, 8, 32) || d->tail_seg_stride16 <= 0) return false;
+    if (!esr_view_ok(d->out0, 8, esr_round_up(d->tail_cout, 8)) || !esr_view_ok(d->post_out, 8, esr_round_up(d->post_cout, 8))) return false;
+    const double px = (double)d->h * d->w * 2.0, lim = ESR_RAW_LIMIT - 1048576.0;
     if (px * d->in.pitch >= lim || px * d->tail_cat.pitch >= lim || px * d->out0.pitch >= lim || px * d->post_out.pitch >= lim) return false;
     return (long)d->n * ((d->w + TILE - 1) / TILE) * ((d->h + 15) / 16) >= 256 && s16_magic_fits(d, 16);
 }
 
 static int run_rfdb_tail(const esr_conv_desc* d, bool bf16, hipStream_t st)
 {
-    S16K k;
-    memset(&k, 0, sizeof(k));
+    S16K k{};
     const int nt = esr_round_up(d->cout, 16) / 16, ot = esr_round_up(d->post_cout, 16) / 16, nch = esr_round_up(d->cin, 16) / 16;
     const int kt = esr_round_up(d->tail_cout, 16) / 16;
     k.x = static_cast<const char*>(d->in.ptr);
@@ -1030,7 +1021,7 @@ static int run_rfdb_tail(const esr_conv_desc* d, bool bf16, hipStream_t st)
     k.act = d->tail_mid_act;
     k.border = d->border_bias;
     k.in_pitch = d->in.pitch; k.in_coff = d->in.coff;
-    k.slope = d->tail_mid_act == ESR_ACT_LRELU ? d->slope : (d->tail_mid_act == ESR_ACT_RELU ? 0.f : 1.f);
+    k.slope = esr_act_slope(d->tail_mid_act, d->slope);
     k.tw = static_cast<const char*>(d->tail_wpacked);
     k.cat = static_cast<const char*>(d->tail_cat.ptr);
     k.cat_pitch = d->tail_cat.pitch; k.cat_coff = d->tail_cat.coff;
@@ -1044,7 +1035,7 @@ static int run_rfdb_tail(const esr_conv_desc* d, bool bf16, hipStream_t st)
     k.py1 = static_cast<char*>(d->post_out.ptr);
     k.py1_pitch = d->post_out.pitch; k.py1_coff = d->post_out.coff;
     k.p1_cout8 = esr_round_up(d->post_cout, 8);
-    k.p1_slope = d->post_act == ESR_ACT_LRELU ? d->slope : (d->post_act == ESR_ACT_RELU ? 0.f : 1.f);
+    k.p1_slope = esr_act_slope(d->post_act, d->slope);
     k.out_layout = ESR_NHWC;
     s16_tile_grid(k, 16);
     return esr_launch_rfdb_tail(k, bf16, st);
@@ -1059,9 +1050,7 @@ int s16_post_plan(const esr_conv_desc* d, int nt, int nchunks, int* pnt1, int* p
     *pnt1 = esr_round_up(d->post_cout, 16) / 16;
     *pnt2 = d->post2_wpacked ? 1 : 0;
     if (*pnt2 && (d->post2_cout <= 0 || d->post2_cout > 16)) return ESR_ERR_UNSUPPORTED;
-    const bool res_is_in = d->res_mode == ESR_RES_PRE_ACT && esr_round_up(d->cin, 16) == esr_round_up(d->cout, 16) && d->res.ptr == d->in.ptr &&
-                           d->res.pitch == d->in.pitch && d->res.coff == d->in.coff;
-    const bool gres = d->res_mode != ESR_RES_NONE && !res_is_in;
+    const bool gres = d->res_mode != ESR_RES_NONE && !esr_res_is_input(d, 16);
     if (!post_variant_exists(d->ksize, nt, gres, *pnt1, *pnt2)) return ESR_ERR_UNSUPPORTED;
     // fp16 storage: the post weights' low parts (and the activations' low parts, see hilo) are not needed -- 11 mantissa bits, the
     // network's own storage precision; bf16 keeps hi + lo wherever the images fit
@@ -1265,7 +1254,7 @@ extern "C" int esr_pack_input_s16(const esr_conv_desc* d, void* hip_stream)
     if (!d || !d->in.ptr || !d->out0.ptr || d->n <= 0 || d->h <= 0 || d->w <= 0) return ESR_ERR_BAD_ARG;
     if (d->cin <= 0 || d->cin > 4) return ESR_ERR_UNSUPPORTED;
     if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return ESR_ERR_BAD_ARG;
-    if ((d->out0.pitch & 7) || (d->out0.coff & 7) || d->out0.coff + 16 > d->out0.pitch) return ESR_ERR_BAD_ARG;
+    if (!esr_view_fits(d->out0, 8, 16)) return ESR_ERR_BAD_ARG;
     const long long hw = (long long)d->h * d->w, npix = hw * d->n;
     const long long want = (npix + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
@@ -1308,15 +1297,15 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     if (d->border_bias && d->out_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;
     if (d->border_bias && ((uintptr_t)d->border_bias & 15)) return ESR_ERR_BAD_ARG;       // (staged by 16-byte LDS-DMA pieces, as the packed weights)
     if (!post && d->post2_wpacked) return ESR_ERR_BAD_ARG;
-    if ((d->in.pitch & 7) || (d->in.coff & 7)) return ESR_ERR_BAD_ARG;                         // 16-byte granules
+    if (!esr_view_aligned(d->in, 8)) return ESR_ERR_BAD_ARG;                                   // 16-byte granules
     const int cin_phys = esr_round_up(d->cin, 16);
     const bool segmented = d->in_seg_stride != 0;
     if (segmented) {
         if (d->in_seg_chunks <= 0 || (cin_phys / 16) % d->in_seg_chunks || d->in_seg_stride < 0 || (d->in_seg_stride & 15)) return ESR_ERR_BAD_ARG;
         // (tight pitch, round 6: a segment's last chunk may run 8 channels into the next pixel, see below)
-        if (d->in.coff + 16 * d->in_seg_chunks - 8 > d->in.pitch) return ESR_ERR_BAD_ARG;
+        if (!esr_view_fits(d->in, 8, 16 * d->in_seg_chunks - 8)) return ESR_ERR_BAD_ARG;
         if (d->ksize != 1) return ESR_ERR_UNSUPPORTED;             // (a 3x3 over a concat does not occur on the path)
-    } else if (d->in.coff + esr_round_up(d->cin, 8) > d->in.pitch) {
+    } else if (!esr_view_fits(d->in, 8, esr_round_up(d->cin, 8))) {
         // TIGHT PITCH (round 6): the pixel holds round_up(cin, 8) channels -- whole 16-byte granules --, not necessarily whole 16-channel K chunks:
         // the last chunk's second half is then the first 16 bytes of the NEXT pixel (zeros behind the image's last one: the buffer range), and
         // meets weight rows that the packer left zero (slots >= cin).  nf = 50 at pitch 56 instead of 64: 12.5 % fewer bytes in every
@@ -1333,7 +1322,7 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
         if (!bf16 || d->ksize != 3 || (post && (hilo != ESR_HILO_OUT || d->post2_wpacked)) || segmented || (d->border_bias && (hilo & ESR_HILO_IN)) || (nt != 3 && nt != 4) || (d->split > 0 && d->split < d->cout)) return ESR_ERR_UNSUPPORTED;
         if (d->hilo_stride <= 0 || (d->hilo_stride & 15)) return ESR_ERR_BAD_ARG;
         if ((hilo & ESR_HILO_RES) && d->res_mode == ESR_RES_NONE) return ESR_ERR_BAD_ARG;
-        if ((hilo & ESR_HILO_RES) && s16_res_is_input(d)) return ESR_ERR_UNSUPPORTED;      // residual == input is added from the staged tile: the low tensor would be dropped
+        if ((hilo & ESR_HILO_RES) && d->ksize == 3 && esr_res_is_input(d, 16)) return ESR_ERR_UNSUPPORTED;      // residual == input is added from the staged tile: the low tensor would be dropped
         if ((hilo & ESR_HILO_OUT) && (shuffle || !d->out0.ptr)) return ESR_ERR_BAD_ARG;
     }
     int split = d->split <= 0 ? cout8 : d->split;
@@ -1345,15 +1334,14 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
         // the conv's own result feeds the post chain only
     } else if (d->out_layout == ESR_NHWC) {
         if (!d->out0.ptr) return ESR_ERR_BAD_ARG;
-        if ((d->out0.pitch & 7) || (d->out0.coff & 7) || d->out0.coff + split > d->out0.pitch) return ESR_ERR_BAD_ARG;
-        if (split < cout8 && (!d->out1.ptr || (d->out1.pitch & 7) || (d->out1.coff & 7) || d->out1.coff + (cout8 - split) > d->out1.pitch))
-            return ESR_ERR_BAD_ARG;
+        if (!esr_view_fits(d->out0, 8, split)) return ESR_ERR_BAD_ARG;
+        if (split < cout8 && !esr_view_ok(d->out1, 8, cout8 - split)) return ESR_ERR_BAD_ARG;
     } else {
         return ESR_ERR_BAD_ARG;
     }
-    if (d->res_mode != ESR_RES_NONE && (!d->res.ptr || (d->res.pitch & 7) || (d->res.coff & 7) || d->res.coff + cout8 > d->res.pitch))
-        return ESR_ERR_BAD_ARG;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;   // per-image raw buffer < 2 GiB
+    if (d->res_mode != ESR_RES_NONE && !esr_view_ok(d->res, 8, cout8)) return ESR_ERR_BAD_ARG;
+    const double px = (double)d->h * d->w;                   // per-image raw buffers < 2 GiB (out-of-range offset 0x80000000)
+    if (!esr_fits_raw(px, d->in.pitch, 2)) return ESR_ERR_UNSUPPORTED;
     const int wchunks = cin_phys / 16;                       // resident weight chunks
     const int nchunks = (hilo & ESR_HILO_IN) ? 2 * wchunks : wchunks;     // input stages per tile
     int ring = RING_MAX;                                     // as many input stages as fit next to the resident weights
@@ -1362,13 +1350,11 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     if (post) {
         const int rc = s16_post_plan(d, nt, nchunks, &pnt1, &pnt2, &post_lo, &ring, &lds);
         if (rc != ESR_OK) return rc;
-        const int p1c8 = esr_round_up(d->post_cout, 8);
-        if (!d->post_out.ptr || (d->post_out.pitch & 7) || (d->post_out.coff & 7) || d->post_out.coff + p1c8 > d->post_out.pitch) return ESR_ERR_BAD_ARG;
-        if ((double)d->h * d->w * d->post_out.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+        if (!esr_view_ok(d->post_out, 8, esr_round_up(d->post_cout, 8))) return ESR_ERR_BAD_ARG;
+        if (!esr_fits_raw(px, d->post_out.pitch, 2)) return ESR_ERR_UNSUPPORTED;
         if (pnt2) {
-            const int p2c8 = esr_round_up(d->post2_cout, 8);
-            if (!d->post2_out.ptr || (d->post2_out.pitch & 7) || (d->post2_out.coff & 7) || d->post2_out.coff + p2c8 > d->post2_out.pitch) return ESR_ERR_BAD_ARG;
-            if ((double)d->h * d->w * d->post2_out.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+            if (!esr_view_ok(d->post2_out, 8, esr_round_up(d->post2_cout, 8))) return ESR_ERR_BAD_ARG;
+            if (!esr_fits_raw(px, d->post2_out.pitch, 2)) return ESR_ERR_UNSUPPORTED;
         }
         if (d->post_act != ESR_ACT_NONE && d->post_act != ESR_ACT_LRELU && d->post_act != ESR_ACT_RELU && d->post_act != ESR_ACT_GELU) return ESR_ERR_UNSUPPORTED;
     } else {
@@ -1378,12 +1364,12 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     }
     if (lds > (size_t)LDS_LIMIT) return ESR_ERR_UNSUPPORTED;                                     // weight set too large to stay resident
     if (!shuffle && d->out0.ptr) {
-        if ((double)d->h * d->w * d->out0.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
-        if (split < cout8 && (double)d->h * d->w * d->out1.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
-    } else if (shuffle && (double)d->cout * d->h * d->w * 4.0 >= 2147483647.0) {
-        return ESR_ERR_UNSUPPORTED;                          // per-image raw buffers < 2 GiB (out-of-range offset 0x80000000)
+        if (!esr_fits_raw(px, d->out0.pitch, 2)) return ESR_ERR_UNSUPPORTED;
+        if (split < cout8 && !esr_fits_raw(px, d->out1.pitch, 2)) return ESR_ERR_UNSUPPORTED;
+    } else if (shuffle && !esr_fits_raw(px, d->cout, 4)) {
+        return ESR_ERR_UNSUPPORTED;                          // (the fp32 planes of one image)
     }
-    if (d->res_mode != ESR_RES_NONE && (double)d->h * d->w * d->res.pitch * 2.0 >= 2147483647.0) return ESR_ERR_UNSUPPORTED;
+    if (d->res_mode != ESR_RES_NONE && !esr_fits_raw(px, d->res.pitch, 2)) return ESR_ERR_UNSUPPORTED;
     const int pairs = (d->ksize * d->ksize + 1) / 2;
 
     S16K k{};
@@ -1403,9 +1389,9 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     k.cout_store = shuffle ? d->cout : cout8;
     k.split = split;
     k.act = d->act;
-    k.slope = d->act == ESR_ACT_LRELU ? d->slope : (d->act == ESR_ACT_RELU ? 0.f : 1.f);
+    k.slope = esr_act_slope(d->act, d->slope);
     k.res_mode = d->res_mode;
-    if (s16_res_is_input(d)) {
+    if (d->ksize == 3 && esr_res_is_input(d, 16)) {
         k.res_in = 1;                               // residual == input: added from the staged tile, no residual loads
         k.res_mode = ESR_RES_NONE;
     }
@@ -1425,7 +1411,7 @@ int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
     k.py1 = static_cast<char*>(d->post_out.ptr); k.py2 = static_cast<char*>(d->post2_out.ptr);
     k.py1_pitch = d->post_out.pitch; k.py1_coff = d->post_out.coff; k.py2_pitch = d->post2_out.pitch; k.py2_coff = d->post2_out.coff;
     k.p1_cout8 = esr_round_up(d->post_cout > 0 ? d->post_cout : 1, 8); k.p2_cout8 = esr_round_up(d->post2_cout > 0 ? d->post2_cout : 1, 8);
-    k.p1_slope = d->post_act == ESR_ACT_LRELU ? d->slope : (d->post_act == ESR_ACT_RELU ? 0.f : 1.f);
+    k.p1_slope = esr_act_slope(d->post_act, d->slope);
     k.p1_gelu = d->post_act == ESR_ACT_GELU;
     k.post_lo = post_lo;
     k.store_main = d->out0.ptr ? 1 : 0;
