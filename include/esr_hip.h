@@ -415,7 +415,8 @@ typedef enum esr_op_kind {
     ESR_OP_PACK_INPUT = 6,      /* esr_pack_input_s16 on esr_op.conv (ABI v5) */
     ESR_OP_ESA_LOWRES = 7,      /* esr_esa_lowres_f32 on esr_op.lo (ABI v7) */
     ESR_OP_CONV_CHAIN = 8,      /* esr_conv_chain_s16 on esr_op.chain (ABI v11) */
-    ESR_OP_MAXPOOL7S7 = 9       /* esr_maxpool7s7_f32 on esr_op.esa (additive within ABI v12) */
+    ESR_OP_MAXPOOL7S7 = 9,      /* esr_maxpool7s7_f32 on esr_op.esa (additive within ABI v12) */
+    ESR_OP_DISTILL_STEP = 10    /* esr_distill_step_s16 on esr_op.chain (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -513,6 +514,33 @@ typedef struct esr_chain_desc {
 int esr_conv_chain_supported(const esr_chain_desc* d);   /* 1: esr_conv_chain_s16 has a kernel for this shape */
 int esr_conv_chain_s16(const esr_chain_desc* d, void* hip_stream);
 
+/*
+ * esr_distill_step_s16 (additive within ABI v12; op kind ESR_OP_DISTILL_STEP on esr_op.chain) -- one distillation step of BMDN's block
+ * (BMDB.forward, models/team37_bmdn.py:154-171) as ONE launch on 16-bit storage (distill_step_kernel, csrc/esr_distill.hip):
+ *     d   = relu(W_d . in + b_d)                              1x1, cin -> cmid, stored (rounded to the storage type) to post_out
+ *     out = relu(W_3 (*) [in | d] + b_3  (+ in))              3x3 over cin + cmid channels -> cout, stored to post2_out
+ * where the 3x3 sees d AS STORED and zero-padded like `in` (a halo pixel outside the image is 0, not relu(b_d)), and W_3 / b_3 are the
+ * fold cat([W_r, W_b], dim 1) / b_r + b_b of the block's two 3x3s c{j}_r (over in) and c{j}_b (over d).  An esr_chain_desc carries it:
+ *     n_layers            2
+ *     in, cin             the step's input r_{j-1} and its logical channels (17..48); channels at and beyond cin are never read
+ *     cmid, cout          17..32 each
+ *     act                 ESR_ACT_RELU (both layers)
+ *     res_mode            ESR_RES_NONE | ESR_RES_PRE_ACT (+ in before the activation; cin == cout)
+ *     storage, compute    ESR_STORE_BF16 / ESR_COMPUTE_BF16 or ESR_STORE_F16 / ESR_COMPUTE_F16
+ *     wpacked[0]          esr_pack_conv_s16(W_d, b_d, ksize 1) with cin_phys = round_up(cin, 16)
+ *     wpacked[1]          esr_pack_conv_s16(W_3, b_3, ksize 3) over cin_phys = round_up(cin, 16) + round_up(cmid, 16) physical slots through a
+ *                         cin_map: slot s < cin -> channel s of `in`, slot round_up(cin, 16) + j (j < cmid) -> channel j of d (logical input
+ *                         cin + j), every other slot -1 (zero rows) -- the K order is [in chunks | d chunks] inside every tap pair
+ *     post_out, post_cout     d and its stored channels (cmid <= post_cout <= round_up(cmid, 16); round_up(post_cout, 8) channels are written,
+ *                             the pad ones as zeros -- what esr_conv2d_f32 writes to an out0 of that width)
+ *     post2_out, post2_cout   out, likewise
+ *     post_wpacked, post2_wpacked   NULL
+ * esr_distill_step_supported: 1 when the descriptor's shape has a kernel; esr_distill_step_s16 returns ESR_ERR_UNSUPPORTED for every other
+ * (fp32 storage included) and ESR_ERR_BAD_ARG for a null pointer or a view that is misaligned or does not hold its channels.
+ */
+int esr_distill_step_supported(const esr_chain_desc* d);
+int esr_distill_step_s16(const esr_chain_desc* d, void* hip_stream);
+
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
@@ -520,7 +548,7 @@ typedef struct esr_op {
     esr_esa_desc esa;           /* the four ESA kinds */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */
-    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11) */
+    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP */
 } esr_op;
 
 /* ABI v5 -- the network input for the 16-bit plans: NCHW fp32 [n, cin <= 4, h, w] (d->in.ptr) -> NHWC 16-bit (d->out0, pitch >= 16,

@@ -6,6 +6,7 @@ Package contents (only what the path needs):
   engine.py    weight packing, workspace, op-list replay
   imdn.py ...  drop-in nn.Modules with the reference's ctor / state_dict surface
 """
+from .bmdn import BMDN  # noqa: F401
 from .bsrn import BSRN  # noqa: F401
 from .efdn import PLAINRFDN  # noqa: F401
 from .fmen import FMEN  # noqa: F401
@@ -13,4 +14,4 @@ from .imdn import IMDN  # noqa: F401
 from .rfdn import RFDN  # noqa: F401
 from .rlfn import RLFN_cut  # noqa: F401
 
-__all__ = ["BSRN", "FMEN", "IMDN", "PLAINRFDN", "RFDN", "RLFN_cut"]
+__all__ = ["BMDN", "BSRN", "FMEN", "IMDN", "PLAINRFDN", "RFDN", "RLFN_cut"]

@@ -1195,6 +1195,7 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_ESA_LOWRES: return esr_esa_lowres_f32(&op.lo, hip_stream);
         case ESR_OP_CONV_CHAIN: return esr_conv_chain_s16(&op.chain, hip_stream);
         case ESR_OP_MAXPOOL7S7: return esr_maxpool7s7_f32(&op.esa, hip_stream);
+        case ESR_OP_DISTILL_STEP: return esr_distill_step_s16(&op.chain, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

@@ -158,6 +158,25 @@ def pack_tail_s16(weight, bias, nseg, seg_c, mid_c, compute):
     return out
 
 
+def distill_cin_map(cin, cmid):
+    """physical K slot -> logical input channel of a distillation step's folded 3x3 (esr_distill_step_s16, wpacked[1]): the chunks of `in`
+    (slot s < cin: channel s), then the chunks of d (slot round_up(cin, 16) + j, j < cmid: logical channel cin + j); -1 = a zero pad row"""
+    ci, cm = (cin + 15) // 16 * 16, (cmid + 15) // 16 * 16
+    return [s if s < cin else -1 for s in range(ci)] + [cin + j if j < cmid else -1 for j in range(cm)]
+
+
+def pack_distill_s16(w_r, b_r, w_b, b_b, compute):
+    """The two 3x3s of a BMDB distillation step, c_r over r [cout, cin, 3, 3] and c_b over d [cout, cmid, 3, 3] (team37_bmdn.py:157-159), folded
+    in fp32 into ONE 3x3 over cat[r, d] -- weights cat([W_r, W_b], 1), bias b_r + b_b -- and packed as an esr_pack_conv_s16 image whose K order
+    is [in chunks | d chunks] inside every tap pair (distill_cin_map; pad rows zero): esr_distill_step_s16's wpacked[1]."""
+    w_r, w_b = w_r.detach().to("cpu", torch.float32), w_b.detach().to("cpu", torch.float32)
+    if w_r.dim() != 4 or w_b.dim() != 4 or w_r.shape[0] != w_b.shape[0] or tuple(w_r.shape[2:]) != (3, 3) or tuple(w_b.shape[2:]) != (3, 3):
+        raise L.EsrError("pack_distill_s16: two 3x3 weights with the same output channels")
+    zero = torch.zeros(w_r.shape[0])
+    b = (zero if b_r is None else b_r.detach().to("cpu", torch.float32)) + (zero if b_b is None else b_b.detach().to("cpu", torch.float32))
+    return pack_conv_s16(torch.cat([w_r, w_b], dim=1), b, compute, cin_map=distill_cin_map(w_r.shape[1], w_b.shape[1]))
+
+
 def pack_apply_post(w0, b0, w1, b1, store):
     """Weights of the 1x1 chain riding in esr_esa_apply_f32's launch (esr_esa_desc.post_w): w0 [cout0, cin(, 1, 1)] applied to the
     apply result, w1 [cout1, cout0(, 1, 1)] (or None) applied to w0's result -> esr_pack_apply_post blob."""
@@ -325,6 +344,7 @@ POST = "#post"     # esr_pack_post_s16 image of a 1x1 in a 16-bit conv's epilogu
 HEAD = "#head"     # a 16-bit plan's head conv reads `<path>#head#s16` (pack_head_s16; Plan.conv)
 DENSE = "#dense"   # esr_pack_dense_f32 blob of a layer of the fused ESA branch (EsaLayer)
 WINO = "#wino"     # esr_pack_wino_f32 blob of an fp32 3x3 (Winograd F(2x2, 3x3))
+FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
 def _cost(name, kernel, cin, cout, k, flops, rd, wr, stored=None, fexec=None):
@@ -868,6 +888,44 @@ class Chain(_Op):
 
 
 @dataclass
+class Distill(_Op):
+    """A BMDB distillation step as ONE esr_distill_step_s16 op -- see Plan.distill_step (distill_step_kernel).  replaces: the three Conv ops it
+    stands for, [c_d, c_b, c_r] (weights, complexity counters, algorithmic costs)."""
+    replaces: list
+    kind = "distill"
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        cd, cb, cr = self.replaces
+        op.kind = L.OP_DISTILL_STEP
+        d = op.chain
+        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 2
+        d.cin, d.cmid, d.cout = cd.cin, cd.cout, cr.cout
+        d.act, d.slope, d.res_mode = L.ACT_RELU, 0.0, (L.RES_PRE_ACT if cb.res is not None else L.RES_NONE)
+        d.storage = d.compute = st
+        d.inp = _view(cd.src, base)
+        d.wpacked[0] = weights[cd.w + S16].data_ptr()
+        d.wpacked[1] = weights[cr.w + FOLD].data_ptr()
+        full = lambda dst, c: min((c + 15) // 16 * 16, dst.pitch) if isinstance(dst, Buffer) else c      # (whole dense buffer: pad channels too)
+        d.post_out, d.post_cout = _view(cd.dst, base), full(cd.dst, cd.cout)
+        d.post2_out, d.post2_cout = _view(cr.dst, base), full(cr.dst, cr.cout)
+        if not L.lib().esr_distill_step_supported(ctypes.byref(d)):
+            raise L.EsrError(f"{cd.w}: no distillation step kernel for this shape (the plan should have kept separate ops)")
+
+    def cost(self, plan, desc):             # the step's input read once, d and the result written once
+        cd, cb, cr = self.replaces
+        npix, es = plan.npix, plan.esize
+        flops = sum(2.0 * npix * so.cin_alg * so.cout * so.k * so.k for so in self.replaces)
+        wb = 4.0 * sum(so.cin_alg * so.cout * so.k * so.k for so in self.replaces)
+        kern = f"distill_step_kernel<{'true' if plan.store == 'bf16' else 'false'}, {(cd.cin + 15) // 16}, {'true' if cb.res is not None else 'false'}>"
+        stored = float(npix * es * (_stored_channels(cd.src, cd.cin, 16) + _stored_channels(cd.dst, cd.cout, 16) + _stored_channels(cr.dst, cr.cout, 16))) + wb
+        return _cost(cd.w, kern, cd.cin, cr.cout, 3, flops, float(npix * cd.cin_alg * es) + wb, float(npix * es * (cd.cout + cr.cout)), stored)
+
+    def counted_convs(self, plan):
+        return [c for o in self.replaces for c in o.counted_convs(plan)]
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1039,6 +1097,21 @@ class Plan:
         del self.ops[mark:]
         self.ops.append(Chain(sub, gate=True))
 
+    def distill_step(self, mark):
+        """The three convolutions appended since `mark = len(plan.ops)` -- a BMDB distillation step in its per-op form, d = relu(c_d(r)),
+        t = c_b(d) (+ r), r' = relu(c_r(r) + t) (team37_bmdn.py:155-171) -- as ONE esr_distill_step_s16 op (16-bit plans): r is read once, d
+        and r' are written once, t never exists (the two 3x3s are one over cat[r, d]: engine.pack_distill_s16, blob `<c_r>#fold`).  The Conv
+        ops stay attached as `replaces`: weights, complexity counters and algorithmic costs are theirs.  Not bit-identical to them: the per-op
+        form rounds t to the storage type."""
+        sub = self.ops[mark:]
+        assert self.esize == 2 and len(sub) == 3 and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub)
+        cd, cb, cr = sub
+        assert cd.k == 1 and cb.k == 3 and cr.k == 3 and cd.act == cr.act == L.ACT_RELU and cb.act == L.ACT_NONE and cd.res is None
+        assert _same_view(cb.src, cd.dst) and _same_view(cr.src, cd.src) and _same_view(cr.res, cb.dst) and cr.res_mode == L.RES_PRE_ACT
+        assert cb.res is None or (_same_view(cb.res, cd.src) and cb.res_mode == L.RES_PRE_ACT)
+        del self.ops[mark:]
+        self.ops.append(Distill(sub))
+
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [Post(w, dst, cout, act, slope, res), ...] -- one or two 1x1 convolutions evaluated in the same launch
@@ -1163,6 +1236,7 @@ class HipSRModel(nn.Module):
         self._fuse_tail = True     # 16-bit RFDN plans: RFDB's c4 -> cat -> c5 -> esa.conv1 as one launch (rfdb_tail_kernel, ABI v12)
         self._tight_pitch = True   # 16-bit RFDN plans: nf-wide tensors at pitch round_up(nf, 8) instead of whole K chunks (56 for nf = 50; esr_conv2d_s16: tight pitch)
         self._fuse_chain = True    # 16-bit plans: a block's 3x3 chain as one esr_conv_chain_s16 launch where a kernel exists (Plan.chain)
+        self._fuse_step = True     # 16-bit BMDN plans: a distillation step as one esr_distill_step_s16 launch (Plan.distill_step); measured: DESIGN.md 7d
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
         self._prof_passes = 0      # >0: record HIP events around every op (bench roofline leg)
@@ -1221,6 +1295,7 @@ class HipSRModel(nn.Module):
     fuse_chain = property(lambda self: self._fuse_chain, lambda self, v: self._set_flag("_fuse_chain", v))
     fuse_tail = property(lambda self: self._fuse_tail, lambda self, v: self._set_flag("_fuse_tail", v))
     tight_pitch = property(lambda self: self._tight_pitch, lambda self, v: self._set_flag("_tight_pitch", v))
+    fuse_step = property(lambda self: self._fuse_step, lambda self, v: self._set_flag("_fuse_step", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels
@@ -1336,7 +1411,7 @@ class HipSRModel(nn.Module):
                 continue
             if o.kind == "bs":                              # BSConvU: pointwise + distillation 1x1 weights as hi + lo blobs
                 s16.update([o.pw] + ([o.distill.w] if o.distill is not None else []))
-            for c in o.replaces if o.kind == "chain" else [o] if o.kind == "conv" else []:
+            for c in o.replaces if o.kind in ("chain", "distill") else [o] if o.kind == "conv" else []:
                 if c.s16(plan) and c.head:
                     head.add(c.w[:-len(HEAD)])
                 elif c.s16(plan):

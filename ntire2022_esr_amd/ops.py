@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .engine import pack_conv, pack_conv_s16, pack_post_s16, pack_wino
+from .engine import pack_conv, pack_conv_s16, pack_distill_s16, pack_post_s16, pack_wino
 
 
 def _view(t, coff=0):
@@ -315,6 +315,44 @@ def _hfab(x, weights, biases, *, act, slope, cin, out):
     stream = torch.cuda.current_stream(x.device).cuda_stream
     _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, stream, L.OP_CONV_CHAIN, "chain")
     return y
+
+
+def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_coff=0, d_out=None, d_coff=0, d_channels=None,
+                 out=None, out_coff=0, out_channels=None):
+    """esr_distill_step_s16: one distillation step of BMDN's block (team37_bmdn.py:155-171) in ONE launch on a 16-bit NHWC tensor x
+    [N, H, W, P]: d = relu(w_d . x + b_d) (1x1), y = relu(conv3x3(x, w_r, b_r) + conv3x3(d, w_b, b_b) (+ x if res)) with d as stored and
+    zero-padded.  Returns (d, y).  `cin` channels of x from `in_coff` are read (default: w_d's inputs).
+    d_out / out: caller-provided NHWC tensors of x's dtype and device (pitch a multiple of 8) that receive d / y from channel d_coff /
+    out_coff; default: freshly allocated zeros of pitch round_up(channels, 8).  d_channels / out_channels: esr_chain_desc.post_cout /
+    post2_cout, the stored widths (default: the logical ones; up to round_up(.., 16): the pad channels are written as zeros)."""
+    if not x.is_cuda:
+        raise L.EsrError("distill_step: tensors must live on the GPU; there is no CPU fallback")
+    st = _STORE_OF[x.dtype]
+    if st == "f32":
+        raise L.EsrError("distill_step: 16-bit storage only")
+    lib = L.lib()
+    n, h, w, _ = x.shape
+    w1 = w_d if w_d.dim() == 4 else w_d[:, :, None, None]
+    d = L.ChainDesc()
+    d.n, d.h, d.w, d.n_layers = n, h, w, 2
+    d.cin = w1.shape[1] if cin is None else cin
+    d.cmid, d.cout = w1.shape[0], w_r.shape[0]
+    d.act, d.res_mode = L.ACT_RELU, (L.RES_PRE_ACT if res else L.RES_NONE)
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x, in_coff)
+    keep = [pack_conv_s16(w1, b_d, st, cin_phys=(w1.shape[1] + 15) // 16 * 16).to(x.device), pack_distill_s16(w_r, b_r, w_b, b_b, st).to(x.device)]
+    d.wpacked[0], d.wpacked[1] = keep[0].data_ptr(), keep[1].data_ptr()
+    d.post_cout = d.cmid if d_channels is None else d_channels
+    d.post2_cout = d.cout if out_channels is None else out_channels
+    dc8, oc8 = (d.post_cout + 7) // 8 * 8, (d.post2_cout + 7) // 8 * 8
+    dd = torch.zeros((n, h, w, dc8), dtype=x.dtype, device=x.device) if d_out is None else _provided(d_out, "distill_step: d_out", x, (n, h, w), dc8, 8)
+    y = torch.zeros((n, h, w, oc8), dtype=x.dtype, device=x.device) if out is None else _provided(out, "distill_step: out", x, (n, h, w), oc8, 8)
+    d.post_out, d.post2_out = _view(dd, d_coff), _view(y, out_coff)
+    if not lib.esr_distill_step_supported(ctypes.byref(d)):
+        raise L.EsrError("distill_step: no kernel for this shape (esr_distill_step_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_distill_step_s16", "esr_distill_step_s16", d, stream, L.OP_DISTILL_STEP, "chain")
+    return dd, y
 
 
 def _hilo_pair(t, what, strides):

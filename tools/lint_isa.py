@@ -12,7 +12,8 @@ Rule 3 -- prologues and wait states (round 5, LAB_NOTES.md 10.8): hipcc keeps ON
     16-byte patch load in front of the first LDS store of the patch; conv48r / conv48rq_kernel with the GELU compiled in -- < 160 s_nop (510).
 Rule 4 -- conv64m_kernel, rfdb_tail_kernel (esr_c64m.hip), rlfb_chain_kernel (esr_chain.hip) and hfab_kernel (esr_hfab.hip): no scratch access, no dynamic register
     indexing -- their s_waitcnt vmcnt(N) count every vector-memory instruction, and the DMA pieces leave m0 changed.  The same for esa_pool7_kernel and
-    esa_pool7_branch_kernel (esr_esa_pool7.hip): the 36 weight fragments must stay in registers (indexed by unrolled taps), not spill.
+    esa_pool7_branch_kernel (esr_esa_pool7.hip): the 36 weight fragments must stay in registers (indexed by unrolled taps), not spill.  And for
+    distill_step_kernel (esr_distill.hip): the 3x3's 40 / 50 weight fragments live in registers for the block's lifetime, next to an LDS-DMA stage.
 Rule 5 -- rlfb_chain_kernel: the post wave's counted wait (PIECES + STORES) (D - 2) + STORES is in the code, and between two barriers
     of the step loop there are exactly PIECES LDS-DMA loads and exactly STORES stores (ChGeo<G>): an extra vector-memory instruction would loosen it.
 Rule 2 -- conv_s16_kernel's wait-count arithmetic (tools/lint_s16_isa.py, unchanged): no scratch / spills, no copies out of registers an
@@ -113,7 +114,8 @@ def lint_prologues(path, unit):
         # must not spill (a scratch access is a VMEM instruction the count does not know) and must not index registers dynamically (the only
         # sequences in which hipcc keeps a value of its own in m0)
         if (unit == "esr_c64m.hip" and ("conv64m_kernel" in name or "rfdb_tail_kernel" in name)) or (unit == "esr_chain.hip" and "rlfb_chain_kernel" in name) or \
-                (unit == "esr_hfab.hip" and "hfab_kernel" in name) or (unit == "esr_esa_pool7.hip" and "esa_pool7_" in name):
+                (unit == "esr_hfab.hip" and "hfab_kernel" in name) or (unit == "esr_esa_pool7.hip" and "esa_pool7_" in name) or \
+                (unit == "esr_distill.hip" and "distill_step_kernel" in name):
             bad = [t for t in ins if t.startswith(("scratch_", "s_set_gpr_idx", "s_movrel", "v_movrel"))]
             if bad:
                 problems.append(f"{unit}: {name}: {len(bad)} scratch / dynamic register index instruction(s), first: {bad[0]}")
