@@ -416,7 +416,8 @@ typedef enum esr_op_kind {
     ESR_OP_ESA_LOWRES = 7,      /* esr_esa_lowres_f32 on esr_op.lo (ABI v7) */
     ESR_OP_CONV_CHAIN = 8,      /* esr_conv_chain_s16 on esr_op.chain (ABI v11) */
     ESR_OP_MAXPOOL7S7 = 9,      /* esr_maxpool7s7_f32 on esr_op.esa (additive within ABI v12) */
-    ESR_OP_DISTILL_STEP = 10    /* esr_distill_step_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_DISTILL_STEP = 10,   /* esr_distill_step_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_RESBLOCK_HEAD = 11   /* esr_resblock_head_s16 on esr_op.conv (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -541,10 +542,36 @@ int esr_conv_chain_s16(const esr_chain_desc* d, void* hip_stream);
 int esr_distill_step_supported(const esr_chain_desc* d);
 int esr_distill_step_s16(const esr_chain_desc* d, void* hip_stream);
 
+/*
+ * esr_resblock_head_s16 (additive within ABI v12; op kind ESR_OP_RESBLOCK_HEAD on esr_op.conv) -- the head of ESAN's residual block
+ * (ResidualBlock_ESA.forward, models/team34_esan.py:71-76, and ESA.conv1, :49) as ONE launch on 16-bit storage at 32 channels
+ * (resblock_head_kernel, csrc/esr_esan.hip):
+ *     x  = in + res                       the previous block's `identity + ESA(..)`; stored to out0 (res_mode ESR_RES_PRE_ACT)
+ *     x  = in                             the first block of the trunk (res_mode ESR_RES_NONE: res and out0 are not used, nothing is stored for x)
+ *     t  = relu(W1 (*) x + b1)            3x3, never stored
+ *     u  = W2 (*) t + b2                  3x3, stored to out1
+ *     c1 = Wc . u + bc                    1x1 on u AS STORED, post_cout (<= ESR_ESA_FP) outputs, stored to post_out (the pitch-16 ESA map)
+ * Every value is rounded once to the storage type, exactly where the separate launches store it (an identity 1x1 with the residual, two
+ * esr_conv2d_f32 3x3s and the 1x1), and the second 3x3 sees t zero-padded like a stored tensor (a halo pixel outside the image is 0, not
+ * relu(b1)).  An esr_conv_desc carries it, no field added:
+ *     cin, cout, ksize     32, 32, 3;  in_layout, out_layout ESR_NHWC;  act ESR_ACT_RELU (of the first 3x3)
+ *     in, res, out0, out1  xin, g, x, u: 32 channels each from coff; out0 must not be `in` or `res` (neighbouring tiles read their halo)
+ *     wpacked              esr_pack_conv_s16(W1, b1, ksize 3, cin_phys 32)
+ *     tail_wpacked         esr_pack_conv_s16(W2, b2, ksize 3, cin_phys 32)      (tail_cat / tail_cat_c stay zero)
+ *     post_wpacked         esr_pack_conv_s16(Wc, bc, ksize 1, cin_phys 32)
+ *     post_out, post_cout  c1 and its stored channels (round_up(post_cout, 8) channels are written: ESA width 8 in a pitch-16 map with
+ *                          post_cout = 16 writes the pad channels as zeros, as esr_conv2d_f32 does for an out0 of that width); post_act none
+ * esr_resblock_head_supported: 1 when the descriptor's shape has a kernel; esr_resblock_head_s16 returns ESR_ERR_UNSUPPORTED for every other
+ * (fp32 storage, channels other than 32, post_cout > 16, a per-image tensor of 1 GiB or more) and ESR_ERR_BAD_ARG for a null pointer or a
+ * view that is misaligned or does not hold its channels.
+ */
+int esr_resblock_head_supported(const esr_conv_desc* d);
+int esr_resblock_head_s16(const esr_conv_desc* d, void* hip_stream);
+
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
-    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV */
+    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD */
     esr_esa_desc esa;           /* the four ESA kinds */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */

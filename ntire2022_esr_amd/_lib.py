@@ -22,6 +22,7 @@ HILO_IN, HILO_RES, HILO_OUT = 1, 2, 4                                     # esr_
 OP_CONV, OP_CONV3X3S2, OP_MAXPOOL7S3, OP_ESA_APPLY, OP_DWCONV, OP_BSCONV, OP_PACK_INPUT, OP_ESA_LOWRES, OP_CONV_CHAIN = 0, 1, 2, 3, 4, 5, 6, 7, 8
 OP_MAXPOOL7S7 = 9                                                         # EFDN's ESA pooling (esr_maxpool7s7_f32)
 OP_DISTILL_STEP = 10                                                      # BMDN's distillation step (esr_distill_step_s16 on Op.chain)
+OP_RESBLOCK_HEAD = 11                                                     # ESAN's residual-block head (esr_resblock_head_s16 on Op.conv)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -143,6 +144,7 @@ EXPORTS = [
     "esr_tensor2uint_u8", "esr_sqerr_u8", "esr_channel_attention_f32",
     "esr_tensor2uint_u8_chk", "esr_ssim_partials", "esr_ssim_u8",
     "esr_conv_chain_supported", "esr_conv_chain_s16", "esr_distill_step_supported", "esr_distill_step_s16",
+    "esr_resblock_head_supported", "esr_resblock_head_s16",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -259,6 +261,10 @@ def lib():
     L.esr_distill_step_supported.restype = ci
     L.esr_distill_step_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
     L.esr_distill_step_s16.restype = ci
+    L.esr_resblock_head_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_resblock_head_supported.restype = ci
+    L.esr_resblock_head_s16.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_resblock_head_s16.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

@@ -1196,6 +1196,7 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_CONV_CHAIN: return esr_conv_chain_s16(&op.chain, hip_stream);
         case ESR_OP_MAXPOOL7S7: return esr_maxpool7s7_f32(&op.esa, hip_stream);
         case ESR_OP_DISTILL_STEP: return esr_distill_step_s16(&op.chain, hip_stream);
+        case ESR_OP_RESBLOCK_HEAD: return esr_resblock_head_s16(&op.conv, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

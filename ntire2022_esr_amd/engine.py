@@ -926,6 +926,56 @@ class Distill(_Op):
 
 
 @dataclass
+class ResHead(_Op):
+    """The head of ESAN's residual block as ONE esr_resblock_head_s16 op -- see Plan.resblock_head (resblock_head_kernel).  replaces: the Conv ops
+    it stands for, [add,] conv1, conv2, ESA.conv1 (weights, complexity counters, algorithmic costs); the first block of the trunk has no add."""
+    replaces: list
+    kind = "reshead"
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        add = self.replaces[0] if len(self.replaces) == 4 else None
+        c1, c2, ce = self.replaces[-3:]
+        op.kind = L.OP_RESBLOCK_HEAD
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        d.cin, d.cout, d.ksize = c1.cin, c2.cout, 3
+        d.in_layout = d.out_layout = L.NHWC
+        d.act, d.slope = L.ACT_RELU, 0.0
+        d.storage = d.compute = st
+        if add is not None:                                   # x = xin + g: the add's residual is the block input, its source the ESA result
+            d.res_mode = L.RES_PRE_ACT
+            d.inp, d.res, d.out0 = _view(add.res, base), _view(add.src, base), _view(add.dst, base)
+        else:
+            d.res_mode = L.RES_NONE
+            d.inp = _view(c1.src, base)
+        d.out1 = _view(c2.dst, base)
+        d.wpacked = ctypes.c_void_p(weights[c1.w + S16].data_ptr())
+        d.tail_wpacked = ctypes.c_void_p(weights[c2.w + S16].data_ptr())
+        d.post_wpacked = ctypes.c_void_p(weights[ce.w + S16].data_ptr())
+        d.post_out = _view(ce.dst, base)
+        d.post_cout = min((ce.cout + 15) // 16 * 16, ce.dst.pitch) if isinstance(ce.dst, Buffer) else ce.cout   # (whole dense buffer: pad channels too)
+        if not L.lib().esr_resblock_head_supported(ctypes.byref(d)):
+            raise L.EsrError(f"{c1.w}: no residual-block head kernel for this shape (the plan should have kept separate ops)")
+
+    def cost(self, plan, desc):             # xin (and g) read once; x, u and c1 written once
+        add = len(self.replaces) == 4
+        c1, c2, ce = self.replaces[-3:]
+        npix, es = plan.npix, plan.esize
+        convs = (c1, c2, ce)
+        flops = sum(2.0 * npix * so.cin_alg * so.cout * so.k * so.k for so in convs)
+        wb = 4.0 * sum(so.cin_alg * so.cout * so.k * so.k for so in convs)
+        kern = f"resblock_head_kernel<{'true' if plan.store == 'bf16' else 'false'}, {'true' if add else 'false'}>"
+        rd = float(npix * es * c1.cin * (2 if add else 1)) + wb
+        wr = float(npix * es * ((c1.cin if add else 0) + c2.cout + ce.cout))
+        stored = float(npix * es * (c1.cin * (3 if add else 1) + c2.cout + _stored_channels(ce.dst, ce.cout, 16))) + wb
+        return _cost(c1.w, kern, c1.cin, c2.cout, 3, flops, rd, wr, stored)
+
+    def counted_convs(self, plan):
+        return [c for o in self.replaces for c in o.counted_convs(plan)]
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1112,6 +1162,24 @@ class Plan:
         del self.ops[mark:]
         self.ops.append(Distill(sub))
 
+    def resblock_head(self, mark):
+        """The convolutions appended since `mark = len(plan.ops)` -- the head of ESAN's residual block in its per-op form, [x = xin + g as an
+        identity 1x1 with the residual xin,] t = relu(conv1(x)), u = conv2(t), c1 = ESA.conv1(u) (team34_esan.py:71-76, :49) -- as ONE
+        esr_resblock_head_s16 op (16-bit plans): xin and g are read once, x, u and c1 written once, t never exists.  The Conv ops stay
+        attached as `replaces`: weights, complexity counters and algorithmic costs are theirs.  x must not be stored over xin or g: the
+        neighbouring tiles read their halo."""
+        sub = self.ops[mark:]
+        assert self.esize == 2 and len(sub) in (3, 4) and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub)
+        c1, c2, ce = sub[-3:]
+        assert c1.k == 3 and c2.k == 3 and ce.k == 1 and c1.act == L.ACT_RELU and c2.act == ce.act == L.ACT_NONE
+        assert c1.res is None and c2.res is None and ce.res is None and _same_view(c2.src, c1.dst) and _same_view(ce.src, c2.dst)
+        if len(sub) == 4:
+            add = sub[0]
+            assert add.k == 1 and not add.counted and add.act == L.ACT_NONE and add.res_mode == L.RES_PRE_ACT and _same_view(c1.src, add.dst)
+            assert not _same_view(add.dst, add.res) and not _same_view(add.dst, add.src)
+        del self.ops[mark:]
+        self.ops.append(ResHead(sub))
+
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [Post(w, dst, cout, act, slope, res), ...] -- one or two 1x1 convolutions evaluated in the same launch
@@ -1237,6 +1305,7 @@ class HipSRModel(nn.Module):
         self._tight_pitch = True   # 16-bit RFDN plans: nf-wide tensors at pitch round_up(nf, 8) instead of whole K chunks (56 for nf = 50; esr_conv2d_s16: tight pitch)
         self._fuse_chain = True    # 16-bit plans: a block's 3x3 chain as one esr_conv_chain_s16 launch where a kernel exists (Plan.chain)
         self._fuse_step = True     # 16-bit BMDN plans: a distillation step as one esr_distill_step_s16 launch (Plan.distill_step); measured: DESIGN.md 7d
+        self._fuse_head = True     # 16-bit ESAN plans: a residual block's head as one esr_resblock_head_s16 launch (Plan.resblock_head); measured: DESIGN.md 7e
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
         self._prof_passes = 0      # >0: record HIP events around every op (bench roofline leg)
@@ -1296,6 +1365,7 @@ class HipSRModel(nn.Module):
     fuse_tail = property(lambda self: self._fuse_tail, lambda self, v: self._set_flag("_fuse_tail", v))
     tight_pitch = property(lambda self: self._tight_pitch, lambda self, v: self._set_flag("_tight_pitch", v))
     fuse_step = property(lambda self: self._fuse_step, lambda self, v: self._set_flag("_fuse_step", v))
+    fuse_head = property(lambda self: self._fuse_head, lambda self, v: self._set_flag("_fuse_head", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels
@@ -1411,7 +1481,7 @@ class HipSRModel(nn.Module):
                 continue
             if o.kind == "bs":                              # BSConvU: pointwise + distillation 1x1 weights as hi + lo blobs
                 s16.update([o.pw] + ([o.distill.w] if o.distill is not None else []))
-            for c in o.replaces if o.kind in ("chain", "distill") else [o] if o.kind == "conv" else []:
+            for c in o.replaces if o.kind in ("chain", "distill", "reshead") else [o] if o.kind == "conv" else []:
                 if c.s16(plan) and c.head:
                     head.add(c.w[:-len(HEAD)])
                 elif c.s16(plan):

@@ -355,6 +355,49 @@ def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_cof
     return dd, y
 
 
+def resblock_head(x, w1, b1, w2, b2, wc, bc, *, g=None, in_coff=0, g_coff=0, x_out=None, x_coff=0, u_out=None, u_coff=0,
+                  c1_out=None, c1_coff=0, c1_channels=None):
+    """esr_resblock_head_s16: the head of ESAN's residual block (team34_esan.py:71-76, :49) in ONE launch on 16-bit NHWC tensors of 32
+    channels: xs = x + g (g given; else xs = x and nothing is stored for it), t = relu(conv3x3(xs, w1, b1)), u = conv3x3(t, w2, b2) with t
+    as rounded and zero-padded, c1 = wc . u + bc on u as stored.  Returns (xs or None, u, c1).
+    x_out / u_out / c1_out: caller-provided NHWC tensors of x's dtype and device (pitch a multiple of 8) that receive xs / u / c1 from channel
+    x_coff / u_coff / c1_coff; default: freshly allocated zeros (c1: pitch 16, the ESA map).  c1_channels: esr_conv_desc.post_cout, the
+    stored width (default: the logical one; round_up(.., 8) channels are written, the pad ones as zeros)."""
+    if not x.is_cuda:
+        raise L.EsrError("resblock_head: tensors must live on the GPU; there is no CPU fallback")
+    st = _STORE_OF[x.dtype]
+    if st == "f32":
+        raise L.EsrError("resblock_head: 16-bit storage only")
+    lib = L.lib()
+    n, h, w, _ = x.shape
+    wc4 = wc if wc.dim() == 4 else wc[:, :, None, None]
+    c, f = w1.shape[1], wc4.shape[0]
+    d = L.ConvDesc()
+    d.n, d.h, d.w = n, h, w
+    d.cin, d.cout, d.ksize = c, w2.shape[0], 3
+    d.in_layout = d.out_layout = L.NHWC
+    d.act, d.res_mode = L.ACT_RELU, (L.RES_NONE if g is None else L.RES_PRE_ACT)
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x, in_coff)
+    keep = [pack_conv_s16(w1, b1, st).to(x.device), pack_conv_s16(w2, b2, st).to(x.device), pack_conv_s16(wc4, bc, st).to(x.device)]
+    d.wpacked, d.tail_wpacked, d.post_wpacked = (ctypes.c_void_p(k.data_ptr()) for k in keep)
+    xs = None
+    if g is not None:
+        d.res = _view(g, g_coff)
+        xs = torch.zeros((n, h, w, c), dtype=x.dtype, device=x.device) if x_out is None else _provided(x_out, "resblock_head: x_out", x, (n, h, w), c, 8)
+        d.out0 = _view(xs, x_coff)
+    u = torch.zeros((n, h, w, c), dtype=x.dtype, device=x.device) if u_out is None else _provided(u_out, "resblock_head: u_out", x, (n, h, w), c, 8)
+    d.post_cout = f if c1_channels is None else c1_channels
+    c8 = (d.post_cout + 7) // 8 * 8
+    c1 = torch.zeros((n, h, w, L.ESA_FP), dtype=x.dtype, device=x.device) if c1_out is None else _provided(c1_out, "resblock_head: c1_out", x, (n, h, w), c8, 8)
+    d.out1, d.post_out = _view(u, u_coff), _view(c1, c1_coff)
+    if not lib.esr_resblock_head_supported(ctypes.byref(d)):
+        raise L.EsrError("resblock_head: no kernel for this shape (esr_resblock_head_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_resblock_head_s16", "esr_resblock_head_s16", d, stream, L.OP_RESBLOCK_HEAD, "conv")
+    return xs, u, c1
+
+
 def _hilo_pair(t, what, strides):
     """checks a hi + lo pair [2, N, H, W, P] (bf16, P a multiple of 16) and records the byte stride between its halves"""
     if t.dtype != torch.bfloat16 or t.shape[-1] % 16:
