@@ -344,6 +344,7 @@ POST = "#post"     # esr_pack_post_s16 image of a 1x1 in a 16-bit conv's epilogu
 HEAD = "#head"     # a 16-bit plan's head conv reads `<path>#head#s16` (pack_head_s16; Plan.conv)
 DENSE = "#dense"   # esr_pack_dense_f32 blob of a layer of the fused ESA branch (EsaLayer)
 WINO = "#wino"     # esr_pack_wino_f32 blob of an fp32 3x3 (Winograd F(2x2, 3x3))
+DWPAD = "#pad16"   # pack_dw image of a depthwise 3x3 of fewer than 16 channels, zero-padded to 16 (Dw: low-resolution maps stored whole)
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -491,8 +492,12 @@ class Conv(_Op):
         def full_width(dst, cout):
             """16-bit storage, destination = a WHOLE dense buffer: store the pad channels of its last K chunk too (they are
             zeros: zero weight rows, zero bias) -- a 24-of-32-channel store leaves every 64-byte run partial, and partial-line
-            stores cost up to 2.3x a full one (tools/dbg/s16_1x1_probe.py).  Slices of shared buffers keep their width."""
-            if st and not lowres and isinstance(dst, Buffer):
+            stores cost up to 2.3x a full one (tools/dbg/s16_1x1_probe.py).  Slices of shared buffers keep their width.
+            A low-resolution fp32 map that is a whole dense buffer likewise, in every storage type, for another reason: the fp16 ESA apply
+            kernel rounds s = bilinear(c3) + conv_f(c1) of all 16 slots to fp16 before conv4's zero weight rows meet it, so a stale fp32
+            value beyond 65504 in a pad slot of c3 would become Inf and 0 * Inf = NaN (tests/test_gpu_stale_workspace.py found it in
+            EFDN's per-op branch); the fused branch (esr_esa_lowres_f32) has always stored the zeros."""
+            if (st or lowres) and isinstance(dst, Buffer):
                 return min((cout + 15) // 16 * 16, dst.pitch)
             return cout
         if dst is not OUTPUT and dst is not None and not self.split:
@@ -668,7 +673,14 @@ class Dw(_Op):
         d.in_layout = d.out_layout = L.NHWC
         d.inp, d.out0 = _view(self.src, base), _view(self.dst, base)
         d.storage = 0 if self.hw is not None else L.STORE[plan.store]
-        d.wpacked = ctypes.c_void_p(weights[self.w].data_ptr())
+        w = self.w
+        if (self.hw is not None and self.c < 16 and isinstance(self.src, Buffer) and isinstance(self.dst, Buffer)
+                and min(self.src.pitch, self.dst.pitch) >= 16 and w + DWPAD in weights):
+            # a low-resolution map that is a whole dense buffer is stored whole, pad channels (zeros: zero weights, zero bias) included:
+            # Conv.encode, full_width.  The pointwise conv in front of it stored its pad channels the same way
+            d.cin = d.cout = 16
+            w += DWPAD
+        d.wpacked = ctypes.c_void_p(weights[w].data_ptr())
 
     def cost(self, plan, desc):
         npix, e_act = (plan.npix, plan.esize) if self.hw is None else (plan.n * self.hw[0] * self.hw[1], 4)
@@ -1396,7 +1408,8 @@ class HipSRModel(nn.Module):
     # Plans of different shapes lay their buffers out in ONE workspace, so after a shape switch another shape's activations lie where
     # this plan keeps its pad channels.  That is harmless: every pad slot is only ever multiplied by a zero weight (packers), added
     # to an accumulator nobody stores, or copied into another pad slot -- stale FINITE values of the SAME element type cannot reach a
-    # result (bit-identical outputs in every mode: tools/dbg/rezero_probe.py, test_hundred_shapes_one_workspace).  Same type is what
+    # result (bit-identical outputs in every mode: tools/dbg/rezero_probe.py, test_hundred_shapes_one_workspace, and for every form the
+    # engine plans under hostile finite patterns tests/test_gpu_stale_workspace.py).  Same type is what
     # the two arenas of a Plan are for: the low-resolution fp32 maps of all plans live in front of the workspace (`_lo_cap` bytes),
     # the full-resolution buffers behind them, so a 16-bit plan never reads another shape's fp32 bytes (Inf / NaN patterns).
     # Re-zeroing 130 MB per forward was 26 us of a 0.7 ms image (every DIV2K image has its own shape): +3 % in DIV2K mode (A/B).
@@ -1519,6 +1532,14 @@ class HipSRModel(nn.Module):
         for path in self._dw_specs:
             leaf = self._leaf(path)
             packed[path] = pack_dw(leaf.weight, leaf.bias).to(device)
+            c = leaf.weight.shape[0]
+            if c < 16:                                  # (ESA's low-resolution depthwise layers: Dw.encode)
+                w16 = torch.zeros(16, 1, 3, 3)
+                w16[:c] = leaf.weight.detach().to("cpu", torch.float32)
+                b16 = torch.zeros(16)
+                if leaf.bias is not None:
+                    b16[:c] = leaf.bias.detach().to("cpu", torch.float32)
+                packed[path + DWPAD] = pack_dw(w16, b16).to(device)
         self._extra_pack(packed, device)
         if torch.device(device).type == "cuda":
             torch.cuda.synchronize(device)           # the blobs are read by forwards on ANY stream from here on
