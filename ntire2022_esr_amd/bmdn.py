@@ -20,8 +20,6 @@ A distillation step has two forms (model.fuse_step):
            forwards at 32 x 256 x 256 / one 339 x 510 image in bf16.
 Which form a plan takes depends on the per-image shape and esr_distill_step_supported only, never on the batch size.
 """
-import ctypes
-
 from . import _lib as L
 from .engine import FOLD, INPUT, OUTPUT, EsaLayer, HipSRModel, Post
 from .rfdn import _slice_map
@@ -63,21 +61,6 @@ class BMDN(HipSRModel):
     def set_scale(self, scale_idx):
         self.scale_idx = scale_idx
 
-    def _step_fused(self, plan, cin, pitch_in, pitch_mid):
-        """does this plan run a step of `cin` input channels as one esr_distill_step_s16 launch?  The per-image shape and the kernel's
-        predicate decide; the batch size is not asked (a batch and its single images take the same kernels)"""
-        if not (self.fuse_step and plan.esize == 2):
-            return False
-        d = L.ChainDesc()
-        d.n, d.h, d.w, d.n_layers = 1, plan.h, plan.w, 2
-        d.cin, d.cmid, d.cout = cin, self.dc, self.dc
-        d.act, d.res_mode = L.ACT_RELU, (L.RES_NONE if cin != self.dc else L.RES_PRE_ACT)
-        d.storage = d.compute = L.STORE[plan.store]
-        d.inp = L.View(None, pitch_in, 0)
-        d.post_out = d.post2_out = L.View(None, pitch_mid, 0)
-        d.post_cout = d.post2_cout = min((self.dc + 15) // 16 * 16, pitch_mid)
-        return bool(L.lib().esr_distill_step_supported(ctypes.byref(d)))
-
     def _build_plan(self, plan, c):
         if c != self.in_nc:
             raise L.EsrError(f'BMDN expects {self.in_nc} input channels, got {c}')
@@ -106,7 +89,6 @@ class BMDN(HipSRModel):
         la, lb = plan.buffer('esa_a', FP, h3, w3), plan.buffer('esa_b', FP, h3, w3)
         relu = dict(act=L.ACT_RELU)
         lo = dict(hw=(h3, w3))
-        fused = {nf: self._step_fused(plan, nf, P, RP), dc: self._step_fused(plan, dc, RP, RP)}
         plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, hilo=L.HILO_OUT if hl else 0)
         cur = fea
         for k in range(1, 5):
@@ -121,8 +103,8 @@ class BMDN(HipSRModel):
                 else:                                     # :163-165 / :169-171: r_j = act(c_r(r) + r + c_b(d))
                     plan.conv(b + f'c{j}_b', cs(j - 1), t, dc, dc, res=r, res_mode=L.RES_PRE_ACT)
                 plan.conv(b + f'c{j}_r', r, dst, cin, dc, res=t, res_mode=L.RES_PRE_ACT, **relu)
-                if fused[cin]:
-                    plan.distill_step(mark)
+                if self.fuse_step and s16:
+                    plan.distill_step(mark)               # (where the kernel takes the step; else the three launches stay)
                 r = dst
             plan.conv(b + 'c4', r, cs(3), dc, dc, **relu)
             if s16 and (nf + 15) // 16 in (3, 4) and f <= 16:

@@ -11,6 +11,7 @@ import collections
 import ctypes
 import itertools
 import threading
+import types
 import weakref
 from dataclasses import dataclass
 
@@ -22,7 +23,32 @@ from . import _lib as L
 
 
 def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _host(t):
+    """a tensor (or None) as a contiguous CPU float32 tensor"""
+    return None if t is None else t.detach().to("cpu", torch.float32).contiguous()
+
+
+def _pack_args(weight=None, bias=None, cin=None, cin_map=None, cin_phys=None, compute=None, flat=False):
+    """The packers' shared opening -> namespace(w, b, cm, cm_p, cin_phys, compute): weight and bias on the host (_host; a 2-D weight as
+    [out, in, 1, 1], `flat`: any weight as [out, -1]); `cin_map[s]` = logical input channel carried by physical slot s, or -1 for a zero pad
+    slot (padded concat buffers) -> its int32 array `cm`, the pointer `cm_p` into it (the namespace keeps the array alive across the C call)
+    and `cin_phys` = its length (no map: `cin_phys`, else the weight's inputs, else `cin`); `compute` by name -> its L.COMPUTE code."""
+    w = _host(weight)
+    if w is not None and flat:
+        w = w.reshape(w.shape[0], -1)
+    elif w is not None and w.dim() == 2:
+        w = w[:, :, None, None].contiguous()
+    cm = cm_p = None
+    if cin_map is not None:
+        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
+        cin_phys, cm_p = len(cm), cm.ctypes.data_as(ctypes.c_void_p)
+    elif cin_phys is None:
+        cin_phys = cin if w is None else w.shape[1]
+    return types.SimpleNamespace(w=w, b=_host(bias), cm=cm, cm_p=cm_p, cin_phys=cin_phys,
+                                 compute=L.COMPUTE[compute] if isinstance(compute, str) else compute)
 
 
 def pack_conv(weight, bias, cin_map=None, cin_phys=None):
@@ -31,26 +57,14 @@ def pack_conv(weight, bias, cin_map=None, cin_phys=None):
     Host-side, no GPU needed.  `cin_map[s]` = logical input channel carried by physical
     slot s, or -1 for a zero pad slot (padded concat buffers)."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    if w.dim() == 2:
-        w = w[:, :, None, None].contiguous()
-    cout, cin, k, k2 = w.shape
+    a = _pack_args(weight, bias, cin_map=cin_map, cin_phys=cin_phys)
+    cout, cin, k, k2 = a.w.shape
     assert k == k2 and k in (1, 3), "only 1x1 / 3x3 kernels are on the hot path"
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
-    if cin_map is not None:
-        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
-        cin_phys = len(cm)
-        cm_p = cm.ctypes.data_as(ctypes.c_void_p)
-    else:
-        cm, cm_p = None, None
-        cin_phys = cin if cin_phys is None else cin_phys
-    nbytes = lib.esr_packed_conv_bytes(cin_phys, cout, k)
+    nbytes = lib.esr_packed_conv_bytes(a.cin_phys, cout, k)
     if nbytes == 0:
-        raise L.EsrError(f"esr_packed_conv_bytes rejected cin_phys={cin_phys} cout={cout} k={k}")
+        raise L.EsrError(f"esr_packed_conv_bytes rejected cin_phys={a.cin_phys} cout={cout} k={k}")
     out = torch.empty(nbytes // 4, dtype=torch.float32)
-    rc = lib.esr_pack_conv_f32(_ptr(w), _ptr(b) if b is not None else None, cin, cout, k,
-                               cm_p, cin_phys, _ptr(out), nbytes)
-    L.check(rc, "esr_pack_conv_f32")
+    L.check(lib.esr_pack_conv_f32(_ptr(a.w), _ptr(a.b), cin, cout, k, a.cm_p, a.cin_phys, _ptr(out), nbytes), "esr_pack_conv_f32")
     return out
 
 
@@ -58,36 +72,22 @@ def pack_wino(weight, bias, cin_map=None, cin_phys=None):
     """OIHW fp32 3x3 weights + bias -> the Winograd F(2x2, 3x3) blob of esr_pack_wino_f32 (U = G g G^T, computed in fp64 and
     rounded once, in wino_f32_kernel's A-operand order).  Host-side, no GPU needed."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    cout, cin, k, k2 = w.shape
+    a = _pack_args(weight, bias, cin_map=cin_map, cin_phys=cin_phys)
+    cout, cin, k, k2 = a.w.shape
     assert k == 3 and k2 == 3
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
-    if cin_map is not None:
-        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
-        cin_phys, cm_p = len(cm), cm.ctypes.data_as(ctypes.c_void_p)
-    else:
-        cm_p = None
-        cin_phys = cin if cin_phys is None else cin_phys
-    nbytes = lib.esr_packed_wino_bytes(cin_phys, cout)
+    nbytes = lib.esr_packed_wino_bytes(a.cin_phys, cout)
     out = torch.empty(nbytes // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_wino_f32(_ptr(w), _ptr(b) if b is not None else None, cin, cout, cm_p, cin_phys, _ptr(out), nbytes),
-            "esr_pack_wino_f32")
+    L.check(lib.esr_pack_wino_f32(_ptr(a.w), _ptr(a.b), cin, cout, a.cm_p, a.cin_phys, _ptr(out), nbytes), "esr_pack_wino_f32")
     return out
 
 
 def unpack_wino(blob, cin, cout, cin_map=None, cin_phys=None):
     """U [cout, cin, 16] and bias of a pack_wino blob (tests)."""
-    lib = L.lib()
-    blob = blob.detach().to("cpu", torch.float32).contiguous()
-    if cin_map is not None:
-        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
-        cin_phys, cm_p = len(cm), cm.ctypes.data_as(ctypes.c_void_p)
-    else:
-        cm_p = None
-        cin_phys = cin if cin_phys is None else cin_phys
+    blob = _host(blob)
+    a = _pack_args(cin=cin, cin_map=cin_map, cin_phys=cin_phys)
     u = torch.empty(cout, cin, 16)
     b = torch.empty(cout)
-    L.check(lib.esr_unpack_wino_f32(_ptr(blob), blob.numel() * 4, cin, cout, cm_p, cin_phys, _ptr(u), _ptr(b)), "esr_unpack_wino_f32")
+    L.check(L.lib().esr_unpack_wino_f32(_ptr(blob), blob.numel() * 4, cin, cout, a.cm_p, a.cin_phys, _ptr(u), _ptr(b)), "esr_unpack_wino_f32")
     return u, b
 
 
@@ -95,23 +95,12 @@ def pack_conv_s16(weight, bias, compute, cin_map=None, cin_phys=None):
     """OIHW (or [out,in]) fp32 weights -> the 16-bit-storage blob of esr_pack_conv_s16 (bf16 or fp16; 3x3 taps rounded
     with error diffusion, 1x1 as hi + lo) + fp32 bias."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    if w.dim() == 2:
-        w = w[:, :, None, None].contiguous()
-    cout, cin, k, _ = w.shape
+    a = _pack_args(weight, bias, cin_map=cin_map, cin_phys=cin_phys, compute=compute)
+    cout, cin, k, _ = a.w.shape
     assert k in (1, 3)
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
-    if cin_map is not None:
-        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
-        cin_phys, cm_p = len(cm), cm.ctypes.data_as(ctypes.c_void_p)
-    else:
-        cm_p = None
-        cin_phys = cin if cin_phys is None else cin_phys
-    nbytes = lib.esr_packed_conv_s16_bytes(cin_phys, cout, k)
+    nbytes = lib.esr_packed_conv_s16_bytes(a.cin_phys, cout, k)
     out = torch.empty((nbytes + 3) // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_conv_s16(_ptr(w), _ptr(b) if b is not None else None, cin, cout, k, cm_p, cin_phys,
-                                  L.COMPUTE[compute] if isinstance(compute, str) else compute, _ptr(out), nbytes),
-            "esr_pack_conv_s16")
+    L.check(lib.esr_pack_conv_s16(_ptr(a.w), _ptr(a.b), cin, cout, k, a.cm_p, a.cin_phys, a.compute, _ptr(out), nbytes), "esr_pack_conv_s16")
     return out
 
 
@@ -130,13 +119,11 @@ def pack_post_s16(weight, bias, compute):
     """[cout, cin(, 1, 1)] fp32 weights of a 1x1 evaluated in a 16-bit conv's epilogue (esr_conv_desc.post_* / post2_*) ->
     esr_pack_post_s16 blob (MFMA images of the weights' 16-bit high and low parts + fp32 bias)."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).reshape(weight.shape[0], -1).contiguous()
-    cout, cin = w.shape
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
+    a = _pack_args(weight, bias, compute=compute, flat=True)
+    cout, cin = a.w.shape
     nbytes = lib.esr_packed_post_s16_bytes(cin, cout)
     out = torch.empty((nbytes + 3) // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_post_s16(_ptr(w), _ptr(b) if b is not None else None, cin, cout,
-                                  L.COMPUTE[compute] if isinstance(compute, str) else compute, _ptr(out), nbytes), "esr_pack_post_s16")
+    L.check(lib.esr_pack_post_s16(_ptr(a.w), _ptr(a.b), cin, cout, a.compute, _ptr(out), nbytes), "esr_pack_post_s16")
     return out
 
 
@@ -144,17 +131,15 @@ def pack_tail_s16(weight, bias, nseg, seg_c, mid_c, compute):
     """[cout, nseg * seg_c + mid_c(, 1, 1)] fp32 weights of the 1x1 of a 16-bit tail (esr_conv_desc.tail_*, ABI v12: RFDB's c5 over
     cat(d1, d2, d3, r4)) -> esr_pack_tail_s16 blob (hi / lo fragment images for v_mfma_f32_32x32x16 + fp32 bias)."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).reshape(weight.shape[0], -1).contiguous()
-    cout, kin = w.shape
+    a = _pack_args(weight, bias, compute=compute, flat=True)
+    cout, kin = a.w.shape
     if kin != nseg * seg_c + mid_c:
         raise L.EsrError("pack_tail_s16: the 1x1 takes nseg * seg_c + mid_c inputs")
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
     nbytes = lib.esr_packed_tail_s16_bytes(nseg, seg_c, mid_c, cout)
     if not nbytes:
         raise L.EsrError("pack_tail_s16: unsupported shape")
     out = torch.empty((nbytes + 3) // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_tail_s16(_ptr(w), _ptr(b) if b is not None else None, nseg, seg_c, mid_c, cout,
-                                  L.COMPUTE[compute] if isinstance(compute, str) else compute, _ptr(out), nbytes), "esr_pack_tail_s16")
+    L.check(lib.esr_pack_tail_s16(_ptr(a.w), _ptr(a.b), nseg, seg_c, mid_c, cout, a.compute, _ptr(out), nbytes), "esr_pack_tail_s16")
     return out
 
 
@@ -181,41 +166,28 @@ def pack_apply_post(w0, b0, w1, b1, store):
     """Weights of the 1x1 chain riding in esr_esa_apply_f32's launch (esr_esa_desc.post_w): w0 [cout0, cin(, 1, 1)] applied to the
     apply result, w1 [cout1, cout0(, 1, 1)] (or None) applied to w0's result -> esr_pack_apply_post blob."""
     lib = L.lib()
-    w0 = w0.detach().to("cpu", torch.float32).reshape(w0.shape[0], -1).contiguous()
-    cout0, cin = w0.shape
-    b0 = None if b0 is None else b0.detach().to("cpu", torch.float32).contiguous()
-    cout1 = 0
-    if w1 is not None:
-        w1 = w1.detach().to("cpu", torch.float32).reshape(w1.shape[0], -1).contiguous()
-        cout1 = w1.shape[0]
-        if w1.shape[1] != cout0:
-            raise L.EsrError("pack_apply_post: w1 must take w0's outputs")
-        b1 = None if b1 is None else b1.detach().to("cpu", torch.float32).contiguous()
+    a0 = _pack_args(w0, b0, flat=True)
+    a1 = _pack_args(w1, None if w1 is None else b1, flat=True)
+    cout0, cin = a0.w.shape
+    cout1 = 0 if w1 is None else a1.w.shape[0]
+    if w1 is not None and a1.w.shape[1] != cout0:
+        raise L.EsrError("pack_apply_post: w1 must take w0's outputs")
     st = L.STORE[store]
     nbytes = lib.esr_packed_apply_post_bytes(cin, cout0, cout1, st)
     if not nbytes:
         raise L.EsrError("pack_apply_post: unsupported shape / storage")
     out = torch.empty((nbytes + 3) // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_apply_post(_ptr(w0), _ptr(b0) if b0 is not None else None, _ptr(w1) if w1 is not None else None,
-                                    _ptr(b1) if (w1 is not None and b1 is not None) else None, cin, cout0, cout1, st, _ptr(out), nbytes),
-            "esr_pack_apply_post")
+    L.check(lib.esr_pack_apply_post(_ptr(a0.w), _ptr(a0.b), _ptr(a1.w), _ptr(a1.b), cin, cout0, cout1, st, _ptr(out), nbytes), "esr_pack_apply_post")
     return out
 
 
 def unpack_conv_s16(blob, cin, cout, k, compute, cin_map=None, cin_phys=None):
     """EFFECTIVE fp32 weights (what the 16-bit kernel multiplies by) + bias of a pack_conv_s16 blob."""
-    lib = L.lib()
     blob = blob.detach().to("cpu").contiguous()
-    if cin_map is not None:
-        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
-        cin_phys, cm_p = len(cm), cm.ctypes.data_as(ctypes.c_void_p)
-    else:
-        cm_p = None
-        cin_phys = cin if cin_phys is None else cin_phys
+    a = _pack_args(cin=cin, cin_map=cin_map, cin_phys=cin_phys, compute=compute)
     w = torch.empty(cout, cin, k, k)
     b = torch.empty(cout)
-    L.check(lib.esr_unpack_conv_s16(_ptr(blob), blob.numel() * blob.element_size(), cin, cout, k, cm_p, cin_phys,
-                                    L.COMPUTE[compute] if isinstance(compute, str) else compute, _ptr(w), _ptr(b)),
+    L.check(L.lib().esr_unpack_conv_s16(_ptr(blob), blob.numel() * blob.element_size(), cin, cout, k, a.cm_p, a.cin_phys, a.compute, _ptr(w), _ptr(b)),
             "esr_unpack_conv_s16")
     return w, b
 
@@ -223,43 +195,31 @@ def unpack_conv_s16(blob, cin, cout, k, compute, cin_map=None, cin_phys=None):
 def pack_dense(weight, bias, cin_p, cout_p):
     """Plain [tap][cin_p][cout_p] + bias[cout_p] layout of the small ESA kernels (esr_pack_dense_f32)."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    if w.dim() == 2:
-        w = w[:, :, None, None].contiguous()
-    cout, cin, k, _ = w.shape
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
+    a = _pack_args(weight, bias)
+    cout, cin, k, _ = a.w.shape
     nbytes = lib.esr_packed_dense_bytes(cin_p, cout_p, k)
     out = torch.empty(nbytes // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_dense_f32(_ptr(w), _ptr(b) if b is not None else None, cin, cout, k, cin_p, cout_p,
-                                   _ptr(out), nbytes), "esr_pack_dense_f32")
+    L.check(lib.esr_pack_dense_f32(_ptr(a.w), _ptr(a.b), cin, cout, k, cin_p, cout_p, _ptr(out), nbytes), "esr_pack_dense_f32")
     return out
 
 
 def pack_dw(weight, bias):
     """Depthwise [C,1,3,3] weights + bias -> [tap][cp] + bias[cp] (esr_pack_dw_f32)."""
     lib = L.lib()
-    w = weight.detach().to("cpu", torch.float32).contiguous()
-    c = w.shape[0]
-    b = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
+    a = _pack_args(weight, bias)
+    c = a.w.shape[0]
     nbytes = lib.esr_packed_dw_bytes(c)
     out = torch.empty(nbytes // 4, dtype=torch.float32)
-    L.check(lib.esr_pack_dw_f32(_ptr(w), _ptr(b) if b is not None else None, c, _ptr(out), nbytes), "esr_pack_dw_f32")
+    L.check(lib.esr_pack_dw_f32(_ptr(a.w), _ptr(a.b), c, _ptr(out), nbytes), "esr_pack_dw_f32")
     return out
 
 
 def unpack_conv(blob, cin, cout, k, cin_map=None, cin_phys=None):
-    lib = L.lib()
-    blob = blob.detach().to("cpu", torch.float32).contiguous()
-    if cin_map is not None:
-        cm = np.ascontiguousarray(np.asarray(cin_map, dtype=np.int32))
-        cin_phys, cm_p = len(cm), cm.ctypes.data_as(ctypes.c_void_p)
-    else:
-        cm_p = None
-        cin_phys = cin if cin_phys is None else cin_phys
+    blob = _host(blob)
+    a = _pack_args(cin=cin, cin_map=cin_map, cin_phys=cin_phys)
     w = torch.empty(cout, cin, k, k)
     b = torch.empty(cout)
-    rc = lib.esr_unpack_conv_f32(_ptr(blob), blob.numel() * 4, cin, cout, k, cm_p, cin_phys, _ptr(w), _ptr(b))
-    L.check(rc, "esr_unpack_conv_f32")
+    L.check(L.lib().esr_unpack_conv_f32(_ptr(blob), blob.numel() * 4, cin, cout, k, a.cm_p, a.cin_phys, _ptr(w), _ptr(b)), "esr_unpack_conv_f32")
     return w, b
 
 
@@ -319,6 +279,25 @@ def _stored_channels(v, logical, chunk):
     if isinstance(v, tuple):
         return (v[2] + chunk - 1) // chunk * chunk
     return logical
+
+
+def _stored_width(dst, c, whole=True):
+    """channels a launch stores for the `c` logical channels of destination `dst`: the pad channels of the last K chunk too where `dst` is
+    a WHOLE dense buffer (`whole`: Conv.encode asks this for 16-bit storage and low-resolution maps only).
+    16-bit storage: the pad channels are zeros (zero weight rows, zero bias) -- a 24-of-32-channel store leaves every 64-byte run partial,
+    and partial-line stores cost up to 2.3x a full one (tools/dbg/s16_1x1_probe.py).  Slices of shared buffers keep their width.
+    A low-resolution fp32 map that is a whole dense buffer likewise, in every storage type, for another reason: the fp16 ESA apply
+    kernel rounds s = bilinear(c3) + conv_f(c1) of all 16 slots to fp16 before conv4's zero weight rows meet it, so a stale fp32
+    value beyond 65504 in a pad slot of c3 would become Inf and 0 * Inf = NaN (tests/test_gpu_stale_workspace.py found it in
+    EFDN's per-op branch); the fused branch (esr_esa_lowres_f32) has always stored the zeros."""
+    if whole and isinstance(dst, Buffer):
+        return min((c + 15) // 16 * 16, dst.pitch)
+    return c
+
+
+def _tf(flag):
+    """a bool as the kernels' template argument"""
+    return "true" if flag else "false"
 
 
 def _addr(buf, base):
@@ -489,19 +468,9 @@ class Conv(_Op):
         d.hilo = self.hilo
         d.storage = 0 if lowres else st                       # ESA low-resolution maps: fp32
 
-        def full_width(dst, cout):
-            """16-bit storage, destination = a WHOLE dense buffer: store the pad channels of its last K chunk too (they are
-            zeros: zero weight rows, zero bias) -- a 24-of-32-channel store leaves every 64-byte run partial, and partial-line
-            stores cost up to 2.3x a full one (tools/dbg/s16_1x1_probe.py).  Slices of shared buffers keep their width.
-            A low-resolution fp32 map that is a whole dense buffer likewise, in every storage type, for another reason: the fp16 ESA apply
-            kernel rounds s = bilinear(c3) + conv_f(c1) of all 16 slots to fp16 before conv4's zero weight rows meet it, so a stale fp32
-            value beyond 65504 in a pad slot of c3 would become Inf and 0 * Inf = NaN (tests/test_gpu_stale_workspace.py found it in
-            EFDN's per-op branch); the fused branch (esr_esa_lowres_f32) has always stored the zeros."""
-            if (st or lowres) and isinstance(dst, Buffer):
-                return min((cout + 15) // 16 * 16, dst.pitch)
-            return cout
+        width = lambda dst, c: _stored_width(dst, c, st or lowres)
         if dst is not OUTPUT and dst is not None and not self.split:
-            d.cout = full_width(dst, self.cout)
+            d.cout = width(dst, self.cout)
         if self.s16(plan):
             d.wpacked = ctypes.c_void_p(weights[self.w + S16].data_ptr())     # conv_s16_kernel
             d.compute = st
@@ -520,7 +489,7 @@ class Conv(_Op):
                 d.tail_cat = _view(t.cat.seg(0), base)
                 d.tail_seg_stride16 = t.cat.stride // 16
                 d.cout = self.cout
-                d.tail_cout = full_width(dst, t.cout)
+                d.tail_cout = width(dst, t.cout)
             else:
                 d.tail_cat = _view(t.cat, base)
                 d.tail_cout = t.cout
@@ -529,7 +498,7 @@ class Conv(_Op):
             psfx = POST if (st and not lowres) else ""       # 16-bit storage: esr_pack_post_s16 images
             d.post_wpacked = ctypes.c_void_p(weights[t.w + psfx].data_ptr())
             d.post_out = _view(t.dst, base)
-            d.post_cout, d.post_act = full_width(t.dst, t.cout) if psfx else t.cout, t.act
+            d.post_cout, d.post_act = width(t.dst, t.cout) if psfx else t.cout, t.act
             t2 = t.post2
             if t2 is not None:
                 d.post2_wpacked = ctypes.c_void_p(weights[t2.w + psfx].data_ptr())
@@ -677,7 +646,7 @@ class Dw(_Op):
         if (self.hw is not None and self.c < 16 and isinstance(self.src, Buffer) and isinstance(self.dst, Buffer)
                 and min(self.src.pitch, self.dst.pitch) >= 16 and w + DWPAD in weights):
             # a low-resolution map that is a whole dense buffer is stored whole, pad channels (zeros: zero weights, zero bias) included:
-            # Conv.encode, full_width.  The pointwise conv in front of it stored its pad channels the same way
+            # _stored_width.  The pointwise conv in front of it stored its pad channels the same way
             d.cin = d.cout = 16
             w += DWPAD
         d.wpacked = ctypes.c_void_p(weights[w].data_ptr())
@@ -798,16 +767,45 @@ class Pool7(_Op):
 
 
 @dataclass
-class Lowres(_Op):
+class _Fused(_Op):
+    """ONE op in place of a run of ops, which stay attached as `replaces`: weights, complexity counters and algorithmic costs are theirs.
+    Where the kernel takes only some shapes the class names the C ABI's `predicate` (esr_*_supported), the esr_op `field` it reads and the
+    kernel in words (`what`), and states the structure it stands for in check(): Plan._fuse asks the predicate about the descriptor
+    `encode` fills before it fuses, Plan.finalize once more."""
+    replaces: list
+    predicate = None
+
+    def check(self):
+        pass
+
+    def supported(self, op):
+        """does the kernel take the descriptor that `encode` filled into `op`?"""
+        return self.predicate is None or bool(getattr(L.lib(), self.predicate)(ctypes.byref(getattr(op, self.field))))
+
+    def counted_convs(self, plan):
+        return [c for o in self.replaces for c in o.counted_convs(plan)]
+
+
+class _AnyBlob:
+    """the weights of Plan._fuse's probe: every name yields a non-null dummy address (the predicates test blob pointers for null only)"""
+
+    def __getitem__(self, name):
+        return self
+
+    def data_ptr(self):
+        return 4096
+
+
+@dataclass
+class Lowres(_Fused):
     """ESA's low-resolution branch as ONE op (esr_esa_lowres_f32) -- see Plan.esa_lowres.  w: conv2's weights (None: EFDN's stride-7 branch,
-    pooled straight from `src`); replaces: the ops it stands for."""
+    pooled straight from `src`)."""
     src: Buffer
     pooled: Buffer
     dst: Buffer
     f: int
     w: str
     layers: list
-    replaces: list
     kind = "lowres"
 
     def encode(self, op, plan, base, weights):
@@ -840,17 +838,26 @@ class Lowres(_Op):
         return _cost(self.w, f"esa_s2pool{'16' if plan.esize == 2 else ''}_kernel<{L.STORE[plan.store]}> + esa_chain_kernel", f, f, 3, flops,
                      float(plan.n * src.h * src.w * f * src.esize + npl * f * 4), float(2 * npl * f * 4))
 
-    def counted_convs(self, plan):
-        return [c for o in self.replaces for c in o.counted_convs(plan)]
-
 
 @dataclass
-class Chain(_Op):
+class Chain(_Fused):
     """A block's 3x3 convolutions as ONE esr_conv_chain_s16 op -- see Plan.chain (gate=False: rlfb_chain_kernel) and Plan.hfab
-    (gate=True: hfab_kernel).  replaces: the Conv ops it stands for (weights, complexity counters, algorithmic costs)."""
-    replaces: list
+    (gate=True: hfab_kernel)."""
     gate: bool = False
     kind = "chain"
+    predicate, field = "esr_conv_chain_supported", "chain"
+    what = property(lambda self: "HFAB" if self.gate else "chain")
+
+    def check(self):
+        sub, last = self.replaces, self.replaces[-1]
+        assert (len(sub) == 4 if self.gate else len(sub) >= 2) and all(o.kind == "conv" and o.k == 3 for o in sub)
+        for a, b in zip(sub[:-1], sub[1:]):
+            assert b.src is a.dst and a.res is None and a.post is None
+        if self.gate:
+            assert all(a.act == sub[0].act for a in sub[:-1])
+            assert last.res_mode == L.RES_GATE and last.res is sub[0].src and last.post is None and isinstance(last.dst, Buffer)
+        else:
+            assert last.dst is None and last.res is sub[0].src and last.post is not None and last.post.post2 is not None
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -865,27 +872,21 @@ class Chain(_Op):
         d.inp = _view(first.src, base)
         for l, so in enumerate(sub):
             d.wpacked[l] = weights[so.w + S16].data_ptr()
-        if self.gate:                                         # HFAB: the gated result goes to post_out, whole pad chunk included
-            d.post_out = _view(last.dst, base)
-            d.post_cout = min((last.cout + 15) // 16 * 16, last.dst.pitch)
-            if not L.lib().esr_conv_chain_supported(ctypes.byref(d)):
-                raise L.EsrError(f"{first.w}: no HFAB kernel for this shape (the plan should have kept separate ops)")
+        if self.gate:                                         # HFAB: the gated result goes to post_out
+            d.post_out, d.post_cout = _view(last.dst, base), _stored_width(last.dst, last.cout)
             return
         t, t2 = last.post, last.post.post2
-        pc = min((t.cout + 15) // 16 * 16, t.dst.pitch) if isinstance(t.dst, Buffer) else t.cout    # (whole dense buffer: pad channels too)
         d.post_wpacked, d.post_out = ctypes.c_void_p(weights[t.w + POST].data_ptr()), _view(t.dst, base)
-        d.post_cout, d.post_act = pc, t.act
+        d.post_cout, d.post_act = _stored_width(t.dst, t.cout), t.act
         d.post2_wpacked, d.post2_out = ctypes.c_void_p(weights[t2.w + POST].data_ptr()), _view(t2.dst, base)
         d.post2_cout = t2.cout
-        if not L.lib().esr_conv_chain_supported(ctypes.byref(d)):
-            raise L.EsrError(f"{first.w}: no chain kernel for this shape (the plan should have kept separate ops)")
 
     def cost(self, plan, desc):
         sub, npix, es = self.replaces, plan.npix, plan.esize
         flops = sum(2.0 * npix * so.cin_alg * so.cout * 9 for so in sub)
         wb = 4.0 * sum(so.cin_alg * so.cout * 9 for so in sub)
         if self.gate:                   # HFAB in one launch: x read once (also the gate operand), the gated result written once
-            kern = f"hfab_kernel<{'true' if plan.store == 'bf16' else 'false'}, {(sub[0].cin + 15) // 16}>"
+            kern = f"hfab_kernel<{_tf(plan.store == 'bf16')}, {(sub[0].cin + 15) // 16}>"
             stored = float(npix * es * (_stored_channels(sub[0].src, sub[0].cin, 16) + _stored_channels(sub[-1].dst, sub[-1].cout, 16))) + wb
             return _cost(sub[0].w, kern, sub[0].cin, sub[-1].cout, 3, flops, float(npix * sub[0].cin_alg * es) + wb,
                          float(npix * sub[-1].cout * es), stored)
@@ -895,16 +896,20 @@ class Chain(_Op):
         rd = float(npix * sub[0].cin_alg * es) + 4.0 * (sum(so.cin_alg * so.cout * 9 for so in sub) + sub[-1].cout * t.cout + t.cout * t2.cout)
         return _cost(sub[0].w, f"rlfb_chain_kernel<{plan.store}>", sub[0].cin, sub[-1].cout, 3, flops, rd, float(npix * es * (t.cout + t2.cout)))
 
-    def counted_convs(self, plan):
-        return [c for o in self.replaces for c in o.counted_convs(plan)]
-
 
 @dataclass
-class Distill(_Op):
-    """A BMDB distillation step as ONE esr_distill_step_s16 op -- see Plan.distill_step (distill_step_kernel).  replaces: the three Conv ops it
-    stands for, [c_d, c_b, c_r] (weights, complexity counters, algorithmic costs)."""
-    replaces: list
+class Distill(_Fused):
+    """A BMDB distillation step as ONE esr_distill_step_s16 op -- see Plan.distill_step (distill_step_kernel).  replaces: [c_d, c_b, c_r]."""
     kind = "distill"
+    predicate, field, what = "esr_distill_step_supported", "chain", "distillation step"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 3 and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub)
+        cd, cb, cr = sub
+        assert cd.k == 1 and cb.k == 3 and cr.k == 3 and cd.act == cr.act == L.ACT_RELU and cb.act == L.ACT_NONE and cd.res is None
+        assert _same_view(cb.src, cd.dst) and _same_view(cr.src, cd.src) and _same_view(cr.res, cb.dst) and cr.res_mode == L.RES_PRE_ACT
+        assert cb.res is None or (_same_view(cb.res, cd.src) and cb.res_mode == L.RES_PRE_ACT)
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -918,31 +923,36 @@ class Distill(_Op):
         d.inp = _view(cd.src, base)
         d.wpacked[0] = weights[cd.w + S16].data_ptr()
         d.wpacked[1] = weights[cr.w + FOLD].data_ptr()
-        full = lambda dst, c: min((c + 15) // 16 * 16, dst.pitch) if isinstance(dst, Buffer) else c      # (whole dense buffer: pad channels too)
-        d.post_out, d.post_cout = _view(cd.dst, base), full(cd.dst, cd.cout)
-        d.post2_out, d.post2_cout = _view(cr.dst, base), full(cr.dst, cr.cout)
-        if not L.lib().esr_distill_step_supported(ctypes.byref(d)):
-            raise L.EsrError(f"{cd.w}: no distillation step kernel for this shape (the plan should have kept separate ops)")
+        d.post_out, d.post_cout = _view(cd.dst, base), _stored_width(cd.dst, cd.cout)
+        d.post2_out, d.post2_cout = _view(cr.dst, base), _stored_width(cr.dst, cr.cout)
 
     def cost(self, plan, desc):             # the step's input read once, d and the result written once
         cd, cb, cr = self.replaces
         npix, es = plan.npix, plan.esize
         flops = sum(2.0 * npix * so.cin_alg * so.cout * so.k * so.k for so in self.replaces)
         wb = 4.0 * sum(so.cin_alg * so.cout * so.k * so.k for so in self.replaces)
-        kern = f"distill_step_kernel<{'true' if plan.store == 'bf16' else 'false'}, {(cd.cin + 15) // 16}, {'true' if cb.res is not None else 'false'}>"
+        kern = f"distill_step_kernel<{_tf(plan.store == 'bf16')}, {(cd.cin + 15) // 16}, {_tf(cb.res is not None)}>"
         stored = float(npix * es * (_stored_channels(cd.src, cd.cin, 16) + _stored_channels(cd.dst, cd.cout, 16) + _stored_channels(cr.dst, cr.cout, 16))) + wb
         return _cost(cd.w, kern, cd.cin, cr.cout, 3, flops, float(npix * cd.cin_alg * es) + wb, float(npix * es * (cd.cout + cr.cout)), stored)
 
-    def counted_convs(self, plan):
-        return [c for o in self.replaces for c in o.counted_convs(plan)]
-
 
 @dataclass
-class ResHead(_Op):
-    """The head of ESAN's residual block as ONE esr_resblock_head_s16 op -- see Plan.resblock_head (resblock_head_kernel).  replaces: the Conv ops
-    it stands for, [add,] conv1, conv2, ESA.conv1 (weights, complexity counters, algorithmic costs); the first block of the trunk has no add."""
-    replaces: list
+class ResHead(_Fused):
+    """The head of ESAN's residual block as ONE esr_resblock_head_s16 op -- see Plan.resblock_head (resblock_head_kernel).  replaces: [add,]
+    conv1, conv2, ESA.conv1; the first block of the trunk has no add."""
     kind = "reshead"
+    predicate, field, what = "esr_resblock_head_supported", "conv", "residual-block head"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) in (3, 4) and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub)
+        c1, c2, ce = sub[-3:]
+        assert c1.k == 3 and c2.k == 3 and ce.k == 1 and c1.act == L.ACT_RELU and c2.act == ce.act == L.ACT_NONE
+        assert c1.res is None and c2.res is None and ce.res is None and _same_view(c2.src, c1.dst) and _same_view(ce.src, c2.dst)
+        if len(sub) == 4:
+            add = sub[0]
+            assert add.k == 1 and not add.counted and add.act == L.ACT_NONE and add.res_mode == L.RES_PRE_ACT and _same_view(c1.src, add.dst)
+            assert not _same_view(add.dst, add.res) and not _same_view(add.dst, add.src)
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -965,10 +975,7 @@ class ResHead(_Op):
         d.wpacked = ctypes.c_void_p(weights[c1.w + S16].data_ptr())
         d.tail_wpacked = ctypes.c_void_p(weights[c2.w + S16].data_ptr())
         d.post_wpacked = ctypes.c_void_p(weights[ce.w + S16].data_ptr())
-        d.post_out = _view(ce.dst, base)
-        d.post_cout = min((ce.cout + 15) // 16 * 16, ce.dst.pitch) if isinstance(ce.dst, Buffer) else ce.cout   # (whole dense buffer: pad channels too)
-        if not L.lib().esr_resblock_head_supported(ctypes.byref(d)):
-            raise L.EsrError(f"{c1.w}: no residual-block head kernel for this shape (the plan should have kept separate ops)")
+        d.post_out, d.post_cout = _view(ce.dst, base), _stored_width(ce.dst, ce.cout)
 
     def cost(self, plan, desc):             # xin (and g) read once; x, u and c1 written once
         add = len(self.replaces) == 4
@@ -977,14 +984,11 @@ class ResHead(_Op):
         convs = (c1, c2, ce)
         flops = sum(2.0 * npix * so.cin_alg * so.cout * so.k * so.k for so in convs)
         wb = 4.0 * sum(so.cin_alg * so.cout * so.k * so.k for so in convs)
-        kern = f"resblock_head_kernel<{'true' if plan.store == 'bf16' else 'false'}, {'true' if add else 'false'}>"
+        kern = f"resblock_head_kernel<{_tf(plan.store == 'bf16')}, {_tf(add)}>"
         rd = float(npix * es * c1.cin * (2 if add else 1)) + wb
         wr = float(npix * es * ((c1.cin if add else 0) + c2.cout + ce.cout))
         stored = float(npix * es * (c1.cin * (3 if add else 1) + c2.cout + _stored_channels(ce.dst, ce.cout, 16))) + wb
         return _cost(c1.w, kern, c1.cin, c2.cout, 3, flops, rd, wr, stored)
-
-    def counted_convs(self, plan):
-        return [c for o in self.replaces for c in o.counted_convs(plan)]
 
 
 @dataclass
@@ -1127,37 +1131,37 @@ class Plan:
         depthwise pairs); or, with s2 = None, EFDN's maxpool7s7, conv_2, conv_3 and conv_23 (layers: one kind-2 pair and one kind-3 layer);
         those ops stay attached as `replaces`: the complexity counters and the algorithmic costs are theirs.
         layers: [EsaLayer, ...]"""
-        sub = self.ops[mark:]
-        del self.ops[mark:]
-        self.ops.append(Lowres(c1, pooled, dst, f, s2, layers, sub))
+        self.ops[mark:] = [Lowres(self.ops[mark:], c1, pooled, dst, f, s2, layers)]
+
+    def _fuse(self, mark, fused, **kw):
+        """ONE `fused` op (a _Fused class) in place of the ops appended since `mark`, if its kernel takes them; says whether it did -- if
+        not, the ops stay as they are.  The kernel's predicate decides, on the descriptor finalize() will launch: `encode` fills it
+        against a null workspace and stand-in weights (_AnyBlob; no blob exists yet in HipSRModel._repack's plan), with n = 1: a batch
+        and its single images take the same kernels."""
+        assert self.esize == 2
+        o = fused(self.ops[mark:], **kw)
+        o.check()
+        probe = L.Op()
+        o.encode(probe, self, (0, 0), _AnyBlob())
+        getattr(probe, o.field).n = 1
+        if not o.supported(probe):
+            return False
+        self.ops[mark:] = [o]
+        return True
 
     def chain(self, mark):
         """The 3x3 convolutions appended since `mark = len(plan.ops)` -- a residual block's chain src -> t1 -> ... -> (+ src) -> post 1x1 ->
         post2 1x1, RLFB's c1_r -> c2_r -> c3_r -> c5 -> esa.conv1 (team04_rlfn.py:109-122) -- as ONE esr_conv_chain_s16 op (16-bit plans):
         the intermediate tensors stay in LDS (rlfb_chain_kernel).  The Conv ops stay attached as `replaces`: weights, complexity
         counters and algorithmic costs are theirs; the result is bit-identical to running them one by one."""
-        sub = self.ops[mark:]
-        assert self.esize == 2 and len(sub) >= 2 and all(o.kind == "conv" and o.k == 3 for o in sub)
-        for a, b in zip(sub[:-1], sub[1:]):
-            assert b.src is a.dst and a.res is None and a.post is None
-        last = sub[-1]
-        assert last.dst is None and last.res is sub[0].src and last.post is not None and last.post.post2 is not None
-        del self.ops[mark:]
-        self.ops.append(Chain(sub))
+        return self._fuse(mark, Chain)
 
     def hfab(self, mark):
         """The four 3x3 convolutions appended since `mark = len(plan.ops)` -- FMEN's HFAB with one BasicBlock, x -> squeeze -> conv -> conv ->
         sigmoid(excitate) * x (team03_fmen.py:60-73) -- as ONE esr_conv_chain_s16 op with res_mode L.RES_GATE (hfab_kernel, 16-bit plans): x is
         read once, t1 .. t3 stay in LDS.  The Conv ops stay attached as `replaces` (weights, complexity counters, algorithmic costs); the
         result is bit-identical to running them one by one."""
-        sub = self.ops[mark:]
-        assert self.esize == 2 and len(sub) == 4 and all(o.kind == "conv" and o.k == 3 for o in sub)
-        for a, b in zip(sub[:-1], sub[1:]):
-            assert b.src is a.dst and a.res is None and a.post is None and a.act == sub[0].act
-        last = sub[-1]
-        assert last.res_mode == L.RES_GATE and last.res is sub[0].src and last.post is None and isinstance(last.dst, Buffer)
-        del self.ops[mark:]
-        self.ops.append(Chain(sub, gate=True))
+        return self._fuse(mark, Chain, gate=True)
 
     def distill_step(self, mark):
         """The three convolutions appended since `mark = len(plan.ops)` -- a BMDB distillation step in its per-op form, d = relu(c_d(r)),
@@ -1165,14 +1169,7 @@ class Plan:
         and r' are written once, t never exists (the two 3x3s are one over cat[r, d]: engine.pack_distill_s16, blob `<c_r>#fold`).  The Conv
         ops stay attached as `replaces`: weights, complexity counters and algorithmic costs are theirs.  Not bit-identical to them: the per-op
         form rounds t to the storage type."""
-        sub = self.ops[mark:]
-        assert self.esize == 2 and len(sub) == 3 and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub)
-        cd, cb, cr = sub
-        assert cd.k == 1 and cb.k == 3 and cr.k == 3 and cd.act == cr.act == L.ACT_RELU and cb.act == L.ACT_NONE and cd.res is None
-        assert _same_view(cb.src, cd.dst) and _same_view(cr.src, cd.src) and _same_view(cr.res, cb.dst) and cr.res_mode == L.RES_PRE_ACT
-        assert cb.res is None or (_same_view(cb.res, cd.src) and cb.res_mode == L.RES_PRE_ACT)
-        del self.ops[mark:]
-        self.ops.append(Distill(sub))
+        return self._fuse(mark, Distill)
 
     def resblock_head(self, mark):
         """The convolutions appended since `mark = len(plan.ops)` -- the head of ESAN's residual block in its per-op form, [x = xin + g as an
@@ -1180,17 +1177,7 @@ class Plan:
         esr_resblock_head_s16 op (16-bit plans): xin and g are read once, x, u and c1 written once, t never exists.  The Conv ops stay
         attached as `replaces`: weights, complexity counters and algorithmic costs are theirs.  x must not be stored over xin or g: the
         neighbouring tiles read their halo."""
-        sub = self.ops[mark:]
-        assert self.esize == 2 and len(sub) in (3, 4) and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub)
-        c1, c2, ce = sub[-3:]
-        assert c1.k == 3 and c2.k == 3 and ce.k == 1 and c1.act == L.ACT_RELU and c2.act == ce.act == L.ACT_NONE
-        assert c1.res is None and c2.res is None and ce.res is None and _same_view(c2.src, c1.dst) and _same_view(ce.src, c2.dst)
-        if len(sub) == 4:
-            add = sub[0]
-            assert add.k == 1 and not add.counted and add.act == L.ACT_NONE and add.res_mode == L.RES_PRE_ACT and _same_view(c1.src, add.dst)
-            assert not _same_view(add.dst, add.res) and not _same_view(add.dst, add.src)
-        del self.ops[mark:]
-        self.ops.append(ResHead(sub))
+        return self._fuse(mark, ResHead)
 
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
@@ -1207,6 +1194,8 @@ class Plan:
         base = workspace if isinstance(workspace, tuple) else ((workspace if isinstance(workspace, int) else (workspace.data_ptr() if workspace is not None else 0)), self.total_lo)
         for i, o in enumerate(self.ops):
             o.encode(arr[i], self, base, weights)
+            if isinstance(o, _Fused) and not o.supported(arr[i]):
+                raise L.EsrError(f"{o.cost(self, None)['name']}: no {o.what} kernel for this shape (the plan should have kept separate ops)")
         in_idx = [i for i, o in enumerate(self.ops) if getattr(o, "src", None) is INPUT]
         out_idx = [i for i, o in enumerate(self.ops) if getattr(o, "dst", None) is OUTPUT]
         return arr, in_idx, out_idx
@@ -1295,6 +1284,12 @@ class _StreamCtx:
         self.lo_cap = 0            # bytes reserved in front of the workspace for the plans' low-resolution fp32 maps (grow-only)
         self.profs = {}
 
+    def drop_profs(self):
+        """destroys the per-kernel event sets"""
+        for prof in self.profs.values():
+            L.lib().esr_prof_destroy(prof)
+        self.profs = {}
+
 
 class HipSRModel(nn.Module):
     """Base of the drop-in nn.Modules.  Subclasses register reference-compatible parameters
@@ -1326,18 +1321,21 @@ class HipSRModel(nn.Module):
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
 
     # -- parameter registration: same key names as the reference state_dict -------------------
-    def _add_conv(self, path, cin, cout, k, cin_map=None, linear=False, dense=None, stride=1, padding=None, custom=False):
-        """Create nested containers so that `path + '.weight'` / `path + '.bias'` are the
-        state_dict keys (e.g. 'model.1.sub.0.conv1.0').  The leaf is an nn.Conv2d / nn.Linear
-        used purely as a parameter holder with the reference's shapes and default init."""
+    def _add_leaf(self, path, leaf):
+        """registers `leaf` under the dotted `path`, creating the nested containers on the way"""
         parts = path.split(".")
         mod = self
         for p in parts[:-1]:
             if p not in mod._modules:
                 mod.add_module(p, nn.Module())
             mod = mod._modules[p]
-        leaf = nn.Linear(cin, cout) if linear else nn.Conv2d(cin, cout, k, stride, (k - 1) // 2 if padding is None else padding)
         mod.add_module(parts[-1], leaf)
+
+    def _add_conv(self, path, cin, cout, k, cin_map=None, linear=False, dense=None, stride=1, padding=None, custom=False):
+        """Create nested containers so that `path + '.weight'` / `path + '.bias'` are the
+        state_dict keys (e.g. 'model.1.sub.0.conv1.0').  The leaf is an nn.Conv2d / nn.Linear
+        used purely as a parameter holder with the reference's shapes and default init."""
+        self._add_leaf(path, nn.Linear(cin, cout) if linear else nn.Conv2d(cin, cout, k, stride, (k - 1) // 2 if padding is None else padding))
         if dense is not None:
             self._dense_specs[path] = dense
         elif not custom:
@@ -1345,13 +1343,7 @@ class HipSRModel(nn.Module):
 
     def _add_dw(self, path, c):
         """depthwise nn.Conv2d(c, c, 3, 1, 1, groups=c) parameter holder (`path.weight` is [c,1,3,3])."""
-        parts = path.split(".")
-        mod = self
-        for p in parts[:-1]:
-            if p not in mod._modules:
-                mod.add_module(p, nn.Module())
-            mod = mod._modules[p]
-        mod.add_module(parts[-1], nn.Conv2d(c, c, 3, 1, 1, groups=c))
+        self._add_leaf(path, nn.Conv2d(c, c, 3, 1, 1, groups=c))
         self._dw_specs.append(path)
 
     def _leaf(self, path):
@@ -1437,9 +1429,7 @@ class HipSRModel(nn.Module):
     def _drop_plans(self):
         with self._lock:
             for ctx in self._ctxs.values():
-                for prof in ctx.profs.values():
-                    L.lib().esr_prof_destroy(prof)
-                ctx.profs = {}
+                ctx.drop_profs()
                 for ent in ctx.plans.values():
                     ent.drop_graph()
                 ctx.plans.clear()
@@ -1456,9 +1446,7 @@ class HipSRModel(nn.Module):
             ctx = _StreamCtx()
         self._ctxs[key] = ctx          # (re)inserted at the end: dict order = least recently used first
         while len(self._ctxs) > self.MAX_STREAMS:
-            old = next(iter(self._ctxs))
-            for prof in self._ctxs.pop(old).profs.values():
-                L.lib().esr_prof_destroy(prof)
+            self._ctxs.pop(next(iter(self._ctxs))).drop_profs()
         return ctx
 
     # the default-stream context under its historical names (tests, tools)
@@ -1494,7 +1482,9 @@ class HipSRModel(nn.Module):
                 continue
             if o.kind == "bs":                              # BSConvU: pointwise + distillation 1x1 weights as hi + lo blobs
                 s16.update([o.pw] + ([o.distill.w] if o.distill is not None else []))
-            for c in o.replaces if o.kind in ("chain", "distill", "reshead") else [o] if o.kind == "conv" else []:
+            for c in (o.replaces if isinstance(o, _Fused) else [o]):      # (a fused op's blobs are those of the ops it stands for)
+                if c.kind != "conv":
+                    continue
                 if c.s16(plan) and c.head:
                     head.add(c.w[:-len(HEAD)])
                 elif c.s16(plan):
@@ -1690,9 +1680,7 @@ class HipSRModel(nn.Module):
     def disable_profiling(self):
         with self._lock:
             for ctx in self._ctxs.values():
-                for prof in ctx.profs.values():
-                    L.lib().esr_prof_destroy(prof)
-                ctx.profs = {}
+                ctx.drop_profs()
             self._prof_passes = 0
 
     def op_costs(self, plan, arr=None):

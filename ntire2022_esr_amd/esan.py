@@ -23,8 +23,6 @@ The head of a block -- the `+` of the previous block, conv1, conv2 and ESA.conv1
            stays a per-op launch.  Measurements: DESIGN.md 7e.
 Which form a plan takes depends on the per-image shape and esr_resblock_head_supported only, never on the batch size.
 """
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -57,21 +55,6 @@ class ESAN(HipSRModel):
             self._add_conv(b + 'ESA.conv4', f, nf, 1, dense=(FP, nf))
         self._add_conv('upconv.0', nf, out_nc * 16, 3)
 
-    def _head_fused(self, plan):
-        """does this plan run a block's head as one esr_resblock_head_s16 launch?  The per-image shape and the kernel's predicate decide; the
-        batch size is not asked (a batch and its single images take the same kernels)"""
-        if not (self.fuse_head and plan.esize == 2):
-            return False
-        d = L.ConvDesc()
-        d.n, d.h, d.w = 1, plan.h, plan.w
-        d.cin, d.cout, d.ksize = self.nf, self.nf, 3
-        d.in_layout = d.out_layout = L.NHWC
-        d.act, d.res_mode = L.ACT_RELU, L.RES_PRE_ACT
-        d.storage = d.compute = L.STORE[plan.store]
-        d.inp = d.res = d.out0 = d.out1 = L.View(None, self.nf, 0)
-        d.post_out, d.post_cout = L.View(None, FP, 0), FP
-        return bool(L.lib().esr_resblock_head_supported(ctypes.byref(d)))
-
     def _build_plan(self, plan, c):
         if c != self.in_nc:
             raise L.EsrError(f'ESAN expects {self.in_nc} input channels, got {c}')
@@ -86,7 +69,6 @@ class ESAN(HipSRModel):
         lo2 = plan.buffer('esa_s2', FP, h2, w2)
         la, lb = plan.buffer('esa_a', FP, h3, w3), plan.buffer('esa_b', FP, h3, w3)
         lo = dict(hw=(h3, w3))
-        fused = self._head_fused(plan)
         if s16:
             # [trunk (32) | the packed input's 16 slots]: the output convolution's folded 3x3 reads both, the head convolution the slots
             cat = plan.buffer('cat', nf + 16)
@@ -108,8 +90,8 @@ class ESAN(HipSRModel):
             plan.conv(b + 'conv1', cur, t, nf, nf, act=L.ACT_RELU)
             plan.conv(b + 'conv2', t, u, nf, nf)
             plan.conv(b + 'ESA.conv1', u, c1, nf, f, k=1)
-            if fused:
-                plan.resblock_head(mark)
+            if self.fuse_head and s16:
+                plan.resblock_head(mark)                      # (where the kernel takes the head; else the launches stay)
             mark = len(plan.ops)
             plan.conv3x3s2(b + 'ESA.conv2', c1, lo2, f)
             plan.maxpool7s3(lo2, la)

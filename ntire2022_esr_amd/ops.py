@@ -32,6 +32,23 @@ def _provided(t, what, like, shape, cmin, gran):
     return t
 
 
+def _zeros_or(t, what, like, shape, cmin, gran, pitch=None):
+    """the output an op stores into: the caller's `t`, checked (_provided), or fresh zeros [*shape, pitch] (default pitch: cmin) like `like`"""
+    if t is not None:
+        return _provided(t, what, like, shape, cmin, gran)
+    return torch.zeros(tuple(shape) + (cmin if pitch is None else pitch,), dtype=like.dtype, device=like.device)
+
+
+def _s16_store(x, what):
+    """the shared opening of the one-launch 16-bit ops: x on the GPU, its storage type by name, 16-bit storage only"""
+    if not x.is_cuda:
+        raise L.EsrError(f"{what}: tensors must live on the GPU; there is no CPU fallback")
+    st = _STORE_OF[x.dtype]
+    if st == "f32":
+        raise L.EsrError(f"{what}: 16-bit storage only")
+    return st
+
+
 _TRACE = None       # kernel_trace(): the list that collects device symbols
 
 
@@ -220,15 +237,14 @@ def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.
         pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
         keep2 = (pack_post_s16(pw, post_bias, st) if s16 else pack_conv(pw, post_bias)).to(x.device)
         pcs = (pw.shape[0] + gran - 1) // gran * gran
-        yp = torch.zeros((n, h, w, pcs), dtype=odt, device=x.device) if post_out is None else \
-            _provided(post_out, "conv2d: post_out", torch.empty(0, dtype=odt, device=x.device), (n, h, w), pcs, gran)
+        like = torch.empty(0, dtype=odt, device=x.device)
+        yp = _zeros_or(post_out, "conv2d: post_out", like, (n, h, w), pcs, gran)
         d.post_wpacked, d.post_out = ctypes.c_void_p(keep2.data_ptr()), _view(yp)
         d.post_cout, d.post_act = pw.shape[0], post_act
         if post2_weight is not None:
             keep3 = pack_post_s16(post2_weight, post2_bias, st).to(x.device)
             pcs2 = (post2_weight.shape[0] + 7) // 8 * 8
-            yp2 = torch.zeros((n, h, w, pcs2), dtype=odt, device=x.device) if post2_out is None else \
-                _provided(post2_out, "conv2d: post2_out", torch.empty(0, dtype=odt, device=x.device), (n, h, w), pcs2, 8)
+            yp2 = _zeros_or(post2_out, "conv2d: post2_out", like, (n, h, w), pcs2, 8)
             d.post2_wpacked, d.post2_out, d.post2_cout = ctypes.c_void_p(keep3.data_ptr()), _view(yp2), post2_weight.shape[0]
     stream = torch.cuda.current_stream(x.device).cuda_stream
     if (post_out is not None and post_weight is None) or (post2_out is not None and post2_weight is None):
@@ -253,67 +269,48 @@ def conv_chain(x, weights, biases, post_weight=None, post_bias=None, post2_weigh
     the first 1x1's channels) and c1 (a multiple of 8 holding the second's); default: freshly allocated zeros.  EsrError otherwise."""
     if res_mode == L.RES_GATE:
         return _hfab(x, weights, biases, act=act, slope=slope, cin=cin, out=out)
-    if not x.is_cuda:
-        raise L.EsrError("conv_chain: tensors must live on the GPU; there is no CPU fallback")
-    st = _STORE_OF[x.dtype]
-    if st == "f32":
-        raise L.EsrError("conv_chain: 16-bit storage only")
-    lib = L.lib()
+    d, st, keep = _chain_desc(x, weights, biases, act, slope, res_mode, cin)
     n, h, w, _ = x.shape
+    pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
+    p1 = pack_post_s16(pw, post_bias, st).to(x.device)
+    p2 = pack_post_s16(post2_weight, post2_bias, st).to(x.device)
+    v = _zeros_or(v_out, "conv_chain: v_out", x, (n, h, w), (pw.shape[0] + 15) // 16 * 16, 16)
+    c1 = _zeros_or(c1_out, "conv_chain: c1_out", x, (n, h, w), (post2_weight.shape[0] + 7) // 8 * 8, 8)
+    d.post_wpacked, d.post_out, d.post_cout, d.post_act = ctypes.c_void_p(p1.data_ptr()), _view(v), pw.shape[0], post_act
+    d.post2_wpacked, d.post2_out, d.post2_cout = ctypes.c_void_p(p2.data_ptr()), _view(c1), post2_weight.shape[0]
+    _launch_chain(d, x)
+    return v, c1
+
+
+def _chain_desc(x, weights, biases, act, slope, res_mode, cin):
+    """what both forms of conv_chain fill: shape, activation, input view and the packed 3x3s -> (descriptor, storage name, the blobs to keep)"""
+    st = _s16_store(x, "conv_chain")
     d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = n, h, w, len(weights)
+    d.n, d.h, d.w, d.n_layers = x.shape[0], x.shape[1], x.shape[2], len(weights)
     d.cin = weights[0].shape[1] if cin is None else cin
     d.cmid, d.cout = weights[0].shape[0], weights[-1].shape[0]
     d.act, d.slope, d.res_mode = act, slope, res_mode
     d.storage = d.compute = L.STORE[st]
     d.inp = _view(x)
-    keep = []
-    for i, (wt, b) in enumerate(zip(weights, biases)):
-        blob = pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device)
-        keep.append(blob)
+    keep = [pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device) for wt, b in zip(weights, biases)]
+    for i, blob in enumerate(keep):
         d.wpacked[i] = blob.data_ptr()
-    pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
-    p1 = pack_post_s16(pw, post_bias, st).to(x.device)
-    p2 = pack_post_s16(post2_weight, post2_bias, st).to(x.device)
-    vc, cc = (pw.shape[0] + 15) // 16 * 16, (post2_weight.shape[0] + 7) // 8 * 8
-    v = torch.zeros((n, h, w, vc), dtype=x.dtype, device=x.device) if v_out is None else _provided(v_out, "conv_chain: v_out", x, (n, h, w), vc, 16)
-    c1 = torch.zeros((n, h, w, cc), dtype=x.dtype, device=x.device) if c1_out is None else _provided(c1_out, "conv_chain: c1_out", x, (n, h, w), cc, 8)
-    d.post_wpacked, d.post_out, d.post_cout, d.post_act = ctypes.c_void_p(p1.data_ptr()), _view(v), pw.shape[0], post_act
-    d.post2_wpacked, d.post2_out, d.post2_cout = ctypes.c_void_p(p2.data_ptr()), _view(c1), post2_weight.shape[0]
-    if not lib.esr_conv_chain_supported(ctypes.byref(d)):
+    return d, st, keep
+
+
+def _launch_chain(d, x):
+    if not L.lib().esr_conv_chain_supported(ctypes.byref(d)):
         raise L.EsrError("conv_chain: no kernel for this shape (esr_conv_chain_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, stream, L.OP_CONV_CHAIN, "chain")
-    return v, c1
+    _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, torch.cuda.current_stream(x.device).cuda_stream, L.OP_CONV_CHAIN, "chain")
 
 
 def _hfab(x, weights, biases, *, act, slope, cin, out):
-    if not x.is_cuda:
-        raise L.EsrError("conv_chain: tensors must live on the GPU; there is no CPU fallback")
-    st = _STORE_OF[x.dtype]
-    if st == "f32":
-        raise L.EsrError("conv_chain: 16-bit storage only")
-    lib = L.lib()
+    d, st, keep = _chain_desc(x, weights, biases, act, slope, L.RES_GATE, cin)
     n, h, w, pitch = x.shape
-    d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = n, h, w, len(weights)
-    d.cin = weights[0].shape[1] if cin is None else cin
-    d.cmid, d.cout = weights[0].shape[0], weights[-1].shape[0]
-    d.act, d.slope, d.res_mode = act, slope, L.RES_GATE
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x)
-    keep = []
-    for i, (wt, b) in enumerate(zip(weights, biases)):
-        blob = pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device)
-        keep.append(blob)
-        d.wpacked[i] = blob.data_ptr()
-    y = torch.zeros((n, h, w, pitch), dtype=x.dtype, device=x.device) if out is None else _provided(out, "conv_chain: out", x, (n, h, w), pitch, 8)
+    y = _zeros_or(out, "conv_chain: out", x, (n, h, w), pitch, 8)
     d.post_out = _view(y)
     d.post_cout = min((d.cout + 15) // 16 * 16, y.shape[-1])      # the pad channels of the last chunk too, as the per-layer store (zeros)
-    if not lib.esr_conv_chain_supported(ctypes.byref(d)):
-        raise L.EsrError("conv_chain: no kernel for this shape (esr_conv_chain_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, stream, L.OP_CONV_CHAIN, "chain")
+    _launch_chain(d, x)
     return y
 
 
@@ -325,11 +322,7 @@ def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_cof
     d_out / out: caller-provided NHWC tensors of x's dtype and device (pitch a multiple of 8) that receive d / y from channel d_coff /
     out_coff; default: freshly allocated zeros of pitch round_up(channels, 8).  d_channels / out_channels: esr_chain_desc.post_cout /
     post2_cout, the stored widths (default: the logical ones; up to round_up(.., 16): the pad channels are written as zeros)."""
-    if not x.is_cuda:
-        raise L.EsrError("distill_step: tensors must live on the GPU; there is no CPU fallback")
-    st = _STORE_OF[x.dtype]
-    if st == "f32":
-        raise L.EsrError("distill_step: 16-bit storage only")
+    st = _s16_store(x, "distill_step")
     lib = L.lib()
     n, h, w, _ = x.shape
     w1 = w_d if w_d.dim() == 4 else w_d[:, :, None, None]
@@ -345,8 +338,8 @@ def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_cof
     d.post_cout = d.cmid if d_channels is None else d_channels
     d.post2_cout = d.cout if out_channels is None else out_channels
     dc8, oc8 = (d.post_cout + 7) // 8 * 8, (d.post2_cout + 7) // 8 * 8
-    dd = torch.zeros((n, h, w, dc8), dtype=x.dtype, device=x.device) if d_out is None else _provided(d_out, "distill_step: d_out", x, (n, h, w), dc8, 8)
-    y = torch.zeros((n, h, w, oc8), dtype=x.dtype, device=x.device) if out is None else _provided(out, "distill_step: out", x, (n, h, w), oc8, 8)
+    dd = _zeros_or(d_out, "distill_step: d_out", x, (n, h, w), dc8, 8)
+    y = _zeros_or(out, "distill_step: out", x, (n, h, w), oc8, 8)
     d.post_out, d.post2_out = _view(dd, d_coff), _view(y, out_coff)
     if not lib.esr_distill_step_supported(ctypes.byref(d)):
         raise L.EsrError("distill_step: no kernel for this shape (esr_distill_step_supported)")
@@ -363,11 +356,7 @@ def resblock_head(x, w1, b1, w2, b2, wc, bc, *, g=None, in_coff=0, g_coff=0, x_o
     x_out / u_out / c1_out: caller-provided NHWC tensors of x's dtype and device (pitch a multiple of 8) that receive xs / u / c1 from channel
     x_coff / u_coff / c1_coff; default: freshly allocated zeros (c1: pitch 16, the ESA map).  c1_channels: esr_conv_desc.post_cout, the
     stored width (default: the logical one; round_up(.., 8) channels are written, the pad ones as zeros)."""
-    if not x.is_cuda:
-        raise L.EsrError("resblock_head: tensors must live on the GPU; there is no CPU fallback")
-    st = _STORE_OF[x.dtype]
-    if st == "f32":
-        raise L.EsrError("resblock_head: 16-bit storage only")
+    st = _s16_store(x, "resblock_head")
     lib = L.lib()
     n, h, w, _ = x.shape
     wc4 = wc if wc.dim() == 4 else wc[:, :, None, None]
@@ -384,12 +373,11 @@ def resblock_head(x, w1, b1, w2, b2, wc, bc, *, g=None, in_coff=0, g_coff=0, x_o
     xs = None
     if g is not None:
         d.res = _view(g, g_coff)
-        xs = torch.zeros((n, h, w, c), dtype=x.dtype, device=x.device) if x_out is None else _provided(x_out, "resblock_head: x_out", x, (n, h, w), c, 8)
+        xs = _zeros_or(x_out, "resblock_head: x_out", x, (n, h, w), c, 8)
         d.out0 = _view(xs, x_coff)
-    u = torch.zeros((n, h, w, c), dtype=x.dtype, device=x.device) if u_out is None else _provided(u_out, "resblock_head: u_out", x, (n, h, w), c, 8)
+    u = _zeros_or(u_out, "resblock_head: u_out", x, (n, h, w), c, 8)
     d.post_cout = f if c1_channels is None else c1_channels
-    c8 = (d.post_cout + 7) // 8 * 8
-    c1 = torch.zeros((n, h, w, L.ESA_FP), dtype=x.dtype, device=x.device) if c1_out is None else _provided(c1_out, "resblock_head: c1_out", x, (n, h, w), c8, 8)
+    c1 = _zeros_or(c1_out, "resblock_head: c1_out", x, (n, h, w), (d.post_cout + 7) // 8 * 8, 8, pitch=L.ESA_FP)
     d.out1, d.post_out = _view(u, u_coff), _view(c1, c1_coff)
     if not lib.esr_resblock_head_supported(ctypes.byref(d)):
         raise L.EsrError("resblock_head: no kernel for this shape (esr_resblock_head_supported)")
@@ -530,8 +518,7 @@ def bsconv(x, pw_weight, pw_bias, dw_weight, dw_bias, *, act=L.ACT_NONE, slope=0
     d.n, d.h, d.w, d.cin, d.c = n, h, w, cin, c
     d.act, d.slope, d.res_mode = act, slope, res_mode
     d.inp = _view(x, in_coff)
-    y = torch.zeros((n, h, w, (c + 3) // 4 * 4), dtype=x.dtype, device=x.device) if out is None else \
-        _provided(out, "bsconv: out", x, (n, h, w), (c + 3) // 4 * 4, 4)
+    y = _zeros_or(out, "bsconv: out", x, (n, h, w), (c + 3) // 4 * 4, 4)
     d.out = _view(y)
     if d_out is not None and d_weight is None:
         raise L.EsrError("bsconv: d_out without d_weight")
@@ -542,8 +529,7 @@ def bsconv(x, pw_weight, pw_bias, dw_weight, dw_bias, *, act=L.ACT_NONE, slope=0
     if d_weight is not None:
         dco = d_weight.shape[0]
         keep.append(pk(d_weight, d_bias))
-        yd = torch.zeros((n, h, w, (dco + 3) // 4 * 4), dtype=x.dtype, device=x.device) if d_out is None else \
-            _provided(d_out, "bsconv: d_out", x, (n, h, w), (dco + 3) // 4 * 4, 4)
+        yd = _zeros_or(d_out, "bsconv: d_out", x, (n, h, w), (dco + 3) // 4 * 4, 4)
         d.d_packed, d.d_cout, d.d_act, d.d_out = ctypes.c_void_p(keep[2].data_ptr()), dco, d_act, _view(yd)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     _launch("esr_bsconv_f32", "esr_bsconv_f32", d, stream, L.OP_BSCONV, "bs")
@@ -624,8 +610,7 @@ def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False, p
         d.skip_y = 1 if skip_y else 0
         for k, t in enumerate(post):
             co = t["weight"].shape[0]
-            o = torch.zeros(n, h, w, (co + 7) // 8 * 8, dtype=x.dtype, device=x.device) if post_out is None else \
-                _provided(post_out[k], f"esa_apply: post_out[{k}]", x, (n, h, w), (co + 7) // 8 * 8, 8)
+            o = _zeros_or(None if post_out is None else post_out[k], f"esa_apply: post_out[{k}]", x, (n, h, w), (co + 7) // 8 * 8, 8)
             outs.append(o)
             pp = d.post[k]
             pp.cout, pp.act, pp.slope = co, t.get("act", L.ACT_NONE), t.get("slope", 0.05)

@@ -83,8 +83,9 @@ class RLFN_cut(HipSRModel):
                 # and three tensor passes less per block, and the rounding that cost RLFN bf16 most of its PSNR budget is gone
                 plan.conv(b + 'c3_r', t2, None, mf, nf, res=cur, res_mode=L.RES_POST_ACT, **act,
                           post=Post(b + 'c5', v, nf, post2=Post(b + 'esa.conv1', c1, f)))
-                if self.fuse_chain and (mf + 15) // 16 == 3:
-                    # ... and the three 3x3s as ONE launch: a layer-per-SIMD pipeline with t1 / t2 / u in LDS (esr_conv_chain_s16, round 5)
+                if self.fuse_chain:
+                    # ... and the three 3x3s as ONE launch where the kernel takes the shape: a layer-per-SIMD pipeline with t1 / t2 / u in LDS
+                    # (esr_conv_chain_s16, round 5)
                     plan.chain(mark_c)
             else:
                 plan.conv(b + 'c3_r', t2, u, mf, nf, res=cur, res_mode=L.RES_POST_ACT, **act)

@@ -171,7 +171,7 @@ def test_per_op_esa_branch_does_not_depend_on_stale_workspace_bytes(name, comput
     only their f < 16 channels, and the fp16 ESA apply kernel rounds all 16 slots of bilinear(c3) + conv_f(c1) to fp16 before conv4's zero
     weight rows: a stale fp32 value beyond 65504 in a pad slot of c3 became Inf, then NaN -- found by this module in EFDN's fp16 per-op form
     (pattern 0x77, buffer esa_c3) and in BSRN's (buffer esa_b, behind a depthwise launch), fixed by storing the whole dense map
-    (engine.Conv.encode: full_width; engine.Dw.encode)"""
+    (engine._stored_width; engine.Dw.encode)"""
     fused = True if name in GOLD_NETS and compute != "f32" else (False if name in GOLD_NETS else None)
     _poisoned_forwards_equal_clean(name, compute, fused, shape, lowres=False)
     ops = _models[name][0]._plans[_key(shape)].plan.ops
