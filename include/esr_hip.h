@@ -121,7 +121,7 @@ typedef struct esr_conv_desc {
     int32_t tail_cout;
     int32_t tail_mid_act;       /* esr_act applied to the 3x3 result before the 1x1 (slope = `slope`) */
     /* ABI v12 -- the tail in 16-bit storage (csrc/esr_c64m.hip: rfdb_tail_kernel): RFDB's c4 -> cat(d1, d2, d3, r4) -> c5 -> esa.conv1
-     * (models/rfdn_baseline/block.py:161-164, :117) in ONE launch.  The 3x3 (64 physical input channels, cout <= 32) is activated by
+     * (models/rfdn_baseline/block.py:161-164, :117) in ONE launch.  The 3x3 (64 physical input channels, 17 <= cout <= 32) is activated by
      * tail_mid_act and ROUNDED to the storage type (exactly the tensor the separate launches store) but never stored; tail_cat are
      * three dense tensors of pitch 32 (tail_cat_c = 96 physical slots) that lie tail_seg_stride16 * 16 bytes apart; the 1x1 (tail_cout
      * <= 64, no activation, weights from esr_pack_tail_s16) is stored to out0 AND, unrounded, feeds the post 1x1 (post_wpacked from

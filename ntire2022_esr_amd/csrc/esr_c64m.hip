@@ -97,13 +97,13 @@ constexpr int m_tail_stores(bool post, int spread)
     return last < M_NG ? m_stores_behind(post, m_slot_of_step(last)) + spp : m_stores_behind(post, m_slot_of_step(last - M_NG));
 }
 
-// the three-chunk forms (NCH = 3, GB: ESDB's c{j}_r, 27 k steps): store slots of a pair's stream -- POST q = 8, 17, 26, 36, 37 at slot q + 4,
+// the three-chunk forms (NCH = 3, GB: ESDB's c{j}_r, 27 k steps): store slots of a pair's stream -- POST q = 8, 17, 26, 38, 39 at slot q + 4,
 // plain q = 6, 13, 20 at 2 q + 4 -- and the tile-end wait: the last DMA piece (L = 36) rides behind k step 9 of the SECOND pair
 constexpr int m3_tail_stores(bool post, int spread)
 {
     const int slot = m_slot_of_step(spread * (M_PPW - 1) - 3 * M_TAPS);
     int n = 0;
-    if (post) { for (int s : {12, 21, 30, 40, 41}) n += s > slot; }
+    if (post) { for (int s : {12, 21, 30, 42, 43}) n += s > slot; }
     else { for (int s : {16, 30, 44}) n += s > slot; }
     return n;
 }
@@ -433,15 +433,16 @@ __global__ __launch_bounds__(256, 1) void conv64m_kernel(const S16K p)
         constexpr int q = decltype(q_)::value;
         if constexpr (NCH == 3 && POST) {
             // three block pairs of 4 + 4 operations (table row | + row, GELU | rounding | the post MFMA) + the pair's store, three idle slots
-            // while the last post MFMA drains, the post result's three blocks (GELU | rounding), its two stores
+            // while the last post MFMA drains, the post result's four blocks (GELU | rounding: all 32 channels of the post 1x1, as the
+            // four-chunk form), its two stores
             if constexpr (q >= 0 && q < 27) {
                 constexpr int P = q / 9, w = q % 9;
                 if constexpr (w < 8) block_op(par_, std::integral_constant<int, 2 * P + w / 4>{}, std::integral_constant<int, (w % 4) < 3 ? (w % 4) : 5>{});
                 else store_op(std::integral_constant<int, P>{}, r_);
-            } else if constexpr (q >= 30 && q < 36) {
+            } else if constexpr (q >= 30 && q < 38) {
                 post_act_op(std::integral_constant<int, (q - 30) / 2>{}, std::integral_constant<int, (q - 30) % 2>{});
-            } else if constexpr (q == 36 || q == 37) {
-                post_store_op(std::integral_constant<int, q - 36>{}, r_);
+            } else if constexpr (q == 38 || q == 39) {
+                post_store_op(std::integral_constant<int, q - 38>{}, r_);
             }
         } else if constexpr (NCH == 3) {
             if constexpr (q >= 0 && q < 21) {

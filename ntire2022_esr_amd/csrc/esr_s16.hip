@@ -980,7 +980,8 @@ static S16Path s16_select(const esr_conv_desc* d, bool any_range)
     return S16Path::S16;
 }
 
-// rfdb_tail_kernel's descriptors (ABI v12, esr_c64m.hip): a 3x3 over 64 physical input channels with <= 32 outputs whose rounded result is the
+// rfdb_tail_kernel's descriptors (ABI v12, esr_c64m.hip): a 3x3 over 64 physical input channels with 17 .. 32 outputs (two output tiles: the only
+// count esr_m32_conv_bytes emits the kernel's 32x32x16 weight image for at both chunk counts) whose rounded result is the
 // last 32 slots of a 1x1 over three more dense 32-slot tensors, <= 64 outputs stored and fed (unrounded) to a post 1x1 of <= 16 outputs; no
 // residual, no activation on the 1x1; from 256 tiles of 16 x 16
 static bool rfdb_tail_takes(const esr_conv_desc* d)
@@ -988,7 +989,7 @@ static bool rfdb_tail_takes(const esr_conv_desc* d)
     if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return false;
     if (!d->tail_wpacked || !d->wpacked || d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return false;
     const int nch = esr_round_up(d->cin, 16) / 16;
-    if ((nch != 3 && nch != 4) || d->cout < 1 || d->cout > 32 || d->tail_cat_c != 96) return false;
+    if ((nch != 3 && nch != 4) || d->cout < 17 || d->cout > 32 || d->tail_cat_c != 96) return false;
     if (d->res_mode != ESR_RES_NONE || d->hilo || d->in_seg_stride != 0 || d->act != ESR_ACT_NONE || d->blocked8) return false;
     if (nch == 4) {                                 // RFDB: LeakyReLU / ReLU / none on r4, 49 .. 64 outputs
         if (d->border_bias || d->tail_cout < 49 || d->tail_cout > 64) return false;
@@ -1015,7 +1016,9 @@ static int run_rfdb_tail(const esr_conv_desc* d, bool bf16, hipStream_t st)
     k.x = static_cast<const char*>(d->in.ptr);
     k.wp = static_cast<const char*>(d->wpacked);
     k.bias = reinterpret_cast<const float*>(k.wp + (size_t)nch * 5 * nt * 1024);
-    k.wm32 = k.wp + esr_m32_conv_offset(16 * nch, d->cout, 3);
+    const size_t m32_off = esr_m32_conv_offset(16 * nch, d->cout, 3);
+    if (!m32_off) return ESR_ERR_UNSUPPORTED;       // (a blob without the 32x32x16 image: nothing for the kernel to read)
+    k.wm32 = k.wp + m32_off;
     k.N = d->n; k.H = d->h; k.W = d->w;
     k.nchunks = nch;
     k.act = d->tail_mid_act;

@@ -237,6 +237,79 @@ def test_s16_packer_layout_diffusion_and_split():
     assert lib.esr_packed_conv_s16_bytes(64, 64, 2) == 0
 
 
+# (cin, cout, k) of the layers that the channel-width cases of the GPU tests launch (tests/test_gpu_{h16, fmen, chain, esan, bmdn, c64m}.py)
+_HFAB_W = [(33, 1), (39, 9), (44, 16), (49, 8), (51, 1), (61, 16), (62, 9), (64, 8)]
+WIDTH_LAYERS = sorted({(c, m, 3) for c, m in _HFAB_W} | {(m, m, 3) for _, m in _HFAB_W} | {(m, c, 3) for c, m in _HFAB_W} |                # HFAB
+                      {(33, 33, 3), (41, 34, 3), (34, 34, 3), (34, 41, 3), (40, 47, 3), (47, 47, 3), (47, 40, 3), (48, 48, 3)} |            # RLFB
+                      {(32, 32, 3), (32, 1, 1), (32, 9, 1), (32, 16, 1), (32, 32, 1)} |                                                     # ESAN's head
+                      {(17, 17, 1), (27, 32, 1), (32, 25, 1), (18, 24, 1), (22, 32, 1), (31, 17, 1), (33, 17, 1), (45, 32, 1), (48, 25, 1)} |   # BMDN's d
+                      {(c, c, 3) for c in (33, 41, 47, 49, 57, 63)} | {(49, 24, 3), (57, 17, 3), (63, 32, 3), (56, 31, 3)} |                # c{j}_r, c4
+                      {(41, 31, 3), (47, 32, 3), (33, 17, 3)})                                                                              # ESDB's c4
+
+
+def _s16_image_checks(blob, w, b, mode, cin_map, k):
+    """what every 16-bit packer test here asserts of a blob: the effective weights within one storage ulp of w per tap, the bias exact, and every
+    element of the tap-pair image, the bias block and the 32x32x16 image that no (slot, tap, output channel) of the layer owns exactly zero"""
+    from ntire2022_esr_amd import _lib as L
+    from ntire2022_esr_amd.engine import unpack_conv_s16
+    dt, eps = (torch.bfloat16, 2.0 ** -8) if mode == "bf16" else (torch.float16, 2.0 ** -11)
+    cout, cin = w.shape[:2]
+    cp = len(cin_map)
+    weff, beff = unpack_conv_s16(blob, cin, cout, k, mode, cin_map=cin_map)
+    assert torch.equal(beff, b)
+    if k == 3:
+        # error diffusion moves a tap by less than the rounding errors it carries: one ulp (2 eps relative) of the filter's largest tap
+        assert torch.equal(weff, weff.to(dt).float())
+        assert float(((weff - w).abs() / w.abs().amax(dim=(2, 3), keepdim=True)).max()) < 2 * eps
+    else:
+        # hi + lo: the fp32 weight to the square of the storage precision (fp16's low part: its subnormal floor)
+        assert bool(((weff - w).abs() <= (w.abs() * eps * eps * 8).clamp_min(6.0e-8)).all())
+    nt, nch, taps = (cout + 15) // 16, (cp + 15) // 16, k * k
+    pairs = (taps + 1) // 2
+    raw = torch.from_numpy(blob.numpy().view(np.int16).astype(np.int64))
+    nw = nch * pairs * nt * 512
+    owned = torch.zeros(nw, dtype=torch.bool)
+    sl = torch.tensor([s_ for s_ in range(cp) if cin_map[s_] >= 0])
+    ts = torch.arange(taps if k == 3 else 2)              # (1x1: the pair's second slot carries the low part)
+    oc = torch.arange(cout)
+    S, T, O = torch.meshgrid(sl, ts, oc, indexing="ij")
+    idx = ((((S // 16) * pairs + T // 2) * nt + O // 16) * 64 + ((T & 1) * 2 + (S % 16) // 8) * 16 + O % 16) * 8 + S % 8       # (s16_index, esr_s16.hip)
+    owned[idx.reshape(-1)] = True
+    assert int(owned.sum()) == idx.numel() and torch.all(raw[:nw][~owned] == 0)
+    bias = torch.from_numpy(blob.numpy().view(np.uint8)[nw * 2:nw * 2 + nt * 64].copy()).view(torch.float32)
+    assert torch.equal(bias[:cout], b) and torch.all(bias[cout:] == 0)
+    # the 32x32x16 image, where the blob has one: the same multiset of 16-bit values as the tap-pair image (so: no row dropped, nothing else set)
+    total = L.lib().esr_packed_conv_s16_bytes(cp, cout, k)
+    assert blob.numel() * 4 >= total
+    m32 = raw[nw + nt * 32:total // 2]
+    if len(m32):
+        assert torch.equal(torch.sort(m32[m32 != 0]).values, torch.sort(raw[:nw][raw[:nw] != 0]).values)
+
+
+@pytest.mark.parametrize("cin,cout,k", WIDTH_LAYERS)
+def test_s16_pack_roundtrip_at_every_tested_width(cin, cout, k):
+    """esr_pack_conv_s16 / esr_unpack_conv_s16 at the widths of the GPU tests' channel-width cases, both storage types"""
+    from ntire2022_esr_amd.engine import pack_conv_s16
+    g = torch.Generator().manual_seed(1000 * cin + 10 * cout + k)
+    w, b = torch.randn(cout, cin, k, k, generator=g) * 0.1, torch.randn(cout, generator=g)
+    cp = (cin + 15) // 16 * 16
+    for mode in ("bf16", "f16"):
+        _s16_image_checks(pack_conv_s16(w, b, mode, cin_phys=cp), w, b, mode, [s_ if s_ < cin else -1 for s_ in range(cp)], k)
+
+
+@pytest.mark.parametrize("cin,cmid,cout", [(17, 17, 17), (33, 17, 25), (48, 32, 32)])
+def test_distill_fold_roundtrip_at_the_ends_of_its_ranges(cin, cmid, cout):
+    """engine.pack_distill_s16 / distill_cin_map: the folded 3x3 over [in chunks | d chunks], its pad rows between and behind the two zero"""
+    from ntire2022_esr_amd.engine import distill_cin_map, pack_distill_s16
+    g = torch.Generator().manual_seed(100 * cin + cmid)
+    w_r, b_r = torch.randn(cout, cin, 3, 3, generator=g) * 0.05, torch.randn(cout, generator=g) * 0.1
+    w_b, b_b = torch.randn(cout, cmid, 3, 3, generator=g) * 0.05, torch.randn(cout, generator=g) * 0.1
+    cmap = distill_cin_map(cin, cmid)
+    assert len(cmap) == (cin + 15) // 16 * 16 + (cmid + 15) // 16 * 16 and sorted(c for c in cmap if c >= 0) == list(range(cin + cmid))
+    for mode in ("bf16", "f16"):
+        _s16_image_checks(pack_distill_s16(w_r, b_r, w_b, b_b, mode), torch.cat([w_r, w_b], 1), b_r + b_b, mode, cmap, 3)
+
+
 def test_m32_images_hold_the_same_weights_as_the_tap_pair_images():
     """Round 6 (csrc/esr_c64m.hip): esr_pack_conv_s16 appends the 64 -> 64 3x3's weights in v_mfma_f32_32x32x16's fragment order -- fragment
     (chunk, tap, half) of 1 KB, lane 32 h + i, slot j = output channel 32 half + i, input slot 16 chunk + 8 h + j -- and esr_pack_post_s16 the
@@ -315,7 +388,7 @@ def test_pack_tail_s16_fragment_order():
     from ntire2022_esr_amd.engine import pack_tail_s16
     g = torch.Generator().manual_seed(5)
     for mode, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
-        for nf, dc in ((50, 25), (64, 32)):
+        for nf, dc in ((50, 25), (64, 32), (49, 17), (33, 17)):       # (.., the lower end of both forms' ranges: RFDB's, ESDB's)
             w, b = torch.randn(nf, 4 * dc, generator=g) * 0.3, torch.randn(nf, generator=g)
             blob = pack_tail_s16(w, b, 3, dc, dc, mode)
             assert blob.numel() * 4 == 32 * 1024 + 256 == L.lib().esr_packed_tail_s16_bytes(3, dc, dc, nf)

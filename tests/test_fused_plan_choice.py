@@ -69,3 +69,37 @@ def test_rlfn_keeps_the_per_op_form_where_the_chain_kernel_refuses(packed):
     chains = [o for o in plan.ops if o.kind == "chain"]
     assert len(chains) == 4 and [[c.w for c in o.replaces] for o in chains] == [[f"B{k}.c{j}_r" for j in (1, 2, 3)] for k in range(1, 5)]
     assert not any(o.kind == "conv" and o.w.endswith(("c1_r", "c2_r", "c3_r")) for o in plan.ops)
+
+
+@pytest.mark.parametrize("esdb", [False, True])
+def test_the_tail_predicate_refuses_a_3x3_of_one_output_tile(esdb):
+    """rfdb_tail_kernel reads the 3x3's weights from the 32x32x16 image behind the blob's bias, which esr_pack_conv_s16 emits for two output tiles
+    (17 .. 32 outputs) at three and four chunks and not for one: the descriptor of tests/test_gpu_c64m.py's tail cases (4 x 128 x 144, nf = 50 |
+    48, f = 16; no pointer is read) is taken with 17, 25 and 32 outputs and refused with 16 and 1 -- as with 33."""
+    from ntire2022_esr_amd import _lib as L
+    lib = L.lib()
+    nf, cp = (48, 48) if esdb else (50, 64)
+    a = 0x10000000                                # (any non-null 16-byte-aligned addresses)
+
+    def desc(dc):
+        d = L.ConvDesc()
+        d.n, d.h, d.w, d.cin, d.cout, d.ksize = 4, 128, 144, nf, dc, 3
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = L.STORE["bf16"]
+        d.act, d.slope = L.ACT_NONE, 0.05
+        d.inp = L.View(ctypes.c_void_p(a), cp, 0)
+        d.out0 = L.View(ctypes.c_void_p(a + (1 << 24)), cp, 0)
+        d.wpacked, d.tail_wpacked, d.post_wpacked = (ctypes.c_void_p(a + (k << 26)) for k in (1, 2, 3))
+        d.tail_cat = L.View(ctypes.c_void_p(a + (2 << 24)), 32, 0)
+        d.tail_cat_c, d.tail_cout, d.tail_mid_act = 96, nf, (L.ACT_GELU if esdb else L.ACT_LRELU)
+        d.tail_seg_stride16 = 4 * 128 * 144 * 32 * 2 // 16
+        d.post_out = L.View(ctypes.c_void_p(a + (3 << 24)), 16, 0)
+        d.post_cout, d.post_act = 16, L.ACT_NONE
+        if esdb:
+            d.border_bias = ctypes.c_void_p(a + (4 << 26))
+        return d
+
+    assert [lib.esr_conv_tail_supported(ctypes.byref(desc(dc))) for dc in (1, 16, 17, 25, 32, 33)] == [0, 0, 1, 1, 1, 0]
+    # the packer's side of the same fact: the blob of a one-tile 3x3 is the tap-pair image and the bias, nothing behind them
+    for dc, image in ((16, 0), (17, (3 if esdb else 4) * 9 * 1024), (32, (3 if esdb else 4) * 9 * 1024)):
+        assert lib.esr_packed_conv_s16_bytes(cp, dc, 3) == (cp // 16) * 5 * ((dc + 15) // 16) * 1024 + ((dc + 15) // 16) * 64 + image

@@ -25,8 +25,32 @@ BUDGET = {"f32": 0.002, "bf16": 0.01, "f16": 0.005}
 # MI355X over both sizes and both forms of the step (bf16 6.57e-3, per-op at 339 x 510; f16 7.81e-4, fused at 339 x 510); the
 # result is deterministic, the margin is for other content.  Both are below EFDN's 1.5e-2 / 2.5e-3
 MAX_REL = {"f32": 2e-5, "bf16": 1.32e-2, "f16": 1.57e-3}
-CMID = COUT = 20
 SIZES = [(15, 15), (16, 17), (33, 18), (40, 52)]      # a lone partial tile; one column / one row spilling into a second tile; interior tiles
+# (cin, cmid, cout, res).  BMDN's own widths (the first two), then the smallest set that reaches every residue of the kernel's pad-slot mask
+# (keep = cin - (round_up(cin, 8) - 8) in 1 .. 7), both chunk counts of `in` and both ends of every range esr_distill_step_supported admits
+BMDN_WIDTHS = [(40, 20, 20, False), (20, 20, 20, True)]
+NEW_WIDTHS = [(17, 17, 17, True),       # keep = 1, the lower end of every range
+              (27, 32, 27, True),       # keep = 3
+              (32, 25, 32, True),       # the upper end of the residual form
+              (18, 24, 31, False),      # keep = 2
+              (22, 32, 17, False),      # keep = 6
+              (31, 17, 32, False),      # keep = 7
+              (33, 17, 25, False),      # three chunks, keep = 1
+              (45, 32, 24, False),      # keep = 5
+              (48, 25, 32, False)]      # the upper end of cin
+
+
+def _widths(extra=None, fmt="{0}-{3}"):
+    """the widths as parameters: BMDN's two under the ids they always had, the new ones spelled out; `extra(cin)`: more values per case"""
+    ps = []
+    for i, wd in enumerate(BMDN_WIDTHS + NEW_WIDTHS):
+        vals = wd + (tuple(extra(wd[0])) if extra else ())
+        ps.append(pytest.param(*vals, id=(fmt.format(*vals) if i < len(BMDN_WIDTHS) else "-".join(str(v) for v in vals))))
+    return ps
+
+
+def _r8(c):
+    return (c + 7) // 8 * 8
 
 
 def _tol(ref, dt):
@@ -38,12 +62,13 @@ def _tol(ref, dt):
 _cases = {}
 
 
-def _case(store, cin, hw, n=2, bd=None):
+def _case(store, cin, hw, n=2, bd=None, cmid=20, cout=20):
     """inputs rounded to the storage type, weights, the blobs' effective weights -- computed once per case and left unchanged"""
-    key = (store, cin, hw, n, bd)
+    CMID, COUT = cmid, cout
+    key = (store, cin, cmid, cout, hw, n, bd)
     if key not in _cases:
         from ntire2022_esr_amd.engine import distill_cin_map, pack_conv_s16, pack_distill_s16, unpack_conv_s16
-        g = torch.Generator().manual_seed(1000 * cin + 10 * hw[0] + hw[1] + (store == "f16"))
+        g = torch.Generator().manual_seed(1000 * cin + 10 * hw[0] + hw[1] + (store == "f16") + 100000 * ((cmid, cout) != (20, 20)) * (32 * cmid + cout))
         x = torch.randn(n, hw[0], hw[1], cin, generator=g).to(DT[store])
         w_d, b_d = torch.randn(CMID, cin, 1, 1, generator=g) * 0.15, torch.randn(CMID, generator=g) * 0.2
         w_r, b_r = torch.randn(COUT, cin, 3, 3, generator=g) * 0.05, torch.randn(COUT, generator=g) * 0.1
@@ -80,26 +105,34 @@ def _run(c, res, pitch=None, **kw):
     return d.cpu(), y.cpu()
 
 
+# BMDN's widths at every size, the new ones at the two sizes with a ragged second tile in one direction each
+STEP_CASES = [pytest.param(hw, *wd, id=f"hw{i}-{wd[0]}-{wd[3]}") for wd in BMDN_WIDTHS for i, hw in enumerate(SIZES)] + \
+             [pytest.param(hw, *wd, id=f"{hw[0]}x{hw[1]}-" + "-".join(str(v) for v in wd)) for wd in NEW_WIDTHS for hw in [(16, 17), (33, 18)]]
+
+
 @pytest.mark.parametrize("store", ["bf16", "f16"])
-@pytest.mark.parametrize("cin,res", [(40, False), (20, True)])
-@pytest.mark.parametrize("hw", SIZES)
-def test_step_matches_fp64_restatement(store, cin, res, hw):
+@pytest.mark.parametrize("hw,cin,CMID,COUT,res", STEP_CASES)
+def test_step_matches_fp64_restatement(store, hw, cin, CMID, COUT, res):
     from ntire2022_esr_amd import ops, _lib as L
-    c = _case(store, cin, hw)
+    c = _case(store, cin, hw, cmid=CMID, cout=COUT)
     dt = DT[store]
     n = c["x"].shape[0]
     # both outputs into sentinel-filled tensors of pitch 32, so that the pad channels show what the launch leaves there
     mk = lambda: torch.full((n, hw[0], hw[1], 32), 7.0, dtype=dt, device=DEV)
-    d, y = _run(c, res, d_out=mk(), out=mk())
+    with ops.kernel_trace() as names:
+        d, y = _run(c, res, d_out=mk(), out=mk())
+    tf = {True: "true", False: "false"}
+    assert len(names) == 1 and names[0].startswith(f"distill_step_kernel<{tf[store == 'bf16']}, {(cin + 15) // 16}, {tf[res]}>"), names
     ref_d = _ref_d(c)
     got_d = d[..., :CMID].permute(0, 3, 1, 2).double()
     err_d = (got_d - ref_d).abs()
-    print(f"step {store} cin={cin} {hw}: max|d - ref| = {float(err_d.max()):.3e}, ", end="")
+    print(f"step {store} cin={cin} cmid={CMID} cout={COUT} {hw}: max|d - ref| = {float(err_d.max()):.3e} "
+          f"({float((err_d / _tol(ref_d, dt)).max()):.3f} of the bound), ", end="")
     assert int((err_d > _tol(ref_d, dt)).sum()) == 0, float(err_d.max())
     ref_y = _ref_out(c, d[..., :CMID].permute(0, 3, 1, 2), res)
     got_y = y[..., :COUT].permute(0, 3, 1, 2).double()
     err_y = (got_y - ref_y).abs()
-    print(f"max|out - ref| = {float(err_y.max()):.3e}")
+    print(f"max|out - ref| = {float(err_y.max()):.3e} ({float((err_y / _tol(ref_y, dt)).max()):.3f} of the bound)")
     assert int((err_y > _tol(ref_y, dt)).sum()) == 0, float(err_y.max())
     # pad channels: what ops.conv2d leaves in an out0 of the same view (zeros up to the 16-byte granule, nothing beyond)
     xp = F.pad(c["x"], (0, (cin + 7) // 8 * 8 - cin)).contiguous().to(DEV)
@@ -108,16 +141,17 @@ def test_step_matches_fp64_restatement(store, cin, res, hw):
     py = ops.conv2d(xp, w_r, b_r, act=L.ACT_RELU, cin=cin, out=mk()).cpu()
     assert torch.equal(d[..., CMID:].view(torch.int16), pd[..., CMID:].view(torch.int16))
     assert torch.equal(y[..., COUT:].view(torch.int16), py[..., COUT:].view(torch.int16))
-    assert torch.all(d[..., CMID:24] == 0) and torch.all(d[..., 24:] == 7.0)
+    assert torch.all(d[..., CMID:_r8(CMID)] == 0) and torch.all(d[..., _r8(CMID):] == 7.0)
+    assert torch.all(y[..., COUT:_r8(COUT)] == 0) and torch.all(y[..., _r8(COUT):] == 7.0)
 
 
 @pytest.mark.parametrize("store", ["bf16", "f16"])
-@pytest.mark.parametrize("cin,res", [(40, False), (20, True)])
-def test_d_is_zero_padded_not_bias_padded(store, cin, res):
+@pytest.mark.parametrize("cin,CMID,COUT,res", _widths())
+def test_d_is_zero_padded_not_bias_padded(store, cin, CMID, COUT, res):
     """The reference zero-pads d: a halo pixel outside the image is 0, not relu(b_d).  With b_d = 3 the two readings differ at the border by
     far more than the bound, which the CPU-side sanity assertion shows before the kernel is held to the right one."""
     hw = (33, 18)
-    c = _case(store, cin, hw, bd=3.0)
+    c = _case(store, cin, hw, bd=3.0, cmid=CMID, cout=COUT)
     dt = DT[store]
     d, y = _run(c, res)
     ref_d = _ref_d(c)
@@ -138,12 +172,18 @@ def test_d_is_zero_padded_not_bias_padded(store, cin, res):
     assert int((err > _tol(ref, dt)).sum()) == 0, float(err.max())
 
 
+# BMDN's widths at the pitch they always had; each new width at the tight pitch round_up(cin, 8) -- NaNs in the last piece's pad slots and
+# right behind the tensor -- and at round_up(cin, 16), where cin <= 8 mod 16 puts a whole 16-byte piece of NaNs behind the last one moved
+NAN_CASES = [pytest.param(40, 20, 20, False, 48, id="40-False-48"), pytest.param(20, 20, 20, True, 32, id="20-True-32")] + \
+            [pytest.param(*wd, p, id="-".join(str(v) for v in wd + (p,))) for wd in NEW_WIDTHS for p in sorted({_r8(wd[0]), (wd[0] + 15) // 16 * 16})]
+
+
 @pytest.mark.parametrize("store", ["bf16", "f16"])
-@pytest.mark.parametrize("cin,res,pitch", [(40, False, 48), (20, True, 32)])
-def test_nothing_beyond_cin_or_behind_the_tensor_is_read(store, cin, res, pitch):
+@pytest.mark.parametrize("cin,CMID,COUT,res,pitch", NAN_CASES)
+def test_nothing_beyond_cin_or_behind_the_tensor_is_read(store, cin, CMID, COUT, res, pitch):
     from ntire2022_esr_amd import ops
     hw = (33, 18)
-    c = _case(store, cin, hw)
+    c = _case(store, cin, hw, cmid=CMID, cout=COUT)
     dt = DT[store]
     n = c["x"].shape[0]
     clean_d, clean_y = _run(c, res, pitch=pitch)
@@ -156,12 +196,13 @@ def test_nothing_beyond_cin_or_behind_the_tensor_is_read(store, cin, res, pitch)
     torch.cuda.synchronize()
     assert torch.equal(d.cpu().view(torch.int16), clean_d.view(torch.int16))
     assert torch.equal(y.cpu().view(torch.int16), clean_y.view(torch.int16))
+    assert bool(torch.isfinite(d.float()).all()) and bool(torch.isfinite(y.float()).all())
 
 
 @pytest.mark.parametrize("store", ["bf16", "f16"])
 @pytest.mark.parametrize("cin,res", [(40, False), (20, True)])
 def test_nothing_outside_the_views_is_written(store, cin, res):
-    hw = (16, 17)
+    hw = (16, 17)                             # (BMDN's widths, cmid = cout = 20: the views' geometry, not the widths, is the subject)
     c = _case(store, cin, hw)
     dt = DT[store]
     n = c["x"].shape[0]

@@ -489,10 +489,22 @@ def test_persistent_64_channel_kernels(store, n, h, w):
 def test_rfdb_and_esdb_tails(store, n, h, w, esdb):
     """rfdb_tail_kernel (ABI v12): c4 -> cat(d1, d2, d3, r4) -> c5 -> esa.conv1 in one launch; RFDB over 64 physical channels, ESDB over 48 with
     the border table and GELU.  v goes into a slice of a wider buffer, the three distilled tensors are one planar [3, N, H, W, 32] input."""
+    _tails(store, n, h, w, esdb, (48, 24, 16) if esdb else (50, 25, 12))
+
+
+@pytest.mark.parametrize("store", ["bf16", "f16"])
+@pytest.mark.parametrize("esdb", [False, True])
+def test_rfdb_and_esdb_tails_at_their_smallest_widths(store, esdb):
+    """... at the lower end of every channel range rfdb_tail_takes admits, on the smallest shape the kernel takes (256 tiles, a ragged right edge)"""
+    _tails(store, 4, 128, 120, esdb, (33, 17, 1) if esdb else (49, 17, 1))
+
+
+def _tails(store, n, h, w, esdb, widths):
     from ntire2022_esr_amd import _lib as L, ops
     from ntire2022_esr_amd.engine import pack_conv_s16, pack_post_s16, pack_tail_s16
     dt = DT[store]
-    nf, dc, f, cp = (48, 24, 16, 48) if esdb else (50, 25, 12, 64)
+    nf, dc, f = widths
+    cp = 48 if esdb else 64
     g = _gen(n, h, w, nf)
     r3 = _core(n, h, w, nf, cp, dt, g)
     ds = F.pad(torch.randn(3, n, h, w, dc, generator=g), (0, 32 - dc)).to(dt)
@@ -534,16 +546,24 @@ def test_rfdb_and_esdb_tails(store, n, h, w, esdb):
 def test_rlfb_chain(store, n, h, w):
     """rlfb_chain_kernel: three 3x3s + two 1x1s in one launch; v and c1 into buffers wider than their channels.  The strip is 5 x 3:
     esr_conv_chain_supported refuses h < 4, so 1 x 90 is not a shape of this kernel"""
+    _chain(store, n, h, w, 46, 48, 16)
+
+
+@pytest.mark.parametrize("store", ["bf16", "f16"])
+def test_rlfb_chain_at_its_smallest_widths(store):
+    _chain(store, 2, 23, 37, 33, 33, 1)
+
+
+def _chain(store, n, h, w, nf, mf, f):
     from ntire2022_esr_amd import ops
-    g = _gen(n, h, w, 46)
-    nf, mf, f = 46, 48, 16
+    g = _gen(n, h, w, nf)
     ws = [torch.randn(mf, nf, 3, 3, generator=g) * 0.06, torch.randn(mf, mf, 3, 3, generator=g) * 0.06, torch.randn(nf, mf, 3, 3, generator=g) * 0.06]
     bs = [torch.randn(c, generator=g) * 0.1 for c in (mf, mf, nf)]
     w5, b5, w1, b1 = torch.randn(nf, nf, generator=g) * 0.15, torch.randn(nf, generator=g) * 0.1, torch.randn(f, nf, generator=g) * 0.15, torch.randn(f, generator=g) * 0.1
     x = _core(n, h, w, nf, 48, DT[store], g)
 
     def make(variant):
-        outs = {"v": ((n, h, w, 64), DT[store], (-1, 0, 48)), "c1": ((n, h, w, 24), DT[store], (-1, 0, 16))}
+        outs = {"v": ((n, h, w, 64), DT[store], (-1, 0, 48)), "c1": ((n, h, w, 24), DT[store], (-1, 0, _up(f, 8)))}
         return Case({"x": x}, outs, lambda t: ops.conv_chain(t["x"], ws, bs, w5, b5, w1, b1, cin=nf, v_out=t["v"], c1_out=t["c1"]), r"rlfb_chain_kernel<")
     _property(make)
 
@@ -552,9 +572,57 @@ def test_rlfb_chain(store, n, h, w):
 @pytest.mark.parametrize("n,h,w", [(2, 23, 37), (1, 31, 33), (1, 1, 90), (2, 5, 3)])
 def test_hfab(store, n, h, w):
     """hfab_kernel (ESR_RES_GATE chain): nf = 50 in pitch 56; channels of `in` at and beyond cin are never read (foreign noise there)"""
+    _hfab(store, n, h, w, 50, 16, 56)
+
+
+@pytest.mark.parametrize("store", ["bf16", "f16"])
+def test_hfab_at_its_smallest_widths(store):
+    """cin = 33 in pitch 40 (three chunks, one channel of the last 16-byte piece kept, seven slots of foreign noise cleared), cmid = 1"""
+    _hfab(store, 2, 23, 37, 33, 1, 40)
+
+
+@pytest.mark.parametrize("store", ["bf16", "f16"])
+def test_distill_step_at_its_smallest_widths(store):
+    """distill_step_kernel at cin = cmid = cout = 17 (the residual form): `in` in pitch 24 with foreign noise in its seven pad slots, d and out
+    into slices of wider buffers"""
+    from ntire2022_esr_amd import ops
+    n, h, w, c = 2, 23, 37, 17
+    g = _gen(n, h, w, c)
+    wd, bd = torch.randn(c, c, 1, 1, generator=g) * 0.15, torch.randn(c, generator=g) * 0.2
+    wr, br = torch.randn(c, c, 3, 3, generator=g) * 0.05, torch.randn(c, generator=g) * 0.1
+    wb, bb = torch.randn(c, c, 3, 3, generator=g) * 0.05, torch.randn(c, generator=g) * 0.1
+    x = torch.randn(n, h, w, c, generator=g).to(DT[store])
+
+    def make(variant):
+        outs = {"d": ((n, h, w, 40), DT[store], (-1, 8, 24)), "y": ((n, h, w, 32), DT[store], (-1, 0, 24))}
+        return Case({"x": _widen(x, 24, 0, variant, 7)}, outs,
+                    lambda t: ops.distill_step(t["x"], wd, bd, wr, br, wb, bb, res=True, cin=c, d_out=t["d"], d_coff=8, out=t["y"]),
+                    r"distill_step_kernel<(true|false), 2, true>")
+    _property(make)
+
+
+@pytest.mark.parametrize("store", ["bf16", "f16"])
+def test_resblock_head_at_its_smallest_width(store):
+    """resblock_head_kernel with one esa.conv1 channel (c1: one 16-byte granule stored), with g"""
+    from ntire2022_esr_amd import ops
+    n, h, w, c = 2, 23, 37, 32
+    g = _gen(n, h, w, c)
+    w1, b1 = torch.randn(c, c, 3, 3, generator=g) * 0.06, torch.randn(c, generator=g) * 0.1
+    w2, b2 = torch.randn(c, c, 3, 3, generator=g) * 0.06, torch.randn(c, generator=g) * 0.1
+    wc, bc = torch.randn(1, c, 1, 1, generator=g) * 0.15, torch.randn(1, generator=g) * 0.2
+    x, gg = torch.randn(n, h, w, c, generator=g).to(DT[store]), (torch.randn(n, h, w, c, generator=g) * 0.5).to(DT[store])
+
+    def make(variant):
+        outs = {"xs": ((n, h, w, 40), DT[store], (-1, 8, 32)), "u": ((n, h, w, 32), DT[store], "all"), "c1": ((n, h, w, 16), DT[store], (-1, 0, 8))}
+        return Case({"x": _widen(x, 48, 8, variant, 3), "g": gg}, outs,
+                    lambda t: ops.resblock_head(t["x"], w1, b1, w2, b2, wc, bc, g=t["g"], in_coff=8, x_out=t["xs"], x_coff=8, u_out=t["u"], c1_out=t["c1"]),
+                    r"resblock_head_kernel<(true|false), true>")
+    _property(make)
+
+
+def _hfab(store, n, h, w, cin, cmid, pitch):
     from ntire2022_esr_amd import _lib as L, ops
-    g = _gen(n, h, w, 50)
-    cin, cmid, pitch = 50, 16, 56
+    g = _gen(n, h, w, cin)
     ws = [torch.randn(cmid, cin, 3, 3, generator=g) * 0.1, torch.randn(cmid, cmid, 3, 3, generator=g) * 0.1, torch.randn(cmid, cmid, 3, 3, generator=g) * 0.1,
           torch.randn(cin, cmid, 3, 3, generator=g) * 0.1]
     bs = [torch.randn(c, generator=g) * 0.1 for c in (cmid, cmid, cmid, cin)]

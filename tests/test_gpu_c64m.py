@@ -22,6 +22,10 @@ def _ref_conv(x, weff, b, res_in, slope=0.05):
     return F.leaky_relu(conv, slope)
 
 
+def _tf(compute):
+    return "true" if compute == "bf16" else "false"
+
+
 def _tol(ref, dt, extra=0.0):
     eps = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
     return ref.abs() * eps * 1.01 + 3e-5 * max(1.0, float(ref.abs().max())) + extra
@@ -29,7 +33,9 @@ def _tol(ref, dt, extra=0.0):
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
 @pytest.mark.parametrize("n,c,hw,res_in", [(1, 64, (270, 480), True), (1, 50, (339, 510), True), (3, 64, (160, 144), False), (2, 50, (250, 203), True),
-                                           (32, 50, (64, 64), True)])
+                                           (32, 50, (64, 64), True),
+                                           # other widths of 49 .. 64 at the kernel's threshold: 256 tiles of 16 x 16, a ragged right edge
+                                           (4, 49, (128, 120), True), (4, 57, (128, 120), False), (4, 63, (128, 120), True)])
 def test_conv64m_plain_matches_fp64_reference(compute, n, c, hw, res_in):
     from ntire2022_esr_amd import ops, _lib as L
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
@@ -44,15 +50,19 @@ def test_conv64m_plain_matches_fp64_reference(compute, n, c, hw, res_in):
     if res_in:
         kw.update(res=x, res_mode=L.RES_PRE_ACT)
     for _ in range(3):                  # a race would not show every time
-        y = ops.conv2d(x, w, b, **kw)
+        with ops.kernel_trace() as names:
+            y = ops.conv2d(x, w, b, **kw)
+        assert len(names) == 1 and names[0].startswith(f"conv64m_kernel<{_tf(compute)}, false, false, 4, false>"), names
         got = y.permute(0, 3, 1, 2)[:, :c].double()
         bad = int(((got - ref).abs() > _tol(ref, dt)).sum())
         assert bad == 0, (bad, float((got - ref).abs().max()))
+    print(f"conv64m {compute} c={c} {n}x{hw}: max|got - ref| = {float((got - ref).abs().max()):.3e} ({float(((got - ref).abs() / _tol(ref, dt)).max()):.3f} of the bound)")
     assert torch.all(y[..., c:(c + 7) // 8 * 8] == 0)        # pad channels of the last 16-byte granule are zeros
 
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("n,c,pc,hw,res_in", [(1, 50, 25, (339, 510), True), (8, 50, 25, (128, 128), True), (9, 64, 32, (100, 77), True), (5, 50, 25, (64, 250), False)])
+@pytest.mark.parametrize("n,c,pc,hw,res_in", [(1, 50, 25, (339, 510), True), (8, 50, 25, (128, 128), True), (9, 64, 32, (100, 77), True), (5, 50, 25, (64, 250), False),
+                                              (4, 49, 17, (128, 120), True), (4, 57, 24, (128, 120), True), (4, 63, 32, (128, 120), False)])      # other widths
 def test_conv64m_post_matches_fp64_reference(compute, n, c, pc, hw, res_in):
     from ntire2022_esr_amd import ops, _lib as L
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
@@ -68,7 +78,9 @@ def test_conv64m_post_matches_fp64_reference(compute, n, c, pc, hw, res_in):
     if res_in:
         kw.update(res=x, res_mode=L.RES_PRE_ACT)
     for _ in range(2):
-        y, yp = ops.conv2d(x, w, b, **kw)
+        with ops.kernel_trace() as names:
+            y, yp = ops.conv2d(x, w, b, **kw)
+        assert len(names) == 1 and names[0].startswith(f"conv64m_kernel<{_tf(compute)}, true, false, 4, false>"), names
         got = y.permute(0, 3, 1, 2)[:, :c].double()
         bad = int(((got - ref).abs() > _tol(ref, dt)).sum())
         assert bad == 0, (bad, float((got - ref).abs().max()))
@@ -84,6 +96,9 @@ def test_conv64m_post_matches_fp64_reference(compute, n, c, pc, hw, res_in):
         gp = yp.permute(0, 3, 1, 2)[:, :pc].double()
         badp = int(((gp - pref).abs() > _tol(pref, dt, extra)).sum())
         assert badp == 0, (badp, float((gp - pref).abs().max()))
+    print(f"conv64m + post {compute} c={c} pc={pc} {n}x{hw}: max|y - ref| = {float((got - ref).abs().max()):.3e} "
+          f"({float(((got - ref).abs() / _tol(ref, dt)).max()):.3f} of the bound), max|post - ref| = {float((gp - pref).abs().max()):.3e} "
+          f"({float(((gp - pref).abs() / _tol(pref, dt, extra)).max()):.3f})")
     assert torch.all(yp[..., pc:] == 0) and torch.all(y[..., c:(c + 7) // 8 * 8] == 0)
 
 
@@ -114,7 +129,12 @@ def _hilo(w, dt):
 
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("n,hw,nf,dc,f", [(1, (339, 510), 50, 25, 16), (4, (128, 144), 50, 25, 16), (2, (250, 203), 64, 32, 16), (32, (64, 64), 50, 25, 12)])
+@pytest.mark.parametrize("n,hw,nf,dc,f", [(1, (339, 510), 50, 25, 16), (4, (128, 144), 50, 25, 16), (2, (250, 203), 64, 32, 16), (32, (64, 64), 50, 25, 12),
+                                          # other widths at the kernel's threshold (256 tiles of 16 x 16, a ragged right edge): both ends of nf in 49 .. 64,
+                                          # of dc in 17 .. 32 and of f in 1 .. 16, and widths at / one past a 16-byte granule
+                                          (4, (128, 120), 49, 17, 1), (4, (128, 120), 57, 24, 8), (4, (128, 120), 56, 31, 9), (4, (128, 120), 63, 32, 16),
+                                          # one output tile: esr_pack_conv_s16 emits no 32x32x16 image for it -- refused, nothing is launched
+                                          (4, (128, 120), 50, 16, 16)])
 def test_rfdb_tail_matches_fp64_reference(compute, n, hw, nf, dc, f):
     """rfdb_tail_kernel (ABI v12, esr_conv_desc.tail_* in 16-bit storage): r4 = round(lrelu(c4(r3))), v = c5 . [d1 d2 d3 r4], c1 = conv1 . v in one
     launch (rfdn_baseline/block.py:161-164, :117), against fp64 on the same 16-bit inputs and the blobs' effective weights."""
@@ -149,8 +169,15 @@ def test_rfdb_tail_matches_fp64_reference(compute, n, hw, nf, dc, f):
     d.post_wpacked = ctypes.c_void_p(blobc.data_ptr())
     d.post_out = L.View(ctypes.c_void_p(c1.data_ptr()), 16, 0)
     d.post_cout, d.post_act = f, L.ACT_NONE
-    assert L.lib().esr_conv_tail_supported(ctypes.byref(d)) == 1
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if dc <= 16:
+        assert L.lib().esr_conv_tail_supported(ctypes.byref(d)) == 0
+        assert L.STATUS[L.lib().esr_conv2d_f32(ctypes.byref(d), st)] == "ESR_ERR_UNSUPPORTED"
+        torch.cuda.synchronize()
+        assert torch.all(v == 7.0) and torch.all(c1 == 7.0)
+        return
+    assert L.lib().esr_conv_tail_supported(ctypes.byref(d)) == 1
+    from ntire2022_esr_amd import ops
     # fp64 reference
     x = r3[..., :nf].permute(0, 3, 1, 2).double()
     r4 = F.leaky_relu(F.conv2d(x, w4e.double().to(DEV), b4.double().to(DEV), padding=1), 0.05)
@@ -158,7 +185,9 @@ def test_rfdb_tail_matches_fp64_reference(compute, n, hw, nf, dc, f):
     cat = torch.cat([ds[j, ..., :dc].permute(0, 3, 1, 2).double() for j in range(3)] + [r4q], 1)
     vref = torch.einsum("oc,nchw->nohw", _hilo(w5, dt).to(DEV), cat) + b5.double().to(DEV)[None, :, None, None]
     for _ in range(3):
-        L.check(L.lib().esr_conv2d_f32(ctypes.byref(d), st), "tail")
+        with ops.kernel_trace() as names:
+            ops._launch("esr_conv2d_f32", "tail", d, st.value, L.OP_CONV, "conv")
+        assert len(names) == 1 and names[0].startswith(f"rfdb_tail_kernel<{_tf(compute)}, 4, false>"), names
         torch.cuda.synchronize()
         got = v.permute(0, 3, 1, 2)[:, :nf].double()
         # r4 sits on rounding boundaries now and then: a flipped r4 value moves v by |w5| x one step of r4
@@ -172,6 +201,9 @@ def test_rfdb_tail_matches_fp64_reference(compute, n, hw, nf, dc, f):
         gc = c1.permute(0, 3, 1, 2)[:, :f].double()
         badc = int(((gc - cref).abs() > _tol(cref, dt, 2e-4 + extra * float(wc.abs().max()) * 8)).sum())
         assert badc == 0, (badc, float((gc - cref).abs().max()))
+    print(f"rfdb tail {compute} ({nf}, {dc}, {f}) {n}x{hw}: max|v - ref| = {float((got - vref).abs().max()):.3e} "
+          f"({float(((got - vref).abs() / _tol(vref, dt, extra)).max()):.3f} of the bound), max|c1 - ref| = {float((gc - cref).abs().max()):.3e} "
+          f"({float(((gc - cref).abs() / _tol(cref, dt, 2e-4 + extra * float(wc.abs().max()) * 8)).max()):.3f})")
     assert torch.all(v[..., (nf + 7) // 8 * 8:] == 7.0) and torch.all(v[..., nf:(nf + 7) // 8 * 8] == 0)
     assert torch.all(c1[..., f:(f + 7) // 8 * 8] == 0)
 
@@ -204,7 +236,8 @@ def test_rfdn_with_and_without_the_fused_block_tail(compute):
     assert torch.equal(m(x), y1)
 
 
-@pytest.mark.parametrize("n,c,hw,act", [(1, 50, (339, 510), 0), (2, 64, (250, 203), 1), (32, 50, (64, 64), 0), (5, 50, (100, 177), 0)])
+@pytest.mark.parametrize("n,c,hw,act", [(1, 50, (339, 510), 0), (2, 64, (250, 203), 1), (32, 50, (64, 64), 0), (5, 50, (100, 177), 0),
+                                        (4, 49, (128, 120), 0), (4, 57, (128, 120), 1), (4, 63, (128, 120), 0)])      # other widths, 256 tiles
 def test_conv64m_hilo_lr_conv_matches_fp64_reference(n, c, hw, act):
     """conv64m_kernel<bf16, plain, HL>: the LR conv behind the long skip on hi + lo pairs (RFDN: LR_conv(out_B) + out_fea, rfdn_baseline/RFDN.py:50-52)
     -- the residual pair of ANOTHER tensor as eight selection MFMAs in front of the next row pair's stream, the fp32 result stored as a hi + lo
@@ -235,7 +268,9 @@ def test_conv64m_hilo_lr_conv_matches_fp64_reference(n, c, hw, act):
     ref = F.leaky_relu(conv, 0.05) if act == 1 else conv
     tol = ref.abs() * 2.0 ** -15 + 3e-5 * max(1.0, float(ref.abs().max()))
     for _ in range(2):
-        y = ops.conv2d(xin, w, b, res=rin, **kw)
+        with ops.kernel_trace() as names:
+            y = ops.conv2d(xin, w, b, res=rin, **kw)
+        assert len(names) == 1 and names[0].startswith("conv64m_kernel<true, false, true, 4, false>"), names
         torch.cuda.synchronize()
         assert tuple(y.shape) == (2, n, *hw, cp)
         got = (y[0].double() + y[1].double()).permute(0, 3, 1, 2)[:, :c]
@@ -250,7 +285,8 @@ def test_conv64m_hilo_lr_conv_matches_fp64_reference(n, c, hw, act):
 
 
 @pytest.mark.parametrize("compute", ["f16", "bf16"])
-@pytest.mark.parametrize("n,hw,C,dc,f", [(1, (339, 510), 48, 24, 12), (4, (128, 160), 48, 24, 16), (2, (250, 203), 40, 20, 10)])
+@pytest.mark.parametrize("n,hw,C,dc,f", [(1, (339, 510), 48, 24, 12), (4, (128, 160), 48, 24, 16), (2, (250, 203), 40, 20, 10),
+                                         (4, (128, 120), 33, 17, 1), (4, (128, 120), 41, 31, 8), (4, (128, 120), 47, 32, 9)])      # other widths, 256 tiles
 def test_esdb_tail_matches_fp64_reference(compute, n, hw, C, dc, f):
     """rfdb_tail_kernel<.., 3, true>: ESDB's tail (team18_bsrn.py:165-171, :109) -- c4 = BSConvU as a dense 3x3 over 48 physical channels with
     the merged pointwise bias's border table and GELU, r4 never stored, v = c5 . [d1 d2 d3 r4], c1_ = esa.conv1 . v -- against fp64 on the
@@ -307,8 +343,11 @@ def test_esdb_tail_matches_fp64_reference(compute, n, hw, C, dc, f):
     step = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
     # a flipped rounding of r4 / the polynomial's 1.3e-4 move v by |w5| x that much
     extra = float(w5.abs().max()) * (1.2 * step * float(r4.abs().max()) + 4 * 1.3e-4)
+    from ntire2022_esr_amd import ops
     for _ in range(2):
-        L.check(L.lib().esr_conv2d_f32(ctypes.byref(d), st), "tail")
+        with ops.kernel_trace() as names:
+            ops._launch("esr_conv2d_f32", "tail", d, st.value, L.OP_CONV, "conv")
+        assert len(names) == 1 and names[0].startswith(f"rfdb_tail_kernel<{_tf(compute)}, 3, true>"), names
         torch.cuda.synchronize()
         got = v.permute(0, 3, 1, 2)[:, :C].double()
         bad = int(((got - vref).abs() > _tol(vref, dt, extra)).sum())
@@ -318,6 +357,9 @@ def test_esdb_tail_matches_fp64_reference(compute, n, hw, C, dc, f):
         gc = c1.permute(0, 3, 1, 2)[:, :f].double()
         badc = int(((gc - cref).abs() > _tol(cref, dt, 2e-4 + extra * float(wc.abs().max()) * 8)).sum())
         assert badc == 0, (badc, float((gc - cref).abs().max()))
+    print(f"esdb tail {compute} ({C}, {dc}, {f}) {n}x{hw}: max|v - ref| = {float((got - vref).abs().max()):.3e} "
+          f"({float(((got - vref).abs() / _tol(vref, dt, extra)).max()):.3f} of the bound), max|c1 - ref| = {float((gc - cref).abs().max()):.3e} "
+          f"({float(((gc - cref).abs() / _tol(cref, dt, 2e-4 + extra * float(wc.abs().max()) * 8)).max()):.3f})")
     assert torch.all(v[..., (C + 7) // 8 * 8:] == 7.0) and torch.all(v[..., C:(C + 7) // 8 * 8] == 0)
     assert torch.all(c1[..., f:(f + 7) // 8 * 8] == 0)
 
@@ -351,8 +393,11 @@ def test_bsrn_with_and_without_the_fused_block_tail():
 
 
 @pytest.mark.parametrize("compute,post", [("f16", True), ("f16", False), ("bf16", False)])
-@pytest.mark.parametrize("n,c,hw", [(1, 48, (270, 480)), (6, 40, (144, 160)), (3, 48, (250, 203))])
-def test_esdb_r_on_conv64m_matches_fp64_reference(compute, post, n, c, hw):
+@pytest.mark.parametrize("n,c,hw,pc", [pytest.param(1, 48, (270, 480), 24, id="1-48-hw0"), pytest.param(6, 40, (144, 160), 20, id="6-40-hw1"),
+                                       pytest.param(3, 48, (250, 203), 24, id="3-48-hw2"),
+                                       # other widths: c over 33 .. 48, the post 1x1's two output tiles over 17 .. 32
+                                       (8, 33, (128, 128), 17), (8, 41, (128, 128), 24), (8, 47, (128, 128), 32)])
+def test_esdb_r_on_conv64m_matches_fp64_reference(compute, post, n, c, hw, pc):
     """conv64m_kernel<.., 3, true>: ESDB's c{j}_r (team18_bsrn.py:150-163) -- gelu(dense BSConvU(x) + table row + x) over 48 physical channels,
     plain or (fp16) with the next distillation Linear + GELU behind it -- against fp64 on the same 16-bit inputs, the blob's effective weights and
     the exact GELU (the kernel's polynomial: |error| <= 1.3e-4)."""
@@ -360,7 +405,6 @@ def test_esdb_r_on_conv64m_matches_fp64_reference(compute, post, n, c, hw):
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
     dt = DT[compute]
     g = torch.Generator().manual_seed(n + c + hw[0] + post)
-    pc = c // 2
     x = F.pad(torch.randn(n, *hw, c, generator=g), (0, 48 - c)).to(dt).to(DEV)
     w, b = torch.randn(c, c, 3, 3, generator=g) * 0.1, torch.randn(c, generator=g)
     wp, bp = torch.randn(pc, c, generator=g) * 0.2, torch.randn(pc, generator=g)
@@ -384,7 +428,9 @@ def test_esdb_r_on_conv64m_matches_fp64_reference(compute, post, n, c, hw):
     pre = F.conv2d(xd, weff.double().to(DEV), b.double().to(DEV), padding=1) + table.double()[mask][..., :c].permute(2, 0, 1)[None] + xd
     ref = F.gelu(pre)
     for _ in range(2):
-        out = ops.conv2d(x, w, b, **kw)
+        with ops.kernel_trace() as names:
+            out = ops.conv2d(x, w, b, **kw)
+        assert len(names) == 1 and names[0].startswith(f"conv64m_kernel<{_tf(compute)}, {'true' if post else 'false'}, false, 3, true>"), names
         torch.cuda.synchronize()
         y, yp = out if post else (out, None)
         got = y.permute(0, 3, 1, 2)[:, :c].double()

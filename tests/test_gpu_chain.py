@@ -22,6 +22,12 @@ def _weights(seed, nf=46, mf=48, f=16, scale=0.06):
     return ws, bs, w5, b5, w1, b1
 
 
+# (nf, mf, f): RLFN's own widths, then both ends of every range esr_conv_chain_supported admits (33 .. 48 for the block's and the middle
+# channels, 1 .. 16 for esa.conv1) and widths one past / one short of a 16-byte granule in between
+RLFN_WIDTHS = (46, 48, 16)
+NEW_WIDTHS = [(33, 33, 1), (41, 34, 8), (40, 47, 9), (48, 48, 16)]
+
+
 def _separate(x, ws, bs, w5, b5, w1, b1, nf):
     """the chain as the three launches of the unfused plan (conv48r / conv48rp / conv_s16 kernels, whichever the shape takes)"""
     from ntire2022_esr_amd import _lib as L, ops
@@ -47,37 +53,55 @@ def strip_groups(request):
         os.environ["ESR_CHAIN_G"] = old
 
 
+CHAIN_CASES = [pytest.param(*nhw, *RLFN_WIDTHS, id="-".join(str(v) for v in nhw)) for nhw in [
+    (1, 40, 56), (2, 23, 37), (1, 17, 15), (1, 64, 28), (3, 33, 29), (1, 5, 90), (1, 96, 61), (2, 50, 44), (1, 30, 133)]] + \
+    [pytest.param(*nhw, *wd, id="-".join(str(v) for v in nhw + wd)) for wd in NEW_WIDTHS for nhw in [(2, 23, 37), (1, 17, 15)]]
+
+
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("n,h,w", [(1, 40, 56), (2, 23, 37), (1, 17, 15), (1, 64, 28), (3, 33, 29), (1, 5, 90), (1, 96, 61), (2, 50, 44), (1, 30, 133)])
-def test_chain_equals_separate_launches(compute, n, h, w, strip_groups):
+@pytest.mark.parametrize("n,h,w,nf,mf,f", CHAIN_CASES)
+def test_chain_equals_separate_launches(compute, n, h, w, nf, mf, f, strip_groups):
     """ragged strips (w not a multiple of the strip width), one-strip and one-segment images, several jobs per block: v and c1 bit for bit"""
     from ntire2022_esr_amd import ops
     dt = DT[compute]
-    nf = 46
-    ws, bs, w5, b5, w1, b1 = _weights(n * 1000 + h + w)
+    ws, bs, w5, b5, w1, b1 = _weights(n * 1000 + h + w, nf, mf, f)
     g = torch.Generator().manual_seed(h * w)
     x = torch.zeros(n, h, w, 48)
     x[..., :nf] = torch.randn(n, h, w, nf, generator=g)
     x = x.to(dt).to(DEV)
-    v, c1 = ops.conv_chain(x, ws, bs, w5, b5, w1, b1, cin=nf)
+    with ops.kernel_trace() as names:
+        v, c1 = ops.conv_chain(x, ws, bs, w5, b5, w1, b1, cin=nf)
+    assert len(names) == 1 and names[0].startswith(f"rlfb_chain_kernel<{'true' if compute == 'bf16' else 'false'}, {strip_groups}>"), names
     rv, rc1 = _separate(x, ws, bs, w5, b5, w1, b1, nf)
     torch.cuda.synchronize()
-    assert v.shape == (n, h, w, 48) and c1.shape == (n, h, w, 16)
+    assert v.shape == (n, h, w, 48) and c1.shape == (n, h, w, (f + 7) // 8 * 8)
+    assert float(c1[..., f:].float().abs().max() if f % 8 else 0.0) == 0.0                          # c1's pad channels are zeros
     dv = (v[..., :nf].float() - rv[..., :nf].float()).abs().max().item()
     dc = (c1.float() - rc1.float()).abs().max().item()
     assert torch.equal(v[..., :nf], rv[..., :nf]) and torch.equal(c1, rc1), (dv, dc)
-    assert torch.isfinite(v.float()).all() and float(v[..., nf:].float().abs().max()) == 0.0        # pad channels stay zero
+    assert torch.isfinite(v.float()).all() and (nf == 48 or float(v[..., nf:].float().abs().max()) == 0.0)        # pad channels stay zero
 
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
 def test_chain_matches_fp64_reference(compute, strip_groups):
     """... and directly against ATen in fp64 on the blobs' effective weights (one rounding per stored tensor: t1, t2, v, c1)"""
+    _chain_against_fp64(compute, 1, 37, 45, *RLFN_WIDTHS)
+
+
+@pytest.mark.parametrize("compute", ["bf16", "f16"])
+@pytest.mark.parametrize("nf,mf,f", NEW_WIDTHS)
+@pytest.mark.parametrize("n,h,w", [(2, 23, 37), (1, 17, 15)])
+def test_chain_matches_fp64_reference_at_other_widths(compute, n, h, w, nf, mf, f, strip_groups):
+    """the same check (test_chain_matches_fp64_reference's, its bound unchanged: no width has a longer K than 48 . 9) at NEW_WIDTHS"""
+    _chain_against_fp64(compute, n, h, w, nf, mf, f)
+
+
+def _chain_against_fp64(compute, n, h, w, nf, mf, f):
     import torch.nn.functional as F
     from ntire2022_esr_amd import ops
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
     dt = DT[compute]
-    nf, n, h, w = 46, 1, 37, 45
-    ws, bs, w5, b5, w1, b1 = _weights(7)
+    ws, bs, w5, b5, w1, b1 = _weights(7, nf, mf, f)
     g = torch.Generator().manual_seed(3)
     x = torch.zeros(n, h, w, 48)
     x[..., :nf] = torch.randn(n, h, w, nf, generator=g)
@@ -96,10 +120,12 @@ def test_chain_matches_fp64_reference(compute, strip_groups):
     cr = F.conv2d(vr, w1.double()[:, :, None, None], b1.double())
     eps = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
     gv = v[..., :nf].float().cpu().permute(0, 3, 1, 2).double()
-    gc = c1.float().cpu().permute(0, 3, 1, 2).double()
+    gc = c1[..., :f].float().cpu().permute(0, 3, 1, 2).double()
     # the post 1x1s see u / v as hi + lo 16-bit parts and hi + lo weights: ~2^-16 (bf16) relative on top of the stored rounding
     for got, ref in ((gv, vr), (gc, cr)):
         tol = ref.abs() * eps * 1.05 + 4e-4 * float(ref.abs().max())
+        print(f"chain {compute} ({nf}, {mf}, {f}) {n}x{h}x{w}: max|got - ref| = {float((got - ref).abs().max()):.3e} "
+              f"({float(((got - ref).abs() / tol).max()):.3f} of the bound)")
         assert bool(((got - ref).abs() <= tol).all()), float(((got - ref).abs() - tol).max())
 
 

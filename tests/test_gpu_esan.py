@@ -32,6 +32,10 @@ C, FE = 32, 8
 # the smallest legal image (a lone partial tile); a tile exactly full; one pixel over a tile edge in both axes; several tiles with a partial
 # right and bottom one, in a batch
 SIZES = [(1, 15, 15), (1, 16, 16), (1, 17, 33), (2, 21, 40)]
+# (size, channels of esa.conv1): ESAN's 8 at every size under the ids they always had, then both ends of the range esr_resblock_head_supported
+# admits (1 .. 16) and one past a 16-byte granule, at the two sizes with more than one tile
+HEAD_CASES = [pytest.param(nhw, FE, id=f"nhw{i}") for i, nhw in enumerate(SIZES)] + \
+             [pytest.param(nhw, fe, id="x".join(str(v) for v in nhw) + f"-fe{fe}") for fe in (1, 9, 16) for nhw in SIZES[2:]]
 
 
 def _tol(ref, store):
@@ -42,9 +46,9 @@ def _tol(ref, store):
 _cases = {}
 
 
-def _case(store, nhw, b1=None):
+def _case(store, nhw, b1=None, FE=FE):
     """inputs rounded to the storage type, weights, the blobs' effective weights -- computed once per case and left unchanged"""
-    key = (store, nhw, b1)
+    key = (store, nhw, b1, FE)
     if key not in _cases:
         from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
         n, h, w = nhw
@@ -99,37 +103,41 @@ def _bits(t):
 
 @pytest.mark.parametrize("store", ["bf16", "f16"])
 @pytest.mark.parametrize("with_g", [False, True])
-@pytest.mark.parametrize("nhw", SIZES)
-def test_head_matches_fp64_restatement(store, with_g, nhw):
-    c = _case(store, nhw)
+@pytest.mark.parametrize("nhw,FE", HEAD_CASES)
+def test_head_matches_fp64_restatement(store, with_g, nhw, FE):
+    from ntire2022_esr_amd import ops
+    c = _case(store, nhw, FE=FE)
     n, h, w = nhw
     c1_out = torch.full((n, h, w, 16), 7.0, dtype=DT[store], device=DEV)
-    xs, u, c1 = _run(c, with_g, c1_out=c1_out, c1_channels=16)
+    with ops.kernel_trace() as names:
+        xs, u, c1 = _run(c, with_g, c1_out=c1_out, c1_channels=16)
+    tf = {True: "true", False: "false"}
+    assert len(names) == 1 and names[0].startswith(f"resblock_head_kernel<{tf[store == 'bf16']}, {tf[with_g]}>"), names
     if with_g:
         ref_x = _nchw(c["x"]) + _nchw(c["g"])
         err = (_nchw(xs) - ref_x).abs()
-        print(f"head {store} {nhw}: max|x - ref| = {float(err.max()):.3e}, ", end="")
+        print(f"head {store} {nhw} fe={FE}: max|x - ref| = {float(err.max()):.3e}, ", end="")
         assert int((err > _tol(ref_x, store)).sum()) == 0, float(err.max())
     else:
         assert xs is None
     t, ref_u = _ref_u(c, _nchw(xs if with_g else c["x"]), store)
     err = (_nchw(u) - ref_u).abs()
-    print(f"max|u - ref| = {float(err.max()):.3e}, ", end="")
+    print(f"max|u - ref| = {float(err.max()):.3e} ({float((err / _tol_u(c, t, ref_u, store)).max()):.3f} of the bound), ", end="")
     assert int((err > _tol_u(c, t, ref_u, store)).sum()) == 0, float(err.max())
     wc, bc = c["ec"]
     ref_c = F.conv2d(_nchw(u), wc.double(), bc.double())
     err = (_nchw(c1[..., :FE]) - ref_c).abs()
-    print(f"max|c1 - ref| = {float(err.max()):.3e}")
+    print(f"max|c1 - ref| = {float(err.max()):.3e} ({float((err / _tol(ref_c, store)).max()):.3f} of the bound)")
     assert int((err > _tol(ref_c, store)).sum()) == 0, float(err.max())
     assert torch.all(c1[..., FE:] == 0)                   # the ESA map's pad channels
 
 
 @pytest.mark.parametrize("store", ["bf16", "f16"])
 @pytest.mark.parametrize("with_g", [False, True])
-@pytest.mark.parametrize("nhw", SIZES)
-def test_head_equals_the_four_launches_bit_for_bit(store, with_g, nhw):
+@pytest.mark.parametrize("nhw,FE", HEAD_CASES)
+def test_head_equals_the_four_launches_bit_for_bit(store, with_g, nhw, FE):
     from ntire2022_esr_amd import ops, _lib as L
-    c = _case(store, nhw)
+    c = _case(store, nhw, FE=FE)
     w1, b1, w2, b2, wc, bc = c["w"]
     xs, u, c1 = _run(c, with_g)
     x = c["x"].to(DEV)

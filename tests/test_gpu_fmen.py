@@ -36,14 +36,25 @@ def _ulp_ok(got, ref, dt):
     return bool(((got.double() - ref).abs() <= tol).all()), float(((got.double() - ref).abs() - tol).max())
 
 
-@pytest.mark.parametrize("cin", [12, 16])
-@pytest.mark.parametrize("pitch", [56, 64])
-@pytest.mark.parametrize("hw", [(17, 15), (5, 90), (23, 37)])
-@pytest.mark.parametrize("store", ["f32", "bf16", "f16"])
-def test_gate_epilogue_matches_fp64(store, hw, pitch, cin):
+# (cin, cmid) of the fused HFAB's channel-width cases: both chunk counts of x (33 .. 48, 49 .. 64) with both ends of each, every residue
+# 1 .. 7 of cin mod 8 (the kernel's pad-slot mask), cmid at both ends, at a whole granule and one past it
+HFAB_WIDTHS = [(33, 1), (39, 9), (44, 16), (49, 8), (51, 1), (61, 16), (62, 9), (64, 8)]
+_GATE_HW = [(17, 15), (5, 90), (23, 37)]
+# FMEN's excitate (cmid 12 / 16 -> 50) at every size and both output pitches, under the ids it always had; then the excitate of every HFAB
+# width case as the per-layer side launches it: cmid -> cin channels on an input of pitch round_up(cmid, 8) (8: the chunk's second half
+# is the next pixel and meets zero weight rows), gate operand and output of pitch round_up(cin, 8)
+# (16-bit storage: the fp32 kernels take no part in the fused HFAB)
+GATE_CASES = [pytest.param(st, hw, pitch, cin, 50, 16, id=f"{st}-hw{i}-{pitch}-{cin}")
+              for cin in (12, 16) for pitch in (56, 64) for i, hw in enumerate(_GATE_HW) for st in ("f32", "bf16", "f16")] + \
+             [pytest.param(st, (23, 37), (c + 7) // 8 * 8, m, c, (m + 7) // 8 * 8, id=f"{st}-23x37-{m}-{c}") for c, m in HFAB_WIDTHS for st in ("bf16", "f16")]
+
+
+@pytest.mark.parametrize("store,hw,pitch,cin,cout,xpitch", GATE_CASES)
+def test_gate_epilogue_matches_fp64(store, hw, pitch, cin, cout, xpitch):
     from ntire2022_esr_amd import _lib as L, ops
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
-    n, cout = 3, 50
+    n = 3
+    c8 = (cout + 7) // 8 * 8
     g = torch.Generator().manual_seed(cin * 1000 + pitch + hw[0])
     x = torch.randn(n, cin, *hw, generator=g)
     r = torch.randn(n, cout, *hw, generator=g) * 3
@@ -51,12 +62,13 @@ def test_gate_epilogue_matches_fp64(store, hw, pitch, cin):
     b = torch.randn(cout, generator=g)
     out = torch.zeros(n, *hw, pitch, device=DEV)
     if store == "f32":
-        xin = F.pad(_nhwc(x), (0, 16 - cin)).to(DEV)
+        xin = F.pad(_nhwc(x), (0, xpitch - cin)).to(DEV)
         rin = F.pad(_nhwc(r), (0, pitch - cout)).to(DEV)
         y = ops.conv2d(xin, w, b, cin=cin, res=rin, res_mode=L.RES_GATE, out=out)
         ref = torch.sigmoid(F.conv2d(x.double(), w.double(), b.double(), padding=1)) * r.double()
         got = y.cpu().permute(0, 3, 1, 2)[:, :cout].double()
         err = float((got - ref).abs().max())
+        print(f"gate f32 {cin}->{cout} {hw}: max|got - ref| = {err:.3e} ({err / (2e-5 * max(1.0, float(ref.abs().max()))):.3f} of the bound)")
         assert err <= 2e-5 * max(1.0, float(ref.abs().max())), err
         return
     dt = DT[store]
@@ -64,15 +76,16 @@ def test_gate_epilogue_matches_fp64(store, hw, pitch, cin):
     blob = pack_conv_s16(w, b, store, cin_phys=16)
     weff, _ = unpack_conv_s16(blob, cin, cout, 3, store, cin_phys=16)
     ref = torch.sigmoid(F.conv2d(x.double(), weff.double(), b.double(), padding=1)) * r.double()
-    xin = F.pad(_nhwc(x), (0, 16 - cin)).to(DEV)
+    xin = F.pad(_nhwc(x), (0, xpitch - cin)).to(DEV)
     rin = F.pad(_nhwc(r), (0, pitch - cout)).to(DEV)
     y = ops.conv2d(xin, w, b, cin=cin, res=rin, res_mode=L.RES_GATE, out=out.to(dt), packed=blob.to(DEV))
     got = y.float().cpu().permute(0, 3, 1, 2)
+    print(f"gate {store} {cin}->{cout} {hw}: max|got - ref| = {float((got[:, :cout].double() - ref).abs().max()):.3e}")
     ok, worst = _ulp_ok(got[:, :cout], ref, dt)
     assert ok, worst
-    assert torch.all(got[:, cout:56] == 0)                    # sigmoid(0) * the residual's zero pad slots
-    if pitch > 56:
-        assert torch.all(got[:, 56:] == 0)                    # never written
+    assert torch.all(got[:, cout:c8] == 0)                    # sigmoid(0) * the residual's zero pad slots
+    if pitch > c8:
+        assert torch.all(got[:, c8:] == 0)                    # never written
 
 
 def test_gate_rejects_an_activation_on_the_gpu():
@@ -101,11 +114,17 @@ def _hfab_per_layer(x, ws, bs, slope, cin, pitch):
     return ops.conv2d(t, ws[3], bs[3], res=x, res_mode=L.RES_GATE, out=out)
 
 
-@pytest.mark.parametrize("store", ["bf16", "f16"])
-@pytest.mark.parametrize("slope", [0.1, 0.05])
-@pytest.mark.parametrize("n,h,w,cin,pitch,cmid", [
+# FMEN's widths at both slopes (the ids they always had); HFAB_WIDTHS at the tight pitch, slope 0.05, one lone partial tile and one shape with
+# six tiles and ragged edges in both directions
+HFAB_CASES = [pytest.param(*c, sl, id="-".join(str(v) for v in c + (sl,))) for sl in (0.1, 0.05) for c in [
     (1, 17, 15, 50, 56, 16), (3, 5, 90, 50, 56, 16), (2, 23, 37, 50, 64, 16), (2, 40, 36, 50, 56, 12), (1, 64, 70, 48, 48, 16),
-    (3, 33, 16, 64, 64, 16), (1, 1, 1, 50, 56, 16)])
+    (3, 33, 16, 64, 64, 16), (1, 1, 1, 50, 56, 16)]] + \
+    [pytest.param(*nhw, c, (c + 7) // 8 * 8, m, 0.05, id="-".join(str(v) for v in nhw + (c, (c + 7) // 8 * 8, m, 0.05)))
+     for c, m in HFAB_WIDTHS for nhw in [(1, 17, 15), (2, 23, 37)]]
+
+
+@pytest.mark.parametrize("store", ["bf16", "f16"])
+@pytest.mark.parametrize("n,h,w,cin,pitch,cmid,slope", HFAB_CASES)
 def test_fused_hfab_equals_per_layer_launches(store, slope, n, h, w, cin, pitch, cmid):
     from ntire2022_esr_amd import _lib as L, ops
     dt = DT[store]
@@ -113,8 +132,10 @@ def test_fused_hfab_equals_per_layer_launches(store, slope, n, h, w, cin, pitch,
     g = torch.Generator().manual_seed(h * w + cin)
     x = F.pad(torch.randn(n, h, w, cin, generator=g) * 2, (0, pitch - cin)).to(dt).to(DEV)
     want = _hfab_per_layer(x, ws, bs, slope, cin, pitch)
-    got = ops.conv_chain(x, ws, bs, slope=slope, res_mode=L.RES_GATE, cin=cin)
+    with ops.kernel_trace() as names:
+        got = ops.conv_chain(x, ws, bs, slope=slope, res_mode=L.RES_GATE, cin=cin)
     torch.cuda.synchronize()
+    assert len(names) == 1 and names[0].startswith(f"hfab_kernel<{'true' if store == 'bf16' else 'false'}, {(cin + 15) // 16}>"), names
     assert got.shape == want.shape and got.dtype == dt
     assert torch.equal(got.view(torch.int16), want.view(torch.int16)), int((got != want).sum())
 
@@ -125,6 +146,7 @@ def test_fused_hfab_equals_per_layer_launches(store, slope, n, h, w, cin, pitch,
     got_nan = ops.conv_chain(xn, ws, bs, slope=slope, res_mode=L.RES_GATE, cin=cin)
     torch.cuda.synchronize()
     assert torch.equal(got_nan.view(torch.int16), got.view(torch.int16))
+    assert bool(torch.isfinite(got_nan[..., :cin].float()).all())
 
 
 _models = {}

@@ -44,12 +44,28 @@ def _same_or_one_step(a, b, dt, frac=0.03, scale=1.0):
 ACTS = {0: lambda t: t, 1: lambda t: F.leaky_relu(t, 0.05), 2: F.relu, 3: lambda t: F.gelu(t)}
 
 
+# The layer shapes that the per-layer / separate-launch sides of the fused kernels' bit-identity cases run on conv_s16_kernel, so that each of
+# those cases rests on an fp64 case of the same widths: (cin, cout, k, act, res_mode) at 23 x 37 on an input of TIGHT pitch round_up(cin, 8),
+# as those launches read it (the last chunk's second half is then the next pixel's bytes, on zero weight rows)
+_HFAB_W = [(33, 1), (39, 9), (44, 16), (49, 8), (51, 1), (61, 16), (62, 9), (64, 8)]                       # tests/test_gpu_fmen.py: squeeze, conv1 / conv2
+_CHAIN_W = [(33, 33), (41, 34), (40, 47), (48, 48)]                                                        # tests/test_gpu_chain.py: c1_r, c2_r
+WIDTH_LAYERS = sorted({(c, m, 3, 1, 0) for c, m in _HFAB_W} | {(m, m, 3, 1, 0) for _, m in _HFAB_W} |
+                      {(nf, mf, 3, 1, 0) for nf, mf in _CHAIN_W} | {(mf, mf, 3, 1, 0) for _, mf in _CHAIN_W} |
+                      # tests/test_gpu_esan.py: the two 3x3s, esa.conv1 at 1 / 9 / 16 channels, the identity 1x1 that adds g
+                      {(32, 32, 3, 2, 0), (32, 32, 3, 0, 0), (32, 1, 1, 0, 0), (32, 9, 1, 0, 0), (32, 16, 1, 0, 0), (32, 32, 1, 0, 1)} |
+                      # the single-image side of the conv48r / conv64r / conv64m cases below (c{j}_r with and without + x, c4's two output tiles)
+                      {(c, c, 3, 1, 0) for c in (33, 41, 47, 49, 57, 63)} | {(c, c, 3, 1, 1) for c in (49, 57, 63)} |
+                      {(49, 24, 3, 1, 0), (57, 17, 3, 1, 0), (63, 32, 3, 1, 0)})
+S16_CASES = [pytest.param(*c[:3], hw, *c[3:], False, id="-".join(str(v) for v in c[:3] + (f"hw{i}",) + c[3:])) for i, (hw, c) in enumerate([
+    ((16, 32), (64, 64, 3, 1, 1)), ((23, 37), (48, 48, 3, 1, 2)), ((17, 15), (48, 16, 3, 0, 0)), ((40, 56), (64, 48, 3, 1, 0)),
+    ((20, 36), (50, 50, 3, 1, 1)), ((5, 3), (16, 16, 3, 2, 0)), ((33, 18), (46, 46, 1, 0, 0)), ((40, 40), (50, 25, 1, 1, 0)),
+    ((19, 70), (128, 50, 1, 0, 0)), ((35, 33), (256, 50, 1, 1, 0)), ((64, 64), (48, 48, 1, 3, 2)), ((70, 50), (32, 64, 3, 1, 1))])] + \
+    [pytest.param(*c[:3], (23, 37), *c[3:], True, id="-".join(str(v) for v in c[:3] + ("23x37",) + c[3:])) for c in WIDTH_LAYERS]
+
+
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("cin,cout,k,hw,act,res_mode", [
-    (64, 64, 3, (16, 32), 1, 1), (48, 48, 3, (23, 37), 1, 2), (48, 16, 3, (17, 15), 0, 0), (64, 48, 3, (40, 56), 1, 0),
-    (50, 50, 3, (20, 36), 1, 1), (16, 16, 3, (5, 3), 2, 0), (46, 46, 1, (33, 18), 0, 0), (50, 25, 1, (40, 40), 1, 0),
-    (128, 50, 1, (19, 70), 0, 0), (256, 50, 1, (35, 33), 1, 0), (48, 48, 1, (64, 64), 3, 2), (32, 64, 3, (70, 50), 1, 1)])
-def test_s16_conv_matches_fp64_reference(compute, cin, cout, k, hw, act, res_mode):
+@pytest.mark.parametrize("cin,cout,k,hw,act,res_mode,tight", S16_CASES)
+def test_s16_conv_matches_fp64_reference(compute, cin, cout, k, hw, act, res_mode, tight):
     """16-bit storage conv (esr_conv2d_f32 with storage = bf16 / f16): inputs are exact 16-bit values, the reference uses
     the EFFECTIVE weights of the packed blob (error-diffused 3x3 taps / hi + lo 1x1) in fp64, so the only differences
     are fp32 accumulation order and the single rounding of the stored result."""
@@ -66,11 +82,14 @@ def test_s16_conv_matches_fp64_reference(compute, cin, cout, k, hw, act, res_mod
     weff, _ = unpack_conv_s16(blob, cin, cout, k, compute, cin_phys=cp)
     conv = F.conv2d(x.double(), weff.double(), b.double(), padding=k // 2)
     ref = ACTS[act](conv + r.double()) if res_mode == 1 else (ACTS[act](conv) + r.double() if res_mode == 2 else ACTS[act](conv))
-    xin = F.pad(_nhwc(x), (0, cp - cin)).to(DEV)
+    xin = F.pad(_nhwc(x), (0, ((cin + 7) // 8 * 8 if tight else cp) - cin)).to(DEV)
     rp = F.pad(_nhwc(r), (0, (-cout) % 8)).to(DEV) if res_mode else None
-    y = ops.conv2d(xin, w, b, act=act, res=rp, res_mode=res_mode, cin=cin, packed=blob.to(DEV))
+    with ops.kernel_trace() as names:
+        y = ops.conv2d(xin, w, b, act=act, res=rp, res_mode=res_mode, cin=cin, packed=blob.to(DEV))
+    assert len(names) == 1 and names[0].startswith("conv_s16_kernel<"), names
     assert y.dtype == dt and y.shape[-1] == (cout + 7) // 8 * 8
     got = y.float().cpu().permute(0, 3, 1, 2)
+    print(f"conv_s16 {compute} {cin}->{cout} k={k} {hw}: max|got - ref| = {float((got[:, :cout].double() - ref).abs().max()):.3e}")
     if act == 3:            # GELU in the 16-bit modes is gelu16(): |error| <= 1.3e-4 (tools/fit_gelu.py) on top of the rounding
         assert bool(((got[:, :cout].double() - ref).abs() <= ref.abs() * 2.0 ** (-8 if dt == torch.bfloat16 else -11) * 1.01 + 2.5e-4).all())
     else:
@@ -182,9 +201,15 @@ def test_s16_head_from_nchw_fp32(compute):
     assert torch.all(y[..., 46:] == 0)
 
 
+# RLFN's widths (mf = 48 -> nf = 46 -> 46 -> 16) at every size under the ids they always had; the widths of tests/test_gpu_chain.py's new cases
+# (their third launch) at the small size
+RLFB_CASES = [pytest.param(n, hw, 48, 46, 16, id=f"{n}-hw{i}") for i, (n, hw) in enumerate([(2, (37, 29)), (1, (256, 250)), (2, (339, 510)), (3, (200, 123))])] + \
+             [pytest.param(2, (37, 29), mf, nf, f, id=f"2-37x29-{mf}-{nf}-{f}") for nf, mf, f in [(33, 33, 1), (41, 34, 8), (40, 47, 9), (48, 48, 16)]]
+
+
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("n,hw", [(2, (37, 29)), (1, (256, 250)), (2, (339, 510)), (3, (200, 123))])
-def test_s16_post_chain_rlfb(compute, n, hw):
+@pytest.mark.parametrize("n,hw,mf,nf,f", RLFB_CASES)
+def test_s16_post_chain_rlfb(compute, n, hw, mf, nf, f):
     """RLFB tail in one launch: u = lrelu(c3_r(x)) + r (never stored), v = c5(u), c1 = esa.conv1(v): the 1x1s run on the fp32
     tile (hi + lo operands), only v and c1 are rounded -- against fp64 with the blob's effective 3x3 weights.  The small shape runs
     on conv_s16_kernel, the others (>= 256 tiles of 16 x 16, < 1024 of 16 x 32) on conv48rp_kernel: weights in registers, the residual
@@ -193,22 +218,22 @@ def test_s16_post_chain_rlfb(compute, n, hw):
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
     dt = DT[compute]
     g = torch.Generator().manual_seed(21 + n + hw[0])
-    x = torch.randn(n, 48, *hw, generator=g).to(dt)
-    r = torch.randn(n, 46, *hw, generator=g).to(dt)
-    w, b = torch.randn(46, 48, 3, 3, generator=g) * 0.1, torch.randn(46, generator=g)
-    w5, b5 = torch.randn(46, 46, generator=g) * 0.2, torch.randn(46, generator=g)
-    w1, b1 = torch.randn(16, 46, generator=g) * 0.2, torch.randn(16, generator=g)
-    weff, _ = unpack_conv_s16(pack_conv_s16(w, b, compute), 48, 46, 3, compute)
+    x = torch.randn(n, mf, *hw, generator=g).to(dt)
+    r = torch.randn(n, nf, *hw, generator=g).to(dt)
+    w, b = torch.randn(nf, mf, 3, 3, generator=g) * 0.1, torch.randn(nf, generator=g)
+    w5, b5 = torch.randn(nf, nf, generator=g) * 0.2, torch.randn(nf, generator=g)
+    w1, b1 = torch.randn(f, nf, generator=g) * 0.2, torch.randn(f, generator=g)
+    weff, _ = unpack_conv_s16(pack_conv_s16(w, b, compute), mf, nf, 3, compute)
     u = F.leaky_relu(F.conv2d(x.double(), weff.double(), b.double(), padding=1), 0.05) + r.double()
     # bf16: hi + lo operands (the chain sees ~fp32 values and weights); fp16: the 11-bit high parts only -- operands of the
     # chain's MFMAs are the fp16 roundings of the fp32 tile and of the weights (the network's own storage precision)
     q = (lambda t: t) if compute == "bf16" else (lambda t: t.to(torch.float16).double())
     v = F.conv2d(q(u), q(w5.double())[:, :, None, None], b5.double())
     c1 = F.conv2d(q(v), q(w1.double())[:, :, None, None], b1.double())
-    rp = F.pad(_nhwc(r), (0, 2)).to(DEV)
-    y, yv, yc = ops.conv2d(_nhwc(x).to(DEV), w, b, act=1, res=rp, res_mode=2, post_weight=w5, post_bias=b5,
-                           post2_weight=w1, post2_bias=b1, store_main=False)
-    assert y is None and yv.dtype == dt and yv.shape[-1] == 48 and yc.shape[-1] == 16
+    rp = F.pad(_nhwc(r), (0, 48 - nf)).to(DEV)
+    y, yv, yc = ops.conv2d(F.pad(_nhwc(x), (0, 48 - mf)).to(DEV), w, b, act=1, res=rp, res_mode=2, post_weight=w5, post_bias=b5,
+                           post2_weight=w1, post2_bias=b1, store_main=False, cin=mf)
+    assert y is None and yv.dtype == dt and yv.shape[-1] == (nf + 7) // 8 * 8 and yc.shape[-1] == (f + 7) // 8 * 8
     eps = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
 
     def close(got, want):
@@ -224,9 +249,9 @@ def test_s16_post_chain_rlfb(compute, n, hw):
             return float((err > tol).double().mean()) <= 2e-5 and bool((err <= 3 * tol).all())
         return bool((err <= tol).all())
 
-    assert close(yv.float().cpu().permute(0, 3, 1, 2)[:, :46], v)
-    assert close(yc.float().cpu().permute(0, 3, 1, 2)[:, :16], c1)
-    assert torch.all(yv[..., 46:] == 0)
+    assert close(yv.float().cpu().permute(0, 3, 1, 2)[:, :nf], v)
+    assert close(yc.float().cpu().permute(0, 3, 1, 2)[:, :f], c1)
+    assert torch.all(yv[..., nf:] == 0) and torch.all(yc[..., f:] == 0)
 
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
@@ -338,7 +363,9 @@ def test_network_psnr_shift(mid, compute, max_dpsnr):
     (48, 24, 3, False, True, (128, 128), 8),       # ESDB c4: two output tiles
     (48, 48, 0, True, False, (128, 128), 8),       # residual == input without activation
     (48, 48, 1, False, False, (128, 128), 32),     # >= 1024 tiles of 16 x 32: the 8-rows-per-wave shape (the others: 16 x 16 tiles)
-    (48, 48, 3, True, True, (128, 120), 33)])
+    (48, 48, 3, True, True, (128, 120), 33),
+    # other widths of the three-chunk range 33 .. 48 at the kernel's threshold, 256 tiles of 16 x 32: both ends and one past a 16-byte granule
+    (33, 33, 1, False, False, (128, 128), 8), (41, 41, 1, False, False, (128, 128), 8), (47, 47, 1, False, False, (128, 128), 8)])
 def test_conv48r_equals_conv_s16(compute, cin, cout, act, res_in, border, hw, n):
     """conv48r_kernel (3x3 over 48 physical input channels, >= 256 tiles of 16 x 32: weights in registers, one wave per SIMD, row pairs
     as the outer loop) against conv_s16_kernel: the batch takes the new kernel (esr_conv_block_waves == 1), each image alone the old
@@ -366,7 +393,12 @@ def test_conv48r_equals_conv_s16(compute, cin, cout, act, res_in, border, hw, n)
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 1
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) != 1
-    y = ops.conv2d(xin, w, b, **kw)
+    with ops.kernel_trace() as names:
+        y = ops.conv2d(xin, w, b, **kw)
+    bf = "true" if compute == "bf16" else "false"
+    want = f"conv64m_kernel<{bf}, false, false, 3, true>" if act == 3 and res_in and border and cout > 32 else \
+        f"conv48r_kernel<{bf}, {(cout + 15) // 16}, {'true' if cout <= 32 or border or res_in or act == 3 else 'false'}, "
+    assert len(names) == 1 and names[0].startswith(want), names
     for i in range(n):
         kw1 = dict(kw)
         if res_in:
@@ -391,23 +423,28 @@ def test_conv48r_equals_conv_s16(compute, cin, cout, act, res_in, border, hw, n)
 
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("hw,n", [((128, 128), 8), ((100, 77), 9)])
-def test_conv48rp_equals_conv_s16(compute, hw, n):
+@pytest.mark.parametrize("hw,n,mf,nf,f", [
+    pytest.param((128, 128), 8, 48, 46, 16, id="hw0-8"), pytest.param((100, 77), 9, 48, 46, 16, id="hw1-9"),
+    # other widths of the ranges: both ends and one past a 16-byte granule (mf -> nf with the block input, nf -> nf, nf -> f)
+    ((128, 128), 8, 33, 33, 1), ((128, 128), 8, 34, 41, 8), ((128, 128), 8, 47, 40, 9)])
+def test_conv48rp_equals_conv_s16(compute, hw, n, mf, nf, f):
     """conv48rp_kernel (RLFB c3_r + block input -> c5 -> esa.conv1: weights in registers, 16 x 16 tiles, the residual staged by each wave
     for its own rows, post images in LDS, the chain on both rows of a pair) against conv_s16_kernel: the batch takes the new kernel
     (>= 256 tiles of 16 x 16), each image alone the old one -- both outputs bit-identical, ragged edges included."""
     from ntire2022_esr_amd import ops, _lib as L
     dt = DT[compute]
     g = torch.Generator().manual_seed(hw[0] + n)
-    x = _nhwc(torch.randn(n, 48, *hw, generator=g).to(dt)).to(DEV)
-    r = F.pad(_nhwc(torch.randn(n, 46, *hw, generator=g).to(dt)), (0, 2)).to(DEV)
-    w, b = torch.randn(46, 48, 3, 3, generator=g) * 0.1, torch.randn(46, generator=g)
-    w5, b5 = torch.randn(46, 46, generator=g) * 0.2, torch.randn(46, generator=g)
-    w1, b1 = torch.randn(16, 46, generator=g) * 0.2, torch.randn(16, generator=g)
-    kw = dict(act=1, res_mode=2, post_weight=w5, post_bias=b5, post2_weight=w1, post2_bias=b1, store_main=False)
+    x = F.pad(_nhwc(torch.randn(n, mf, *hw, generator=g).to(dt)), (0, 48 - mf)).to(DEV)
+    r = F.pad(_nhwc(torch.randn(n, nf, *hw, generator=g).to(dt)), (0, 48 - nf)).to(DEV)
+    w, b = torch.randn(nf, mf, 3, 3, generator=g) * 0.1, torch.randn(nf, generator=g)
+    w5, b5 = torch.randn(nf, nf, generator=g) * 0.2, torch.randn(nf, generator=g)
+    w1, b1 = torch.randn(f, nf, generator=g) * 0.2, torch.randn(f, generator=g)
+    kw = dict(act=1, res_mode=2, post_weight=w5, post_bias=b5, post2_weight=w1, post2_bias=b1, store_main=False, cin=mf)
     tiles16 = lambda nn: nn * ((hw[1] + 15) // 16) * ((hw[0] + 15) // 16)
     assert tiles16(n) >= 256 and tiles16(1) < 256
-    y, yv, yc = ops.conv2d(x, w, b, res=r, **kw)
+    with ops.kernel_trace() as names:
+        y, yv, yc = ops.conv2d(x, w, b, res=r, **kw)
+    assert len(names) == 1 and names[0].startswith(f"conv48rp_kernel<{'true' if compute == 'bf16' else 'false'}, false>"), names
     assert y is None
     for i in range(n):
         _, v1, c1 = ops.conv2d(x[i:i + 1].contiguous(), w, b, res=r[i:i + 1].contiguous(), **kw)
@@ -501,7 +538,11 @@ def test_s16_hilo_rejects_what_it_does_not_cover():
     (50, 50, 1, True, (100, 77), 9),         # RFDB c{j}_r: lrelu(conv(x) + x), 50 logical channels in 64, ragged edges
     (64, 32, 1, False, (128, 128), 5),       # RFDB c4: two output tiles
     (50, 25, 1, False, (64, 250), 7),
-    (64, 64, 0, True, (128, 128), 4)])       # residual == input without activation
+    (64, 64, 0, True, (128, 128), 4),        # residual == input without activation
+    # other widths of the four-chunk range 49 .. 64 at the kernels' threshold, 256 tiles of 16 x 16 with a ragged right edge: four output tiles
+    # (conv64m_kernel) and two (conv64r_kernel, 17 .. 32 outputs: both ends and a whole granule)
+    (49, 49, 1, True, (128, 120), 4), (57, 57, 1, False, (128, 120), 4), (63, 63, 0, True, (128, 120), 4),
+    (49, 24, 1, False, (128, 120), 4), (57, 17, 1, False, (128, 120), 4), (63, 32, 1, False, (128, 120), 4)])
 def test_conv64r_equals_conv_s16(compute, cin, cout, act, res_in, hw, n):
     """The 3x3s over 64 physical input channels at >= 256 tiles of 16 x 16 (one wave per SIMD, weights in registers, row pairs as the outer
     loop, 160-byte LDS pixels) against conv_s16_kernel: the batch takes the register-resident kernel (esr_conv_block_waves == 1), each image
@@ -528,7 +569,10 @@ def test_conv64r_equals_conv_s16(compute, cin, cout, act, res_in, hw, n):
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 1
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) != 1
-    y = ops.conv2d(xin, w, b, **kw)
+    with ops.kernel_trace() as names:
+        y = ops.conv2d(xin, w, b, **kw)
+    bf = "true" if compute == "bf16" else "false"
+    assert len(names) == 1 and names[0].startswith(f"conv64m_kernel<{bf}, false, false, 4, false>" if cout > 48 else f"conv64r_kernel<{bf}, 2,"), names
     for i in range(n):
         kw1 = dict(kw)
         if res_in:
@@ -549,7 +593,8 @@ def test_conv64r_equals_conv_s16(compute, cin, cout, act, res_in, hw, n):
     assert int(((got - ref).abs() > tol).sum()) == 0
 
 
-@pytest.mark.parametrize("hw,n,c,act", [((128, 128), 8, 48, 0), ((100, 77), 9, 46, 0), ((64, 250), 5, 46, 1)])
+@pytest.mark.parametrize("hw,n,c,act", [((128, 128), 8, 48, 0), ((100, 77), 9, 46, 0), ((64, 250), 5, 46, 1),
+                                        ((128, 128), 8, 33, 0), ((128, 128), 8, 41, 0), ((128, 128), 8, 47, 1)])      # other widths of 33 .. 48
 def test_conv48rl_equals_conv_s16(hw, n, c, act):
     """conv48rp_kernel<bf16, LRS> (the LR conv of a 48-channel network on hi + lo pairs: residual pair staged by each wave for its own rows,
     (conv + hi) + lo, hi / lo stores) against conv_s16_kernel's HILO instantiation: the batch takes the new kernel (>= 256 tiles of
@@ -576,7 +621,9 @@ def test_conv48rl_equals_conv_s16(hw, n, c, act):
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 8
     kw = dict(cin=c, packed=blob, act=act, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-    y = ops.conv2d(xin, w, b, res=rin, **kw)
+    with ops.kernel_trace() as names:
+        y = ops.conv2d(xin, w, b, res=rin, **kw)
+    assert len(names) == 1 and names[0].startswith("conv48rp_kernel<true, true>"), names
     assert tuple(y.shape) == (2, n, *hw, cp)
     for i in range(n):
         y1 = ops.conv2d(xin[i:i + 1].contiguous(), w, b, res=rin[:, i:i + 1].contiguous(), **kw)
@@ -604,31 +651,37 @@ def test_s16_hilo_head_with_post(c, pc, hw):
     assert float(lo.abs().max()) > 0 and bool((lo.abs() <= y1[0].float().abs() * 2.0 ** -7 + 1e-30).all())
 
 
-@pytest.mark.parametrize("hw,n,border,act,pact", [((128, 128), 8, True, 3, 3), ((100, 77), 9, False, 3, 3), ((64, 250), 5, True, 1, 1)])
-def test_conv48rq_equals_conv_s16(hw, n, border, act, pact):
+@pytest.mark.parametrize("hw,n,border,act,pact,c,pc", [
+    pytest.param((128, 128), 8, True, 3, 3, 48, 24, id="hw0-8-True-3-3"), pytest.param((100, 77), 9, False, 3, 3, 48, 24, id="hw1-9-False-3-3"),
+    pytest.param((64, 250), 5, True, 1, 1, 48, 24, id="hw2-5-True-1-1"),
+    # other widths: c over 33 .. 48, the post 1x1's two output tiles over 17 .. 32
+    ((128, 128), 8, False, 3, 3, 33, 17), ((128, 128), 8, True, 1, 1, 41, 24), ((128, 128), 8, False, 3, 3, 47, 32)])
+def test_conv48rq_equals_conv_s16(hw, n, border, act, pact, c, pc):
     """conv48rq_kernel (fp16: ESDB c{j}_r as a dense BSConvU + input + GELU, stored, with the next distillation 1x1 + GELU as 87 micro-operations
     behind the next row pair's MFMAs) against conv_s16_kernel<3, 3, 8, .., 2, 0>: the batch takes the new kernel (>= 256 tiles of 16 x 16,
     esr_conv_block_waves == 1), each image alone the old one -- both outputs bit-identical, ragged edges and the border table included."""
     from ntire2022_esr_amd import ops, _lib as L
     from ntire2022_esr_amd.engine import pack_conv_s16
     g = torch.Generator().manual_seed(n * 10 + hw[0])
-    c, pc = 48, 24
-    x = torch.randn(n, *hw, c, generator=g).to(torch.float16).to(DEV)
+    x = F.pad(torch.randn(n, *hw, c, generator=g), (0, 48 - c)).to(torch.float16).to(DEV)
     w, b = torch.randn(c, c, 3, 3, generator=g) * 0.1, torch.randn(c, generator=g)
     wp, bp = torch.randn(pc, c, generator=g) * 0.2, torch.randn(pc, generator=g)
     table = None
     if border:
         table = torch.randn(16, 48, generator=g) * 0.2
         table[0] = 0
+        table[:, c:] = 0
         table = table.to(DEV)
     blob = pack_conv_s16(w, b, "f16").to(DEV)
-    kw = dict(act=act, packed=blob, border=table, res_mode=L.RES_PRE_ACT, post_weight=wp, post_bias=bp, post_act=pact)
-    y, yp = ops.conv2d(x, w, b, res=x, **kw)
+    kw = dict(act=act, packed=blob, border=table, res_mode=L.RES_PRE_ACT, post_weight=wp, post_bias=bp, post_act=pact, cin=c)
+    with ops.kernel_trace() as names:
+        y, yp = ops.conv2d(x, w, b, res=x, **kw)
+    assert len(names) == 1 and names[0].startswith("conv64m_kernel<false, true, false, 3, true>" if border and act == 3 and pact == 3 else "conv48rq_kernel<false,"), names
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, hw[0], hw[1], c, c, 3
     d.in_layout = d.out_layout = L.NHWC
     d.storage, d.act, d.res_mode, d.post_cout = L.STORE["f16"], act, L.RES_PRE_ACT, pc
-    d.inp = d.res = L.View(ctypes.c_void_p(x.data_ptr()), c, 0)
+    d.inp = d.res = L.View(ctypes.c_void_p(x.data_ptr()), 48, 0)
     d.out0 = L.View(ctypes.c_void_p(y.data_ptr()), y.shape[-1], 0)
     d.post_wpacked = ctypes.c_void_p(blob.data_ptr())                  # (any non-null pointer: the query does not read it)
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 1
@@ -646,7 +699,8 @@ def test_conv48rq_equals_conv_s16(hw, n, border, act, pact):
 
 
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
-@pytest.mark.parametrize("hw,n,c,pc,res_in", [((128, 128), 8, 50, 25, True), ((100, 77), 9, 64, 32, True), ((64, 250), 5, 50, 25, False)])
+@pytest.mark.parametrize("hw,n,c,pc,res_in", [((128, 128), 8, 50, 25, True), ((100, 77), 9, 64, 32, True), ((64, 250), 5, 50, 25, False),
+                                              ((128, 120), 4, 49, 17, True), ((128, 120), 4, 57, 24, True), ((128, 120), 4, 63, 32, True)])      # other widths
 def test_conv64m_post_agrees_with_conv_s16(compute, hw, n, c, pc, res_in):
     """conv64m_kernel<.., POST> (esr_c64m.hip, round 6: RFDB c{j}_r = lrelu(conv(x) + x), stored, with c{j+1}_d + LeakyReLU in its epilogue, on
     v_mfma_f32_32x32x16; rounds 4 / 5: conv64rq_kernel) against conv_s16_kernel<4, 3, 8, .., 2, 0>: the batch takes the register-resident kernel
@@ -663,7 +717,9 @@ def test_conv64m_post_agrees_with_conv_s16(compute, hw, n, c, pc, res_in):
     kw = dict(act=1, cin=c, packed=blob, post_weight=wp, post_bias=bp, post_act=1)
     if res_in:
         kw.update(res_mode=L.RES_PRE_ACT)
-    y, yp = ops.conv2d(x, w, b, **(dict(res=x) if res_in else {}), **kw)
+    with ops.kernel_trace() as names:
+        y, yp = ops.conv2d(x, w, b, **(dict(res=x) if res_in else {}), **kw)
+    assert len(names) == 1 and names[0].startswith(f"conv64m_kernel<{'true' if compute == 'bf16' else 'false'}, true, false, 4, false>"), names
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, hw[0], hw[1], c, c, 3
     d.in_layout = d.out_layout = L.NHWC
