@@ -417,7 +417,8 @@ typedef enum esr_op_kind {
     ESR_OP_CONV_CHAIN = 8,      /* esr_conv_chain_s16 on esr_op.chain (ABI v11) */
     ESR_OP_MAXPOOL7S7 = 9,      /* esr_maxpool7s7_f32 on esr_op.esa (additive within ABI v12) */
     ESR_OP_DISTILL_STEP = 10,   /* esr_distill_step_s16 on esr_op.chain (additive within ABI v12) */
-    ESR_OP_RESBLOCK_HEAD = 11   /* esr_resblock_head_s16 on esr_op.conv (additive within ABI v12) */
+    ESR_OP_RESBLOCK_HEAD = 11,  /* esr_resblock_head_s16 on esr_op.conv (additive within ABI v12) */
+    ESR_OP_REFINE_CASCADE = 12  /* esr_refine_cascade_s16 on esr_op.chain (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -568,6 +569,36 @@ int esr_distill_step_s16(const esr_chain_desc* d, void* hip_stream);
 int esr_resblock_head_supported(const esr_conv_desc* d);
 int esr_resblock_head_s16(const esr_conv_desc* d, void* hip_stream);
 
+/*
+ * esr_refine_cascade_s16 (additive within ABI v12; op kind ESR_OP_REFINE_CASCADE on esr_op.chain) -- the narrowing refinement path of
+ * FasterRFDN's block (FRFDB.forward, models/team25_frfdn/block.py:115-122) as ONE launch on 16-bit storage (refine_cascade_kernel,
+ * csrc/esr_cascade.hip):
+ *     r2 = act(W2r (*) in + b2r + in)         3x3, 32 -> 32, never stored          (in = d2, the 1x1 c2_d of r1)
+ *     d3 = act(W3d  .  r2 + b3d)              1x1, 32 -> 16, stored to post_out
+ *     r3 = act(W3r (*) d3 + b3r + d3)         3x3, 16 -> 16, never stored
+ *     r4 = act(W4  (*) r3 + b4  + r3)         3x3, 16 -> 16, stored to post2_out
+ * Every value is rounded once to the storage type, exactly where the separate launches store it (three esr_conv2d_f32 3x3s whose residual
+ * is their input, and the 1x1), and every layer sees its input zero-padded like a stored tensor (a halo pixel of r2, d3 or r3 outside the
+ * image is 0, not act(bias)): what is stored is bit-identical to the four launches.  An esr_chain_desc carries it, no field added:
+ *     n_layers            4
+ *     in, cin             d2 and 32 (32 channels from coff)
+ *     cmid, cout          16 and 16
+ *     act, slope          ESR_ACT_LRELU and its slope (every layer)
+ *     res_mode            ESR_RES_PRE_ACT: every 3x3 adds its own input before the activation
+ *     storage, compute    ESR_STORE_BF16 / ESR_COMPUTE_BF16 or ESR_STORE_F16 / ESR_COMPUTE_F16
+ *     wpacked[0..3]       esr_pack_conv_s16 of c2_r (ksize 3, cin_phys 32), c3_d (ksize 1, cin_phys 32), c3_r and c4 (ksize 3, cin_phys 16)
+ *     post_out, post_cout     d3 and 16
+ *     post2_out, post2_cout   r4 and 16
+ *     post_wpacked, post2_wpacked   NULL
+ * d3 and r4 may be two slices of one tensor (channel offsets 0 and 16 of a pitch-32 concat segment); neither may be stored into `in`'s
+ * tensor: neighbouring tiles read its halo.
+ * esr_refine_cascade_supported: 1 when the descriptor has exactly this shape and a per-image input below 1 GiB; esr_refine_cascade_s16
+ * returns ESR_ERR_UNSUPPORTED for every other (fp32 storage included) and ESR_ERR_BAD_ARG for a null pointer, a view that is misaligned or
+ * does not hold its channels, or an output whose pointer is `in`'s.
+ */
+int esr_refine_cascade_supported(const esr_chain_desc* d);
+int esr_refine_cascade_s16(const esr_chain_desc* d, void* hip_stream);
+
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
@@ -575,7 +606,7 @@ typedef struct esr_op {
     esr_esa_desc esa;           /* the four ESA kinds */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */
-    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP */
+    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP, ESR_OP_REFINE_CASCADE */
 } esr_op;
 
 /* ABI v5 -- the network input for the 16-bit plans: NCHW fp32 [n, cin <= 4, h, w] (d->in.ptr) -> NHWC 16-bit (d->out0, pitch >= 16,

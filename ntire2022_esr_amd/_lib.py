@@ -23,6 +23,7 @@ OP_CONV, OP_CONV3X3S2, OP_MAXPOOL7S3, OP_ESA_APPLY, OP_DWCONV, OP_BSCONV, OP_PAC
 OP_MAXPOOL7S7 = 9                                                         # EFDN's ESA pooling (esr_maxpool7s7_f32)
 OP_DISTILL_STEP = 10                                                      # BMDN's distillation step (esr_distill_step_s16 on Op.chain)
 OP_RESBLOCK_HEAD = 11                                                     # ESAN's residual-block head (esr_resblock_head_s16 on Op.conv)
+OP_REFINE_CASCADE = 12                                                    # FasterRFDN's refinement cascade (esr_refine_cascade_s16 on Op.chain)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -144,7 +145,7 @@ EXPORTS = [
     "esr_tensor2uint_u8", "esr_sqerr_u8", "esr_channel_attention_f32",
     "esr_tensor2uint_u8_chk", "esr_ssim_partials", "esr_ssim_u8",
     "esr_conv_chain_supported", "esr_conv_chain_s16", "esr_distill_step_supported", "esr_distill_step_s16",
-    "esr_resblock_head_supported", "esr_resblock_head_s16",
+    "esr_resblock_head_supported", "esr_resblock_head_s16", "esr_refine_cascade_supported", "esr_refine_cascade_s16",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -265,6 +266,10 @@ def lib():
     L.esr_resblock_head_supported.restype = ci
     L.esr_resblock_head_s16.argtypes = [ctypes.POINTER(ConvDesc), vp]
     L.esr_resblock_head_s16.restype = ci
+    L.esr_refine_cascade_supported.argtypes = [ctypes.POINTER(ChainDesc)]
+    L.esr_refine_cascade_supported.restype = ci
+    L.esr_refine_cascade_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
+    L.esr_refine_cascade_s16.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

@@ -1197,6 +1197,7 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_MAXPOOL7S7: return esr_maxpool7s7_f32(&op.esa, hip_stream);
         case ESR_OP_DISTILL_STEP: return esr_distill_step_s16(&op.chain, hip_stream);
         case ESR_OP_RESBLOCK_HEAD: return esr_resblock_head_s16(&op.conv, hip_stream);
+        case ESR_OP_REFINE_CASCADE: return esr_refine_cascade_s16(&op.chain, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

@@ -992,6 +992,47 @@ class ResHead(_Fused):
 
 
 @dataclass
+class Cascade(_Fused):
+    """FRFDB's narrowing refinement path as ONE esr_refine_cascade_s16 op -- see Plan.refine_cascade (refine_cascade_kernel).
+    replaces: [c2_r, c3_d, c3_r, c4]."""
+    kind = "cascade"
+    predicate, field, what = "esr_refine_cascade_supported", "chain", "refinement cascade"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 4 and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo and o.hw is None for o in sub)
+        c2r, c3d, c3r, c4 = sub
+        assert c2r.k == 3 and c3d.k == 1 and c3r.k == 3 and c4.k == 3 and c3d.res is None
+        assert all(o.act == L.ACT_LRELU and o.slope == c2r.slope for o in sub)
+        assert all(o.res_mode == L.RES_PRE_ACT and _same_view(o.res, o.src) for o in (c2r, c3r, c4))       # every 3x3 adds its own input
+        assert _same_view(c3d.src, c2r.dst) and _same_view(c3r.src, c3d.dst) and _same_view(c4.src, c3r.dst)
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        c2r, c3d, c3r, c4 = self.replaces
+        op.kind = L.OP_REFINE_CASCADE
+        d = op.chain
+        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 4
+        d.cin, d.cmid, d.cout = c2r.cin, c3d.cout, c4.cout
+        d.act, d.slope, d.res_mode = L.ACT_LRELU, c2r.slope, L.RES_PRE_ACT
+        d.storage = d.compute = st
+        d.inp = _view(c2r.src, base)
+        for l, so in enumerate(self.replaces):
+            d.wpacked[l] = weights[so.w + S16].data_ptr()
+        d.post_out, d.post_cout = _view(c3d.dst, base), _stored_width(c3d.dst, c3d.cout)
+        d.post2_out, d.post2_cout = _view(c4.dst, base), _stored_width(c4.dst, c4.cout)
+
+    def cost(self, plan, desc):             # d2 read once; d3 and r4 written once
+        c2r, c3d, c3r, c4 = self.replaces
+        npix, es = plan.npix, plan.esize
+        flops = sum(2.0 * npix * so.cin_alg * so.cout * so.k * so.k for so in self.replaces)
+        wb = 4.0 * sum(so.cin_alg * so.cout * so.k * so.k for so in self.replaces)
+        kern = f"refine_cascade_kernel<{_tf(plan.store == 'bf16')}>"
+        stored = float(npix * es * (_stored_channels(c2r.src, c2r.cin, 16) + _stored_channels(c3d.dst, c3d.cout, 16) + _stored_channels(c4.dst, c4.cout, 16))) + wb
+        return _cost(c2r.w, kern, c2r.cin, c4.cout, 3, flops, float(npix * c2r.cin_alg * es) + wb, float(npix * es * (c3d.cout + c4.cout)), stored)
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1179,6 +1220,14 @@ class Plan:
         neighbouring tiles read their halo."""
         return self._fuse(mark, ResHead)
 
+    def refine_cascade(self, mark):
+        """The four convolutions appended since `mark = len(plan.ops)` -- FRFDB's refinement path behind d2 in its per-op form,
+        r2 = lrelu(c2_r(d2) + d2), d3 = lrelu(c3_d(r2)), r3 = lrelu(c3_r(d3) + d3), r4 = lrelu(c4(r3) + r3) (team25_frfdn/block.py:115-122) --
+        as ONE esr_refine_cascade_s16 op (16-bit plans): d2 is read once, d3 and r4 are written once, r2 and r3 never exist.  The Conv ops stay
+        attached as `replaces`: weights, complexity counters and algorithmic costs are theirs; the result is bit-identical to running them
+        one by one.  d3 and r4 must not be stored into d2's tensor: the neighbouring tiles read its halo."""
+        return self._fuse(mark, Cascade)
+
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [Post(w, dst, cout, act, slope, res), ...] -- one or two 1x1 convolutions evaluated in the same launch
@@ -1313,6 +1362,7 @@ class HipSRModel(nn.Module):
         self._fuse_chain = True    # 16-bit plans: a block's 3x3 chain as one esr_conv_chain_s16 launch where a kernel exists (Plan.chain)
         self._fuse_step = True     # 16-bit BMDN plans: a distillation step as one esr_distill_step_s16 launch (Plan.distill_step); measured: DESIGN.md 7d
         self._fuse_head = True     # 16-bit ESAN plans: a residual block's head as one esr_resblock_head_s16 launch (Plan.resblock_head); measured: DESIGN.md 7e
+        self._fuse_cascade = False # 16-bit FasterRFDN plans: FRFDB's refinement path as one esr_refine_cascade_s16 launch (Plan.refine_cascade); OFF: faster on one image, not at 32 x 256 x 256
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
         self._prof_passes = 0      # >0: record HIP events around every op (bench roofline leg)
@@ -1370,6 +1420,7 @@ class HipSRModel(nn.Module):
     tight_pitch = property(lambda self: self._tight_pitch, lambda self, v: self._set_flag("_tight_pitch", v))
     fuse_step = property(lambda self: self._fuse_step, lambda self, v: self._set_flag("_fuse_step", v))
     fuse_head = property(lambda self: self._fuse_head, lambda self, v: self._set_flag("_fuse_head", v))
+    fuse_cascade = property(lambda self: self._fuse_cascade, lambda self, v: self._set_flag("_fuse_cascade", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels

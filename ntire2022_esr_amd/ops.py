@@ -386,6 +386,41 @@ def resblock_head(x, w1, b1, w2, b2, wc, bc, *, g=None, in_coff=0, g_coff=0, x_o
     return xs, u, c1
 
 
+def refine_cascade(d2, w2r, b2r, w3d, b3d, w3r, b3r, w4, b4, *, slope=0.05, in_coff=0, d3_out=None, d3_coff=0, r4_out=None, r4_coff=0,
+                   store=None):
+    """esr_refine_cascade_s16: the narrowing refinement path of FasterRFDN's block (team25_frfdn/block.py:115-122) in ONE launch on a 16-bit
+    NHWC tensor d2 [N, H, W, P] (32 channels from in_coff): r2 = lrelu(conv3x3(d2, w2r, b2r) + d2), d3 = lrelu(w3d . r2 + b3d),
+    r3 = lrelu(conv3x3(d3, w3r, b3r) + d3), r4 = lrelu(conv3x3(r3, w4, b4) + r3), every tensor as rounded to the storage type and
+    zero-padded.  Returns (d3, r4), 16 channels each.
+    d3_out / r4_out: caller-provided NHWC tensors of d2's dtype and device (pitch a multiple of 8) that receive d3 / r4 from channel d3_coff /
+    r4_coff -- they may be one tensor (offsets 0 and 16 of a pitch-32 concat segment), never d2's; default: freshly allocated zeros of
+    pitch 16.  store: "bf16" | "f16", if given it must be d2's storage type."""
+    st = _s16_store(d2, "refine_cascade")
+    if store is not None and store != st:
+        raise L.EsrError(f"refine_cascade: store {store!r}, d2 is stored as {st}")
+    lib = L.lib()
+    n, h, w, _ = d2.shape
+    w1 = w3d if w3d.dim() == 4 else w3d[:, :, None, None]
+    d = L.ChainDesc()
+    d.n, d.h, d.w, d.n_layers = n, h, w, 4
+    d.cin, d.cmid, d.cout = w2r.shape[1], w1.shape[0], w4.shape[0]
+    d.act, d.slope, d.res_mode = L.ACT_LRELU, slope, L.RES_PRE_ACT
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(d2, in_coff)
+    keep = [pack_conv_s16(wt, b, st).to(d2.device) for wt, b in ((w2r, b2r), (w1, b3d), (w3r, b3r), (w4, b4))]
+    for i, k in enumerate(keep):
+        d.wpacked[i] = k.data_ptr()
+    d.post_cout, d.post2_cout = d.cmid, d.cout
+    d3 = _zeros_or(d3_out, "refine_cascade: d3_out", d2, (n, h, w), (d.post_cout + 7) // 8 * 8, 8)
+    r4 = _zeros_or(r4_out, "refine_cascade: r4_out", d2, (n, h, w), (d.post2_cout + 7) // 8 * 8, 8)
+    d.post_out, d.post2_out = _view(d3, d3_coff), _view(r4, r4_coff)
+    if not lib.esr_refine_cascade_supported(ctypes.byref(d)):
+        raise L.EsrError("refine_cascade: no kernel for this shape (esr_refine_cascade_supported)")
+    stream = torch.cuda.current_stream(d2.device).cuda_stream
+    _launch("esr_refine_cascade_s16", "esr_refine_cascade_s16", d, stream, L.OP_REFINE_CASCADE, "chain")
+    return d3, r4
+
+
 def _hilo_pair(t, what, strides):
     """checks a hi + lo pair [2, N, H, W, P] (bf16, P a multiple of 16) and records the byte stride between its halves"""
     if t.dtype != torch.bfloat16 or t.shape[-1] % 16:
