@@ -418,7 +418,9 @@ typedef enum esr_op_kind {
     ESR_OP_MAXPOOL7S7 = 9,      /* esr_maxpool7s7_f32 on esr_op.esa (additive within ABI v12) */
     ESR_OP_DISTILL_STEP = 10,   /* esr_distill_step_s16 on esr_op.chain (additive within ABI v12) */
     ESR_OP_RESBLOCK_HEAD = 11,  /* esr_resblock_head_s16 on esr_op.conv (additive within ABI v12) */
-    ESR_OP_REFINE_CASCADE = 12  /* esr_refine_cascade_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_REFINE_CASCADE = 12, /* esr_refine_cascade_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_DWCONV7 = 13,        /* esr_dwconv7x7 on esr_op.conv (additive within ABI v12) */
+    ESR_OP_CX_BLOCK = 14        /* esr_cx_block_s16 on esr_op.chain (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -599,6 +601,53 @@ int esr_resblock_head_s16(const esr_conv_desc* d, void* hip_stream);
 int esr_refine_cascade_supported(const esr_chain_desc* d);
 int esr_refine_cascade_s16(const esr_chain_desc* d, void* hip_stream);
 
+/*
+ * esr_dwconv7x7 (additive within ABI v12; op kind ESR_OP_DWCONV7 on esr_op.conv) -- depthwise nn.Conv2d(C, C, 7, 1, 3, groups=C) with zero
+ * padding and bias, no activation, no residual, on an NHWC tensor in fp32, bf16 or fp16 storage (dwconv7x7_kernel, csrc/esr_cx.hip).  The 49
+ * taps are summed in fp32 in (ky, kx) ascending order, the bias is added last and the sum is rounded once to the storage type.
+ * esr_conv_desc: ksize 7, cin == cout == C <= 64, in / out0 NHWC views that hold round_up(C, 4) (fp32) or round_up(C, 8) (16-bit) channels
+ * from coff -- the pad channels are stored as zeros --, act ESR_ACT_NONE, res_mode ESR_RES_NONE, storage; out0 must not be `in`'s tensor.
+ * Every other feature field (tail_*, post_*, split / out1, hilo, border_bias, blocked8, in_seg_stride, wino_wpacked) must be zero.
+ * wpacked = esr_pack_dw7_f32 of the [C, 1, 7, 7] weights: [tap][c_p] floats + bias[c_p], c_p = round_up(C, 8).
+ * esr_dwconv7x7_supported: 1 for such a descriptor; esr_dwconv7x7 returns ESR_ERR_UNSUPPORTED for every other and ESR_ERR_BAD_ARG for a
+ * null pointer, a view that is misaligned or does not hold its channels, or out0.ptr == in.ptr.
+ */
+size_t esr_packed_dw7_bytes(int c);
+int    esr_pack_dw7_f32(const float* w_c177, const float* bias, int c, void* out, size_t out_bytes);
+int    esr_dwconv7x7_supported(const esr_conv_desc* d);
+int    esr_dwconv7x7(const esr_conv_desc* d, void* hip_stream);
+
+/*
+ * esr_cx_block_s16 (additive within ABI v12; op kind ESR_OP_CX_BLOCK on esr_op.chain) -- RFDNeXt's ConvNeXt block CX
+ * (models/team38_rfdnext/rfdn_block.py:132-144) as ONE launch on 16-bit storage (cx_block_kernel, csrc/esr_cx.hip):
+ *     t   = dw7(in) + b0                      depthwise 7x7, zero padding, never stored
+ *     h   = act(W1 . t + b1)                  1x1, cin -> cmid, never stored
+ *     out = W2 . h + b2 + in                  1x1, cmid -> cout, stored to post_out
+ * t, h and out are each rounded once to the storage type, exactly where esr_dwconv7x7 and two esr_conv2d_f32 1x1s would store them; W1 and
+ * W2 are rounded once to the storage type (the separate 1x1 launches multiply by hi + lo pairs), so the result is within one rounding per
+ * stage of those launches, not bit-identical to them.  An esr_chain_desc carries it, no field added:
+ *     n_layers            3
+ *     in, cin             v and its channels, 33 .. 64 (round_up(cin, 8) channels are read from coff)
+ *     cmid                129 .. 256
+ *     cout                == cin
+ *     act, slope          ESR_ACT_LRELU and its slope (the hidden layer)
+ *     res_mode            ESR_RES_POST_ACT: `in` is added to the last layer's result
+ *     storage, compute    ESR_STORE_BF16 / ESR_COMPUTE_BF16 or ESR_STORE_F16 / ESR_COMPUTE_F16
+ *     wpacked[0..2]       esr_pack_dw7_f32, esr_pack_cx_pw1_s16 (W1 [cmid, cin], b1), esr_pack_cx_pw2_s16 (W2 [cout, cmid], b2)
+ *     post_out, post_cout the result and the channels stored: a multiple of 8 in cout .. round_up(cout, 16); channels >= cout are zeros
+ *     post_wpacked, post2_wpacked   NULL
+ * The result may not be stored into `in`'s tensor: neighbouring tiles read its halo.
+ * esr_cx_block_supported: 1 when the descriptor has this shape and a per-image input below 1 GiB; esr_cx_block_s16 returns
+ * ESR_ERR_UNSUPPORTED for every other (fp32 storage included) and ESR_ERR_BAD_ARG for a null pointer, a view that is misaligned or does not
+ * hold its channels, or post_out.ptr == in.ptr.
+ */
+size_t esr_packed_cx_pw1_bytes(int cin, int cmid);
+int    esr_pack_cx_pw1_s16(const float* w_mid_in, const float* bias, int cin, int cmid, int compute, void* out, size_t out_bytes);
+size_t esr_packed_cx_pw2_bytes(int cmid, int cout);
+int    esr_pack_cx_pw2_s16(const float* w_out_mid, const float* bias, int cmid, int cout, int compute, void* out, size_t out_bytes);
+int    esr_cx_block_supported(const esr_chain_desc* d);
+int    esr_cx_block_s16(const esr_chain_desc* d, void* hip_stream);
+
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
@@ -606,7 +655,7 @@ typedef struct esr_op {
     esr_esa_desc esa;           /* the four ESA kinds */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */
-    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP, ESR_OP_REFINE_CASCADE */
+    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP, ESR_OP_REFINE_CASCADE, ESR_OP_CX_BLOCK */
 } esr_op;
 
 /* ABI v5 -- the network input for the 16-bit plans: NCHW fp32 [n, cin <= 4, h, w] (d->in.ptr) -> NHWC 16-bit (d->out0, pitch >= 16,

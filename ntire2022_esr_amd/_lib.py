@@ -24,6 +24,8 @@ OP_MAXPOOL7S7 = 9                                                         # EFDN
 OP_DISTILL_STEP = 10                                                      # BMDN's distillation step (esr_distill_step_s16 on Op.chain)
 OP_RESBLOCK_HEAD = 11                                                     # ESAN's residual-block head (esr_resblock_head_s16 on Op.conv)
 OP_REFINE_CASCADE = 12                                                    # FasterRFDN's refinement cascade (esr_refine_cascade_s16 on Op.chain)
+OP_DWCONV7 = 13                                                           # depthwise 7x7 (esr_dwconv7x7 on Op.conv)
+OP_CX_BLOCK = 14                                                          # RFDNeXt's ConvNeXt block (esr_cx_block_s16 on Op.chain)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -146,6 +148,8 @@ EXPORTS = [
     "esr_tensor2uint_u8_chk", "esr_ssim_partials", "esr_ssim_u8",
     "esr_conv_chain_supported", "esr_conv_chain_s16", "esr_distill_step_supported", "esr_distill_step_s16",
     "esr_resblock_head_supported", "esr_resblock_head_s16", "esr_refine_cascade_supported", "esr_refine_cascade_s16",
+    "esr_packed_dw7_bytes", "esr_pack_dw7_f32", "esr_dwconv7x7_supported", "esr_dwconv7x7",
+    "esr_packed_cx_pw1_bytes", "esr_pack_cx_pw1_s16", "esr_packed_cx_pw2_bytes", "esr_pack_cx_pw2_s16", "esr_cx_block_supported", "esr_cx_block_s16",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -270,6 +274,26 @@ def lib():
     L.esr_refine_cascade_supported.restype = ci
     L.esr_refine_cascade_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
     L.esr_refine_cascade_s16.restype = ci
+    L.esr_packed_dw7_bytes.argtypes = [ci]
+    L.esr_packed_dw7_bytes.restype = sz
+    L.esr_pack_dw7_f32.argtypes = [vp, vp, ci, vp, sz]
+    L.esr_pack_dw7_f32.restype = ci
+    L.esr_dwconv7x7_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_dwconv7x7_supported.restype = ci
+    L.esr_dwconv7x7.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_dwconv7x7.restype = ci
+    L.esr_packed_cx_pw1_bytes.argtypes = [ci, ci]
+    L.esr_packed_cx_pw1_bytes.restype = sz
+    L.esr_pack_cx_pw1_s16.argtypes = [vp, vp, ci, ci, ci, vp, sz]
+    L.esr_pack_cx_pw1_s16.restype = ci
+    L.esr_packed_cx_pw2_bytes.argtypes = [ci, ci]
+    L.esr_packed_cx_pw2_bytes.restype = sz
+    L.esr_pack_cx_pw2_s16.argtypes = [vp, vp, ci, ci, ci, vp, sz]
+    L.esr_pack_cx_pw2_s16.restype = ci
+    L.esr_cx_block_supported.argtypes = [ctypes.POINTER(ChainDesc)]
+    L.esr_cx_block_supported.restype = ci
+    L.esr_cx_block_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
+    L.esr_cx_block_s16.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

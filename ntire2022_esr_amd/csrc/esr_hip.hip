@@ -1198,6 +1198,8 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_DISTILL_STEP: return esr_distill_step_s16(&op.chain, hip_stream);
         case ESR_OP_RESBLOCK_HEAD: return esr_resblock_head_s16(&op.conv, hip_stream);
         case ESR_OP_REFINE_CASCADE: return esr_refine_cascade_s16(&op.chain, hip_stream);
+        case ESR_OP_DWCONV7: return esr_dwconv7x7(&op.conv, hip_stream);
+        case ESR_OP_CX_BLOCK: return esr_cx_block_s16(&op.chain, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

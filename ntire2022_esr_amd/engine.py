@@ -214,6 +214,70 @@ def pack_dw(weight, bias):
     return out
 
 
+def pack_dw7(weight, bias):
+    """Depthwise [C,1,7,7] weights + bias -> [tap][cp] + bias[cp], cp = round_up(C, 8) (esr_pack_dw7_f32)."""
+    lib = L.lib()
+    a = _pack_args(weight, bias)
+    c = a.w.shape[0]
+    assert tuple(a.w.shape[1:]) == (1, 7, 7)
+    nbytes = lib.esr_packed_dw7_bytes(c)
+    out = torch.empty(nbytes // 4, dtype=torch.float32)
+    L.check(lib.esr_pack_dw7_f32(_ptr(a.w), _ptr(a.b), c, _ptr(out), nbytes), "esr_pack_dw7_f32")
+    return out
+
+
+def unpack_dw7(blob, c):
+    """[C,1,7,7] weights and bias of a pack_dw7 blob (tests)."""
+    blob = _host(blob)
+    cp = (c + 7) // 8 * 8
+    img = blob[:49 * cp].reshape(49, cp)
+    return img[:, :c].t().reshape(c, 1, 7, 7).contiguous(), blob[49 * cp:49 * cp + c].clone()
+
+
+def pack_cx_pw(w1, b1, w2, b2, compute):
+    """The two 1x1s of a ConvNeXt block for esr_cx_block_s16: w1 [cmid, cin(, 1, 1)] -> esr_pack_cx_pw1_s16 blob, w2 [cout, cmid(, 1, 1)] ->
+    esr_pack_cx_pw2_s16 blob whose K order is the one in which cx_block_kernel's first GEMM leaves the hidden channels in a lane.  Both are
+    rounded once to the storage type; the biases stay fp32.  Returns (blob1, blob2)."""
+    lib = L.lib()
+    a1 = _pack_args(w1, b1, compute=compute, flat=True)
+    a2 = _pack_args(w2, b2, compute=compute, flat=True)
+    cmid, cin = a1.w.shape
+    cout, cmid2 = a2.w.shape
+    if cmid2 != cmid:
+        raise L.EsrError("pack_cx_pw: w2 must take w1's outputs")
+    n1, n2 = lib.esr_packed_cx_pw1_bytes(cin, cmid), lib.esr_packed_cx_pw2_bytes(cmid, cout)
+    if not n1 or not n2:
+        raise L.EsrError("pack_cx_pw: unsupported shape")
+    o1, o2 = torch.empty(n1 // 4, dtype=torch.float32), torch.empty(n2 // 4, dtype=torch.float32)
+    L.check(lib.esr_pack_cx_pw1_s16(_ptr(a1.w), _ptr(a1.b), cin, cmid, a1.compute, _ptr(o1), n1), "esr_pack_cx_pw1_s16")
+    L.check(lib.esr_pack_cx_pw2_s16(_ptr(a2.w), _ptr(a2.b), cmid, cout, a2.compute, _ptr(o2), n2), "esr_pack_cx_pw2_s16")
+    return o1, o2
+
+
+def cx_pw_fragments(blob1, blob2, cmid, compute):
+    """The MFMA fragment images of a pack_cx_pw pair as float64 arrays (tests): A1 [2 nhp, 2, 64, 8] and b1 [32 nhp] of the first 1x1 --
+    fragment (output tile, K step), lane, element --, A2 [nhp, 4, 64, 8] and b2 [64] of the second, nhp = ceil(cmid / 32)."""
+    nhp = (cmid + 31) // 32
+    dt = torch.bfloat16 if compute == "bf16" else torch.float16
+    out = []
+    for blob, shape, nb in ((blob1, (2 * nhp, 2, 64, 8), 32 * nhp), (blob2, (nhp, 4, 64, 8), 64)):
+        raw = blob.detach().to("cpu").contiguous().view(torch.uint8)
+        img = raw[:nhp * 4096].view(dt).to(torch.float64).reshape(shape).numpy()
+        bias = raw[nhp * 4096:nhp * 4096 + 4 * nb].view(torch.float32).to(torch.float64).numpy()
+        out += [img, bias]
+    return tuple(out)
+
+
+def fold_center(w_r, b_r, w_d, b_d):
+    """A 3x3 and a 1x1 over the same input as ONE 3x3: W_r + the 1x1 on the centre tap, b_r + b_d, both summed in fp32
+    (RFDNeXt: rc_1 = c1_r(x) + c1_d(x))."""
+    w = w_r.detach().to("cpu", torch.float32).clone()
+    w[:, :, 1, 1] += w_d.detach().to("cpu", torch.float32).reshape(w.shape[0], w.shape[1])
+    zero = torch.zeros(w.shape[0])
+    b = (zero if b_r is None else b_r.detach().to("cpu", torch.float32)) + (zero if b_d is None else b_d.detach().to("cpu", torch.float32))
+    return w, b
+
+
 def unpack_conv(blob, cin, cout, k, cin_map=None, cin_phys=None):
     blob = _host(blob)
     a = _pack_args(cin=cin, cin_map=cin_map, cin_phys=cin_phys)
@@ -324,6 +388,8 @@ HEAD = "#head"     # a 16-bit plan's head conv reads `<path>#head#s16` (pack_hea
 DENSE = "#dense"   # esr_pack_dense_f32 blob of a layer of the fused ESA branch (EsaLayer)
 WINO = "#wino"     # esr_pack_wino_f32 blob of an fp32 3x3 (Winograd F(2x2, 3x3))
 DWPAD = "#pad16"   # pack_dw image of a depthwise 3x3 of fewer than 16 channels, zero-padded to 16 (Dw: low-resolution maps stored whole)
+CX1 = "#cx1"       # esr_pack_cx_pw1_s16 image of a ConvNeXt block's first 1x1 (CxBlock; pack_cx_pw)
+CX2 = "#cx2"       # esr_pack_cx_pw2_s16 image of its second 1x1
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -655,6 +721,36 @@ class Dw(_Op):
         npix, e_act = (plan.npix, plan.esize) if self.hw is None else (plan.n * self.hw[0] * self.hw[1], 4)
         return _cost(self.w, "dwconv3x3_kernel", self.c, self.c, 3, 2.0 * 9 * self.c * npix, float(npix * e_act * self.c),
                      float(npix * e_act * self.c))
+
+
+@dataclass
+class Dw7(_Op):
+    """depthwise 7x7 + bias (esr_dwconv7x7) -- see Plan.dwconv7.  The blob `w` is pack_dw7's."""
+    w: str
+    src: object
+    dst: object
+    c: int
+    kind = "dw7"
+
+    def encode(self, op, plan, base, weights):
+        op.kind = L.OP_DWCONV7
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        d.cin = d.cout = self.c
+        d.ksize = 7
+        d.in_layout = d.out_layout = L.NHWC
+        d.inp, d.out0 = _view(self.src, base), _view(self.dst, base)
+        d.storage = L.STORE[plan.store]
+        d.wpacked = ctypes.c_void_p(weights[self.w].data_ptr())
+
+    def cost(self, plan, desc):
+        npix, es = plan.npix, plan.esize
+        return _cost(self.w, f"dwconv7x7_kernel<{L.STORE[plan.store]}>", self.c, self.c, 7, 2.0 * 49 * self.c * npix,
+                     float(npix * es * self.c) + 4.0 * 50 * self.c, float(npix * es * self.c),
+                     float(npix * es * (_stored_channels(self.src, self.c, 8) + _stored_channels(self.dst, self.c, 8))) + 4.0 * 50 * self.c)
+
+    def counted_convs(self, plan):            # nn.Conv2d(c, c, 7, groups=c): one input channel per filter
+        return [(1, self.c, 7, plan.npix, L.ACT_NONE)]
 
 
 @dataclass
@@ -1033,6 +1129,46 @@ class Cascade(_Fused):
 
 
 @dataclass
+class CxBlock(_Fused):
+    """RFDNeXt's ConvNeXt block as ONE esr_cx_block_s16 op -- see Plan.cx_block (cx_block_kernel).  replaces: [dw7, pw1, pw2]."""
+    kind = "cx"
+    predicate, field, what = "esr_cx_block_supported", "chain", "ConvNeXt block"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 3 and sub[0].kind == "dw7" and all(o.kind == "conv" and o.k == 1 and o.post is None and o.tail is None and not o.hilo
+                                                              and o.hw is None for o in sub[1:])
+        dw, pw1, pw2 = sub
+        assert pw1.act == L.ACT_LRELU and pw1.res is None and pw2.act == L.ACT_NONE
+        assert pw2.res_mode == L.RES_PRE_ACT and _same_view(pw2.res, dw.src)       # + v (no activation behind it: pre == post)
+        assert _same_view(pw1.src, dw.dst) and _same_view(pw2.src, pw1.dst) and pw1.cin == dw.c and pw2.cin == pw1.cout and pw2.cout == dw.c
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        dw, pw1, pw2 = self.replaces
+        op.kind = L.OP_CX_BLOCK
+        d = op.chain
+        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 3
+        d.cin, d.cmid, d.cout = dw.c, pw1.cout, pw2.cout
+        d.act, d.slope, d.res_mode = L.ACT_LRELU, pw1.slope, L.RES_POST_ACT
+        d.storage = d.compute = st
+        d.inp = _view(dw.src, base)
+        d.wpacked[0] = weights[dw.w].data_ptr()
+        d.wpacked[1] = weights[pw1.w + CX1].data_ptr()
+        d.wpacked[2] = weights[pw2.w + CX2].data_ptr()
+        d.post_out, d.post_cout = _view(pw2.dst, base), _stored_width(pw2.dst, pw2.cout)
+
+    def cost(self, plan, desc):             # v read once, the result written once
+        dw, pw1, pw2 = self.replaces
+        npix, es = plan.npix, plan.esize
+        flops = 2.0 * npix * (49 * dw.c + pw1.cin * pw1.cout + pw2.cin * pw2.cout)
+        wb = 4.0 * (50 * dw.c + pw1.cin * pw1.cout + pw2.cin * pw2.cout)
+        kern = f"cx_block_kernel<{_tf(plan.store == 'bf16')}>"
+        stored = float(npix * es * (_stored_channels(dw.src, dw.c, 8) + _stored_channels(pw2.dst, pw2.cout, 8))) + wb
+        return _cost(dw.w, kern, dw.c, pw2.cout, 7, flops, float(npix * dw.c * es) + wb, float(npix * es * pw2.cout), stored)
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1131,6 +1267,16 @@ class Plan:
         self.buffers.append(b)
         return b
 
+    def release(self, bufs):
+        """Gives back full-resolution buffers that no op of the plan addresses (a fused op made the launches between which they lived
+        unnecessary).  They must be the plan's LAST allocations, in order: the arena then simply ends in front of them, and no other
+        buffer moves or falls outside it -- anything else raises."""
+        k = len(bufs)
+        if not k or len(self.buffers) < k or any(a is not b or b.arena != 0 for a, b in zip(self.buffers[-k:], bufs)):
+            raise L.EsrError("Plan.release: only the plan's last full-resolution allocations can be given back")
+        del self.buffers[-k:]
+        self.total = bufs[0].offset
+
     def planar(self, name, nseg, seg_pitch):
         """nseg equal full-resolution buffers back to back (see Planar); 16-bit plans only"""
         assert self.esize == 2 and seg_pitch % 8 == 0            # (whole 16-byte granules; a tight pitch -- 56 -- is not whole K chunks)
@@ -1153,6 +1299,11 @@ class Plan:
 
     def dwconv(self, wname, src, dst, c, **kw):
         self.ops.append(Dw(wname, src, dst, c, **kw))
+
+    def dwconv7(self, wname, src, dst, c):
+        """nn.Conv2d(c, c, 7, 1, 3, groups=c) with bias, every storage (esr_dwconv7x7); `wname` names a pack_dw7 blob.  dst is another
+        tensor than src."""
+        self.ops.append(Dw7(wname, src, dst, c))
 
     def bsconv(self, pw, dw, src, dst, cin, c, **kw):
         self.ops.append(Bs(pw, dw, src, dst, cin, c, **kw))
@@ -1227,6 +1378,14 @@ class Plan:
         attached as `replaces`: weights, complexity counters and algorithmic costs are theirs; the result is bit-identical to running them
         one by one.  d3 and r4 must not be stored into d2's tensor: the neighbouring tiles read its halo."""
         return self._fuse(mark, Cascade)
+
+    def cx_block(self, mark):
+        """The three ops appended since `mark = len(plan.ops)` -- a ConvNeXt block in its per-layer form, t = dw7(v), h = lrelu(pw1(t)),
+        out = pw2(h) + v (team38_rfdnext/rfdn_block.py:132-144) -- as ONE esr_cx_block_s16 op (16-bit plans): v is read once, out is
+        written once, t and the 4x-wide h never exist.  The ops stay attached as `replaces`: complexity counters and algorithmic costs are
+        theirs; the 1x1 blobs are pack_cx_pw's (`<pw1>#cx1`, `<pw2>#cx2`).  Not bit-identical to the per-layer launches: the 1x1 weights
+        are rounded once where conv_s16_kernel multiplies by hi + lo pairs.  out must not be stored into v's tensor."""
+        return self._fuse(mark, CxBlock)
 
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
@@ -1363,6 +1522,7 @@ class HipSRModel(nn.Module):
         self._fuse_step = True     # 16-bit BMDN plans: a distillation step as one esr_distill_step_s16 launch (Plan.distill_step); measured: DESIGN.md 7d
         self._fuse_head = True     # 16-bit ESAN plans: a residual block's head as one esr_resblock_head_s16 launch (Plan.resblock_head); measured: DESIGN.md 7e
         self._fuse_cascade = False # 16-bit FasterRFDN plans: FRFDB's refinement path as one esr_refine_cascade_s16 launch (Plan.refine_cascade); OFF: faster on one image, not at 32 x 256 x 256
+        self._fuse_cx = True       # 16-bit RFDNeXt plans: the ConvNeXt block as one esr_cx_block_s16 launch (Plan.cx_block); measured: DESIGN.md 7g
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
         self._prof_passes = 0      # >0: record HIP events around every op (bench roofline leg)
@@ -1421,6 +1581,7 @@ class HipSRModel(nn.Module):
     fuse_step = property(lambda self: self._fuse_step, lambda self, v: self._set_flag("_fuse_step", v))
     fuse_head = property(lambda self: self._fuse_head, lambda self, v: self._set_flag("_fuse_head", v))
     fuse_cascade = property(lambda self: self._fuse_cascade, lambda self, v: self._set_flag("_fuse_cascade", v))
+    fuse_cx = property(lambda self: self._fuse_cx, lambda self, v: self._set_flag("_fuse_cx", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels

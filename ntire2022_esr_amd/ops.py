@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .engine import pack_conv, pack_conv_s16, pack_distill_s16, pack_post_s16, pack_wino
+from .engine import pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw7, pack_post_s16, pack_wino
 
 
 def _view(t, coff=0):
@@ -419,6 +419,66 @@ def refine_cascade(d2, w2r, b2r, w3d, b3d, w3r, b3r, w4, b4, *, slope=0.05, in_c
     stream = torch.cuda.current_stream(d2.device).cuda_stream
     _launch("esr_refine_cascade_s16", "esr_refine_cascade_s16", d, stream, L.OP_REFINE_CASCADE, "chain")
     return d3, r4
+
+
+def dwconv7x7(x, weight, bias, *, in_coff=0, out=None, out_coff=0, packed=None):
+    """esr_dwconv7x7: depthwise nn.Conv2d(C, C, 7, 1, 3, groups=C) with zero padding and bias on an NHWC tensor x [N, H, W, P] (C channels
+    from in_coff) in fp32, bf16 or fp16 storage: fp32 sums in (ky, kx) ascending order, the bias last, one rounding.  weight [C, 1, 7, 7].
+    out: a caller-provided NHWC tensor of x's dtype and device (another tensor than x) that receives the result from channel out_coff;
+    default: freshly allocated zeros of pitch round_up(C, granule).  The pad channels up to the granule (4 fp32 / 8 16-bit) are stored as zeros."""
+    if not x.is_cuda:
+        raise L.EsrError("dwconv7x7: tensors must live on the GPU; there is no CPU fallback")
+    lib = L.lib()
+    st = _STORE_OF[x.dtype]
+    gran = 4 if st == "f32" else 8
+    n, h, w, _ = x.shape
+    c = weight.shape[0]
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, h, w, c, c, 7
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = L.STORE[st]
+    d.inp = _view(x, in_coff)
+    keep = pack_dw7(weight, bias).to(x.device) if packed is None else packed
+    d.wpacked = keep.data_ptr()
+    y = _zeros_or(out, "dwconv7x7: out", x, (n, h, w), (c + gran - 1) // gran * gran, gran)
+    d.out0 = _view(y, out_coff)
+    if not lib.esr_dwconv7x7_supported(ctypes.byref(d)):
+        raise L.EsrError("dwconv7x7: no kernel for this shape (esr_dwconv7x7_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_dwconv7x7", "esr_dwconv7x7", d, stream, L.OP_DWCONV7, "conv")
+    return y
+
+
+def cx_block(v, w0, b0, w1, b1, w2, b2, *, slope=0.05, in_coff=0, out=None, out_coff=0, out_channels=None, store=None):
+    """esr_cx_block_s16: a ConvNeXt block (team38_rfdnext/rfdn_block.py:132-144) in ONE launch on a 16-bit NHWC tensor v [N, H, W, P] (C
+    channels from in_coff): t = dw7(v, w0, b0), h = lrelu(w1 . t + b1), out = w2 . h + b2 + v, each of t, h and out rounded once to the
+    storage type, v zero-padded.  w0 [C, 1, 7, 7], w1 [M, C(, 1, 1)], w2 [C, M(, 1, 1)]; 33 <= C <= 64, 129 <= M <= 256.
+    out: a caller-provided NHWC tensor of v's dtype and device, never v itself, that receives the result from channel out_coff; default:
+    freshly allocated zeros of pitch round_up(C, 8).  out_channels: the channels stored (default round_up(C, 8); those >= C are zeros).
+    store: "bf16" | "f16", if given it must be v's storage type."""
+    st = _s16_store(v, "cx_block")
+    if store is not None and store != st:
+        raise L.EsrError(f"cx_block: store {store!r}, v is stored as {st}")
+    lib = L.lib()
+    n, h, w, _ = v.shape
+    c, m = w0.shape[0], w1.shape[0]
+    d = L.ChainDesc()
+    d.n, d.h, d.w, d.n_layers = n, h, w, 3
+    d.cin, d.cmid, d.cout = c, m, w2.shape[0]
+    d.act, d.slope, d.res_mode = L.ACT_LRELU, slope, L.RES_POST_ACT
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(v, in_coff)
+    keep = [pack_dw7(w0, b0).to(v.device)] + [p.to(v.device) for p in pack_cx_pw(w1, b1, w2, b2, st)]
+    for i, k in enumerate(keep):
+        d.wpacked[i] = k.data_ptr()
+    d.post_cout = (d.cout + 7) // 8 * 8 if out_channels is None else out_channels
+    y = _zeros_or(out, "cx_block: out", v, (n, h, w), d.post_cout, 8)
+    d.post_out = _view(y, out_coff)
+    if not lib.esr_cx_block_supported(ctypes.byref(d)):
+        raise L.EsrError("cx_block: no kernel for this shape (esr_cx_block_supported)")
+    stream = torch.cuda.current_stream(v.device).cuda_stream
+    _launch("esr_cx_block_s16", "esr_cx_block_s16", d, stream, L.OP_CX_BLOCK, "chain")
+    return y
 
 
 def _hilo_pair(t, what, strides):
