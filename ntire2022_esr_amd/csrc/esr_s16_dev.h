@@ -142,7 +142,9 @@ __device__ __forceinline__ f32x4 unpack4(uint2 u)
 
 // GELU for the 16-bit storage modes: x * Phi(x) with Phi(x) - 0.5 = x * P(x^2), P a degree-7 minimax polynomial on |x| <= 4
 // (|error| of Phi <= 2.1e-5, tools/fit_gelu.py), the argument clamped to [-4, 4] and the factor x to [-4, inf): |gelu error| <=
-// 1.3e-4 for x <= 4 and 5.3e-5 x beyond, about one fp16 step of the values that matter, far below a bf16 step -- and 11 plain VALU instructions
+// 1.3e-4 for -4 <= x <= 4 (8.6e-5 over the 16-bit values), 5.33e-5 x beyond +4, and 2.13e-4 below -4 -- there the result is the constant
+// -4 (0.5 - 4 P(16)) = -2.127e-4 while GELU(x) -> 0 (tests/_sweep.py gelu16_cpu over every finite bf16 / fp16 value; the MI355X returns the
+// emulation's bits, tests/test_gpu_value_sweep.py) -- about one fp16 step of the values that matter, far below a bf16 step -- and 11 plain VALU instructions
 // (packable two values at a time) instead of libm erff's ~40 or the 16 + v_rcp + v_exp of an erf approximation.  The fp32
 // path keeps erff.
 __device__ __forceinline__ __attribute__((unused)) float gelu16(float x)       // the scalar definition (esr_bsconv.hip uses it as is)
