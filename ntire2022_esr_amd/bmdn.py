@@ -19,11 +19,12 @@ A distillation step has two forms (model.fuse_step):
            3x3s run as one over cat[r, d_j] (engine.pack_distill_s16), t never exists.  On by default in 16-bit plans: 17 % / 34 % faster
            forwards at 32 x 256 x 256 / one 339 x 510 image in bf16.
 Which form a plan takes depends on the per-image shape and esr_distill_step_supported only, never on the batch size.
+
+The long skip (team37_bmdn.py:214), the concats and ESA's low-resolution branch are the shared frame's (frame.py).
 """
 from . import _lib as L
-from .engine import FOLD, INPUT, OUTPUT, EsaLayer, HipSRModel, Post
-from .rfdn import _slice_map
-from .rlfn import FP, _lowres, _pad8
+from .engine import FOLD, HipSRModel, Post
+from .frame import FP, Concat, EsaBranch, LongSkip, _pad8, _slice_map, block_cin_map, check_input, set_scale
 
 
 class BMDN(HipSRModel):
@@ -58,39 +59,28 @@ class BMDN(HipSRModel):
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'BMDN expects {self.in_nc} input channels, got {c}')
-        if plan.h < 15 or plan.w < 15:
-            raise L.EsrError('ESA needs H, W >= 15 (3x3/s2 then 7x7/s3 pooling)')
+        check_input('BMDN', plan, c, self.in_nc)
         nf, dc, f, DP = self.nf, self.dc, self.f, self.DP
         s16 = plan.esize == 2
         KP = plan.cpad(nf)                                # 40 fp32 channels / 48 16-bit channels: whole K chunks
         P = _pad8(nf) if (s16 and self.tight_pitch) else KP          # 16-bit storage: the nf-wide tensors at the tight pitch (rfdn.py)
         RP = plan.cpad(dc)                                # the 20-channel refinement tensors: 24 fp32 / 32 16-bit channels
-        h2, w2, h3, w3 = _lowres(plan.h, plan.w)
-        # bf16: `fea` and `out_lr` -- the long skip, team37_bmdn.py:214 -- are hi + lo pairs (Plan.pair: two dense tensors)
-        hl = self._skip_hilo(plan, nf)
-        fea2 = plan.pair('fea', P) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', P)
-        out_lr2 = plan.pair('out_lr', P) if hl else None
+        skip = LongSkip(plan, self, nf, P)
         # the four block outputs (team37_bmdn.py:213) and d1 d2 d3 r4 (:175): dense tensors in the 16-bit modes (engine.Planar), slices in fp32
-        bcat = plan.planar('bcat', 4, P) if s16 else plan.buffer('bcat', 4 * P)
-        cat = plan.planar('cat', 4, DP) if s16 else plan.buffer('cat', _pad8(4 * DP))
-        cs = (lambda j: cat.seg(j)) if s16 else (lambda j: (cat[j * DP:(j + 1) * DP]))
+        bcat = Concat(plan, 'bcat', 4, P, s16)
+        cat = Concat(plan, 'cat', 4, DP, s16, _pad8(4 * DP))
+        cs = cat.seg
         ra, rb, t = plan.buffer('ra', RP), plan.buffer('rb', RP), plan.buffer('t', RP)
         v = plan.buffer('v', P)
-        lr = None if hl else plan.buffer('lr', P)
-        c1 = plan.buffer('esa_c1', FP)
-        lo2 = plan.buffer('esa_s2', FP, h2, w2)
-        la, lb = plan.buffer('esa_a', FP, h3, w3), plan.buffer('esa_b', FP, h3, w3)
+        lr = None if skip.hl else plan.buffer('lr', P)
+        esa = EsaBranch(plan, f)
+        c1 = esa.c1
         relu = dict(act=L.ACT_RELU)
-        lo = dict(hw=(h3, w3))
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, hilo=L.HILO_OUT if hl else 0)
-        cur = fea
+        skip.head('fea_conv', self.in_nc)
+        cur = skip.fea
         for k in range(1, 5):
             b = f'B{k}.'
             r = cur
@@ -109,36 +99,19 @@ class BMDN(HipSRModel):
             plan.conv(b + 'c4', r, cs(3), dc, dc, **relu)
             if s16 and (nf + 15) // 16 in (3, 4) and f <= 16:
                 # 16-bit storage: esa.conv1 rides in c5's epilogue on the fp32 tile (one launch less per block)
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
                 plan.conv(b + 'esa.conv1', v, c1, nf, f, k=1)
-            mark = len(plan.ops)
-            plan.conv3x3s2(b + 'esa.conv2', c1, lo2, f)
-            plan.maxpool7s3(lo2, la)
-            plan.conv(b + 'esa.conv_max', la, lb, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'esa.conv3', lb, la, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'esa.conv3_', la, lb, f, f, **lo)
-            if self.fuse_esa_lowres:
-                # the five launches above as one op of two (halo recompute; only the pooled map reaches memory)
-                plan.esa_lowres(mark, c1, la, lb, f, b + 'esa.conv2',
-                                [EsaLayer(0, L.ACT_RELU, b + 'esa.conv_max'), EsaLayer(0, L.ACT_RELU, b + 'esa.conv3'),
-                                 EsaLayer(0, L.ACT_NONE, b + 'esa.conv3_')])
-            out = bcat.seg(k - 1) if s16 else bcat[(k - 1) * P:k * P]
-            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lb, out, nf, f)
+            c3 = esa.lowres(b + 'esa.conv2', [(b + 'esa.conv_max', L.ACT_RELU), (b + 'esa.conv3', L.ACT_RELU), (b + 'esa.conv3_', L.ACT_NONE)],
+                            self.fuse_esa_lowres)
+            out = bcat.seg(k - 1)
+            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, c3, out, nf, f)
             cur = out
-        plan.conv('c.0', bcat, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **relu)
-        if hl:
-            plan.conv('LR_conv', v, out_lr2, nf, nf, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.0', out_lr2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('LR_conv', v, lr, nf, nf, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('upsampler.0', lr, OUTPUT, nf, self.out_nc * 16)
+        plan.conv('c.0', bcat.whole, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **relu)
+        skip.close('LR_conv', 'upsampler.0', v, lr, self.out_nc * 16)
 
-    def _cin_map(self, path, cin_map, store):
-        if path == 'c.0':                                 # the block-output slices are as wide as the storage type's K chunks
-            return _slice_map(self.num_modules, self.nf, _pad8(self.nf) if store == "f32" else (self.nf + 15) // 16 * 16)
-        return cin_map
+    _cin_map = block_cin_map
 
     def _extra_pack(self, packed, device):
         if self._store() != "f32" and self.fuse_step:
@@ -147,12 +120,3 @@ class BMDN(HipSRModel):
                 for j in (1, 2, 3):
                     cr, cb = self._leaf(f'B{k}.c{j}_r'), self._leaf(f'B{k}.c{j}_b')
                     packed[f'B{k}.c{j}_r' + FOLD] = pack_distill_s16(cr.weight, cr.bias, cb.weight, cb.bias, self._store()).to(device)
-
-    def _counted_convs(self, plan, o):
-        """logical channel counts for the padded-concat 1x1 convs (the reference sees 80 / 160 inputs)"""
-        r = super()._counted_convs(plan, o)
-        if o.kind == "conv" and o.w.endswith('.c5'):
-            return [(self.dc * 4, o.cout, 1, plan.npix, o.act)] + r[1:]
-        if o.kind == "conv" and o.w == 'c.0':
-            return [(self.nf * self.num_modules, o.cout, 1, plan.npix, o.act)]
-        return r

@@ -12,12 +12,14 @@ weights W[c,k,tap] = dw[c,tap] * pw[c,k] -- at 16x the fp32 matrix rate the 9x l
 depthwise pass (0.12 ms against bsconv_kernel's 0.37 ms per launch at 32x256x256, C = 48).  The depthwise conv zero-pads the
 pointwise OUTPUT (bias included), which a dense conv of the input cannot express at the image border: the bias term goes
 through esr_conv_desc.border_bias (a 16-row table indexed by which sides of the pixel lie outside), see _merged_bsconv.
+The long skip (team18_bsrn.py:231-234), the two concats and ESA's maps are the shared frame's (frame.py); the ESA layers here are pointwise +
+depthwise pairs through a third map, and the LR conv is a BSConvU.
 """
 import torch
 
 from . import _lib as L
-from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Planar, Post, Tail, pack_apply_post, pack_conv, pack_conv_s16, pack_head_s16
-from .rlfn import FP, _lowres, _pad8
+from .engine import INPUT, EsaLayer, HipSRModel, Planar, Post, Tail, pack_apply_post, pack_conv, pack_conv_s16, pack_head_s16
+from .frame import FP, Concat, EsaBranch, LongSkip, check_input
 
 
 class BSRN(HipSRModel):
@@ -135,12 +137,8 @@ class BSRN(HipSRModel):
                                                                      None if nd is None else nd.bias, self._store()).to(device)
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'BSRN expects {self.in_nc} input channels, got {c}')
-        if plan.h < 15 or plan.w < 15:
-            raise L.EsrError('ESA needs H, W >= 15 (3x3/s2 then 7x7/s3 pooling)')
+        check_input('BSRN', plan, c, self.in_nc)
         C, dc, f, nb = self.C, self.dc, self.f, self.nb
-        h2, w2, h3, w3 = _lowres(plan.h, plan.w)
         g = dict(act=L.ACT_GELU)
         merged = plan.esize == 2
         # the post-chain kernel variants that exist: 3 main tiles (C in 33..48) with a 2-tile post (dc in 17..32)
@@ -148,44 +146,37 @@ class BSRN(HipSRModel):
 
         def bs3(path, src, dst, cin, cout, **kw):
             plan.conv(path + '#bs3', src, dst, cin, cout, k=3, border=path + '#bs3#border', bs_of=path, **kw)
-        # bf16: `fea` and `out_lr` -- the long skip, team18_bsrn.py:231-234 -- are hi + lo pairs (Plan.pair: two dense tensors)
-        hl = merged and self._skip_hilo(plan, C)
-        fea2 = plan.pair('fea', plan.cpad(C)) if hl else None
-        out_lr2 = plan.pair('out_lr', plan.cpad(C)) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', C)
+        skip = LongSkip(plan, self, C, C, pair_pitch=plan.cpad(C))
         # block outputs, team18_bsrn.py:226.  16-bit storage: nb dense tensors (engine.Planar) -- as C-channel slices of one [.., nb C]
         # buffer every block wrote 96 of 384 bytes per pixel (partial lines) and the next block's first convolutions read them back
         # at 1.7x their algorithmic bytes (profiles/pmc_traffic.json, r03b)
         bplanar = merged and C % 16 == 0
-        bcat = plan.planar('bcat', nb, C) if bplanar else plan.buffer('bcat', nb * C)
+        bcat = Concat(plan, 'bcat', nb, C, bplanar)
         # d1 d2 d3 r4, team18_bsrn.py:166.  16-bit storage: four dense tensors of DP = round_up(dc, 16) channels (engine.Planar):
         # a dc-channel slice of a [.., 4 dc] buffer is a partial-line store (48 of 192 bytes per pixel), 2.3x the cost of a dense one
         DP = (dc + 15) // 16 * 16
-        cat = plan.planar('cat', 4, DP) if merged else plan.buffer('cat', 4 * dc)
-        cs = (lambda j: cat.seg(j)) if merged else (lambda j: cat[j * dc:(j + 1) * dc])
+        cat = Concat(plan, 'cat', 4, DP if merged else dc, merged)
+        cs = cat.seg
         t = None if merged else plan.buffer('t', C)       # pointwise result feeding the head's depthwise
         r1, r2, v, u = plan.buffer('r1', C), plan.buffer('r2', C), plan.buffer('v', C), plan.buffer('u', C)
-        c1 = plan.buffer('esa_c1', FP)
-        lo2 = plan.buffer('esa_s2', FP, h2, w2)
-        la, lb, lt = (plan.buffer(n, FP, h3, w3) for n in ('esa_a', 'esa_b', 'esa_t'))
-        lo = (h3, w3)
+        esa = EsaBranch(plan, f)
+        c1, lo2, la, lb, lo = esa.c1, esa.s2, esa.a, esa.b, esa.hw
+        lt = plan.buffer('esa_t', FP, *lo)                # the pointwise results feeding the branch's depthwise convolutions
         # a block's FIRST distillation Linear + GELU (c1_d reads the block input) rides in the epilogue of the launch that produces
         # that input: the head for block 1, the previous block's conv_out for the others (one launch and one read of the tensor less)
         apply_out = fuse_d and bplanar and bool(L.lib().esr_esa_apply_post_supported(C, C, dc))
         def first_d(k):
             return Post(f'B{k}.c1_d', cs(0), dc, L.ACT_GELU) if fuse_d else None
-        if hl:
-            plan.conv('fea_conv#bs3', INPUT, fea2, self.in_nc, C, k=3, border='fea_conv#bs3#border', bs_of='fea_conv', post=first_d(1), hilo=L.HILO_OUT)
-        elif merged:
-            plan.conv('fea_conv#bs3', INPUT, fea, self.in_nc, C, k=3, border='fea_conv#bs3#border', bs_of='fea_conv', post=first_d(1))
+        if merged:
+            skip.head('fea_conv#bs3', self.in_nc, k=3, border='fea_conv#bs3#border', bs_of='fea_conv', post=first_d(1))
         else:
             plan.conv('fea_conv.pw', INPUT, t, self.in_nc, C, counted=False)
-            plan.dwconv('fea_conv.dw', t, fea, C)
+            plan.dwconv('fea_conv.dw', t, skip.fea, C)
         # ESDB's tail -- c4 (BSConvU + GELU) -> cat(d1, d2, d3, r4) -> c5 -> esa.conv1, team18_bsrn.py:165-171, :109 -- as ONE launch
         # (rfdb_tail_kernel<.., 3, true>, ABI v12): r4 never reaches memory; from 256 tiles of 16 x 16
         fused_tail = (self.fuse_tail and merged and 32 < C <= 48 and DP == 32 and dc <= 32 and f <= 16 and FP == 16
                       and plan.n * ((plan.w + 15) // 16) * ((plan.h + 15) // 16) >= 256)
-        cur = fea
+        cur = skip.fea
         for k in range(1, nb + 1):
             b = f'B{k}.'
             src = cur
@@ -207,7 +198,7 @@ class BSRN(HipSRModel):
                                 distill=Post(b + f'c{j}_d', cs(j - 1), dc, L.ACT_GELU), **g)
             if fused_tail:
                 bs3(b + 'c4', r1, v, C, dc,
-                    tail=Tail(b + 'c5#tail', Planar(cat.segs[:3]), 3 * DP, 3 * dc, C, L.ACT_GELU),
+                    tail=Tail(b + 'c5#tail', Planar(cat.whole.segs[:3]), 3 * DP, 3 * dc, C, L.ACT_GELU),
                     post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             elif merged:
                 bs3(b + 'c4', r1, cs(3), C, dc, **g)
@@ -217,10 +208,10 @@ class BSRN(HipSRModel):
                 pass
             elif plan.esize == 2 and (C + 15) // 16 in (3, 4) and f <= 16:
                 # 16-bit storage: esa.conv1 rides in c5's epilogue on the fp32 tile (one launch less per block)
-                plan.conv(b + 'c5', cat, v, 4 * DP if merged else 4 * dc, C, k=1, counted=False, cin_alg=4 * dc,
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP if merged else 4 * dc, C, k=1, counted=False, cin_alg=4 * dc,
                           post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
-                plan.conv(b + 'c5', cat, v, 4 * DP if merged else 4 * dc, C, k=1, counted=False, cin_alg=4 * dc)
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP if merged else 4 * dc, C, k=1, counted=False, cin_alg=4 * dc)
                 plan.conv(b + 'esa.conv1', v, c1, C, f, k=1, counted=False)
             mark = len(plan.ops)
             plan.conv3x3s2(b + 'esa.conv2', c1, lo2, f)
@@ -237,7 +228,7 @@ class BSRN(HipSRModel):
                                 [EsaLayer(1, L.ACT_GELU, b + 'esa.conv_max.pw', b + 'esa.conv_max.dw'),
                                  EsaLayer(1, L.ACT_GELU, b + 'esa.conv3.pw', b + 'esa.conv3.dw'),
                                  EsaLayer(1, L.ACT_NONE, b + 'esa.conv3_.pw', b + 'esa.conv3_.dw')])
-            out = bcat.seg(k - 1) if bplanar else bcat[(k - 1) * C:k * C]
+            out = bcat.seg(k - 1)
             if apply_out:
                 # conv_out (. cw, + block input) and the next block's c1_d in the ESA apply launch: the attention output never reaches memory
                 chain = [Post(b + 'conv_out', out, C, res=src)]
@@ -249,16 +240,9 @@ class BSRN(HipSRModel):
                 plan.conv(b + 'conv_out', u, out, C, C, k=1, res=src, res_mode=L.RES_PRE_ACT, counted=False,
                           post=first_d(k + 1) if (merged and k < nb) else None)
             cur = out
-        plan.conv('c1', bcat, v, nb * C, C, k=1, counted=False, **g)
-        if hl:
-            bs3('c2', v, out_lr2, C, C, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.upsampleOneStep.0', out_lr2, OUTPUT, C, self.out_nc * 16, hilo=L.HILO_IN)
-            return
-        if merged:
-            bs3('c2', v, u, C, C, res=fea, res_mode=L.RES_PRE_ACT)
-        else:
-            plan.bsconv('c2.pw', 'c2.dw', v, u, C, C, res=fea, res_mode=L.RES_PRE_ACT)
-        plan.conv('upsampler.upsampleOneStep.0', u, OUTPUT, C, self.out_nc * 16)
+        plan.conv('c1', bcat.whole, v, nb * C, C, k=1, counted=False, **g)
+        c2 = bs3 if merged else (lambda _, *a, **kw: plan.bsconv('c2.pw', 'c2.dw', *a, **kw))
+        skip.close('c2', 'upsampler.upsampleOneStep.0', v, u, self.out_nc * 16, conv=c2)
 
     # -- complexity counters: what utils/model_summary.py reports for this graph -----------------------------
     def _complexity_terms(self, plan, o):

@@ -7,17 +7,12 @@ dc = 10 in every block, no `+ input` in the RFDB, no 1x1 over the four block out
 an ESA whose low-resolution branch pools the conv1 map directly, max_pool2d(7, stride 7, padding 1), then runs two parallel 3x3s and a 3x3
 over their concat (plainblock.py:124-150; Plan.maxpool7s7, or one esr_esa_lowres_f32 op with w_s2 = NULL).  nf = 42 lives in NHWC buffers
 of pitch 48 (whole K chunks in every storage type, so the tight pitch is the same); d1, d2, d3 and r4 are 16-wide slices (16-bit: four dense
-tensors, engine.Planar) that c5 reads through a cin_map -- torch.cat never runs.
+tensors, engine.Planar) that c5 reads through a cin_map -- torch.cat never runs.  The long skip (plainsr.py:30) and the concat are the shared
+frame's (frame.py); the stride-7 ESA branch and its maps are this file's.
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Post
-from .rfdn import _slice_map
-from .rlfn import FP
-
-
-def _pool7(h, w):
-    """size of max_pool2d(7, stride 7, padding 1) (plainblock.py:143)"""
-    return (h - 5) // 7 + 1, (w - 5) // 7 + 1
+from .engine import EsaLayer, HipSRModel, Post
+from .frame import FP, Concat, LongSkip, _pool7, _slice_map, check_input, pack_c1d_apost, set_scale
 
 
 class PLAINRFDN(HipSRModel):
@@ -49,12 +44,10 @@ class PLAINRFDN(HipSRModel):
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'PLAINRFDN expects {self.in_nc} input channels, got {c}')
+        check_input('PLAINRFDN', plan, c, self.in_nc, esa=False)
         if plan.h < 5 or plan.w < 8:
             # the pooling needs H, W >= 5; esr_esa_apply_f32's kernels carry a 16-pixel group's column over at most two image rows, which
             # holds for W >= 8 (RFDN, RLFN and BSRN never go below W = 15)
@@ -67,14 +60,9 @@ class PLAINRFDN(HipSRModel):
         # refused by esr_conv_post_supported for a 42-channel 3x3 with a 10-channel post (the fp32 post kernels need 48 < cout): separate 1x1s
         s16 = plan.esize == 2
         apply_d = s16 and bool(L.lib().esr_esa_apply_post_supported(nf, dc, 0))
-        # bf16: `fea` and `out_lr` -- the long skip, plainsr.py:30 -- are hi + lo pairs (Plan.pair: two dense tensors)
-        hl = self._skip_hilo(plan, nf)
-        fea2 = plan.pair('fea', P) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', P)
-        out_lr2 = plan.pair('out_lr', P) if hl else None
-        planar = plan.esize == 2
-        cat = plan.planar('cat', 4, DP) if planar else plan.buffer('cat', 4 * DP)
-        cs = (lambda j: cat.seg(j)) if planar else (lambda j: cat[j * DP:(j + 1) * DP])
+        skip = LongSkip(plan, self, nf, P)
+        cat = Concat(plan, 'cat', 4, DP, s16)
+        cs = cat.seg
         r1, r2, v = plan.buffer('r1', P), plan.buffer('r2', P), plan.buffer('v', P)
         bo = [plan.buffer('bo0', P), plan.buffer('bo1', P)]
         c1 = plan.buffer('esa_c1', FP)
@@ -83,8 +71,8 @@ class PLAINRFDN(HipSRModel):
         c3 = plan.buffer('esa_c3', FP, h7, w7)
         act = dict(act=L.ACT_LRELU, slope=0.05)
         lo = dict(hw=(h7, w7))
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, hilo=L.HILO_OUT if hl else 0)
-        cur = fea
+        skip.head('fea_conv', self.in_nc)
+        cur = skip.fea
         for k in range(1, 5):
             b = f'B{k}.'
             if not (apply_d and k > 1):
@@ -96,9 +84,9 @@ class PLAINRFDN(HipSRModel):
             plan.conv(b + 'c3_r.conv3x3', r2, r1, nf, nf, **act)
             plan.conv(b + 'c4.conv3x3', r1, cs(3), nf, dc, **act)
             if s16:
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
                 plan.conv(b + 'esa.conv1', v, c1, nf, f, k=1)
             # ESA's low-resolution branch (plainblock.py:143-147): pooling, the pair into the two 16-wide slices of one map, conv_23 over it
             mark = len(plan.ops)
@@ -114,16 +102,7 @@ class PLAINRFDN(HipSRModel):
             nxt_d = [Post(f'B{k + 1}.c1_d', cs(0), dc, L.ACT_LRELU, slope=0.05)] if (apply_d and k < 4) else None
             plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, c3, out, nf, f, post=nxt_d)
             cur = out
-        if hl:
-            plan.conv('LR_conv', cur, out_lr2, nf, nf, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.0', out_lr2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('LR_conv', cur, r1, nf, nf, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('upsampler.0', r1, OUTPUT, nf, self.out_nc * 16)
+        skip.close('LR_conv', 'upsampler.0', cur, r1, self.out_nc * 16)
 
     def _extra_pack(self, packed, device):
-        if self._store() != "f32" and L.lib().esr_esa_apply_post_supported(self.nf, self.dc, 0):
-            from .engine import pack_apply_post      # c1_d of blocks 2..4 as the post of the previous block's ESA apply launch
-            for k in range(2, 5):
-                leaf = self._leaf(f'B{k}.c1_d')
-                packed[f'B{k}.c1_d#apost'] = pack_apply_post(leaf.weight, leaf.bias, None, None, self._store()).to(device)
+        pack_c1d_apost(self, packed, device)

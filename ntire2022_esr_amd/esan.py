@@ -22,12 +22,14 @@ The head of a block -- the `+` of the previous block, conv1, conv2 and ESA.conv1
            written once, t stays in LDS.  It stores what the four launches store.  The last block's `+` in front of the output convolution
            stays a per-op launch.  Measurements: DESIGN.md 7e.
 Which form a plan takes depends on the per-image shape and esr_resblock_head_supported only, never on the batch size.
+
+ESA's maps and its low-resolution branch are the shared frame's (frame.py); ESAN has no long skip.
 """
 import torch
 
 from . import _lib as L
-from .engine import FOLD, HEAD, INPUT, OUTPUT, S16, Conv, EsaLayer, HipSRModel, Pack
-from .rlfn import FP, _lowres
+from .engine import FOLD, HEAD, INPUT, OUTPUT, S16, Conv, HipSRModel, Pack
+from .frame import FP, EsaBranch, check_input, identity_conv_f
 
 IDENT = "ident"     # the blob of the 32 -> 32 identity 1x1 behind every `x + g`
 
@@ -56,19 +58,13 @@ class ESAN(HipSRModel):
         self._add_conv('upconv.0', nf, out_nc * 16, 3)
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'ESAN expects {self.in_nc} input channels, got {c}')
-        if plan.h < 15 or plan.w < 15:
-            raise L.EsrError('ESA needs H, W >= 15 (3x3/s2 then 7x7/s3 pooling)')
+        check_input('ESAN', plan, c, self.in_nc)
         nf, f, co = self.nf, self.f, self.out_nc * 16
         s16 = plan.esize == 2
-        h2, w2, h3, w3 = _lowres(plan.h, plan.w)
         xa, xb = plan.buffer('xa', nf), plan.buffer('xb', nf)             # the trunk, ping-pong: x' is never stored over the x it is made from
         t, u, g = plan.buffer('t', nf), plan.buffer('u', nf), plan.buffer('g', nf)
-        c1 = plan.buffer('esa_c1', FP)
-        lo2 = plan.buffer('esa_s2', FP, h2, w2)
-        la, lb = plan.buffer('esa_a', FP, h3, w3), plan.buffer('esa_b', FP, h3, w3)
-        lo = dict(hw=(h3, w3))
+        esa = EsaBranch(plan, f)
+        c1 = esa.c1
         if s16:
             # [trunk (32) | the packed input's 16 slots]: the output convolution's folded 3x3 reads both, the head convolution the slots
             cat = plan.buffer('cat', nf + 16)
@@ -92,17 +88,9 @@ class ESAN(HipSRModel):
             plan.conv(b + 'ESA.conv1', u, c1, nf, f, k=1)
             if self.fuse_head and s16:
                 plan.resblock_head(mark)                      # (where the kernel takes the head; else the launches stay)
-            mark = len(plan.ops)
-            plan.conv3x3s2(b + 'ESA.conv2', c1, lo2, f)
-            plan.maxpool7s3(lo2, la)
-            plan.conv(b + 'ESA.conv3_1', la, lb, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'ESA.conv3_2', lb, la, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'ESA.conv3_3', la, lb, f, f, **lo)
-            if self.fuse_esa_lowres:
-                plan.esa_lowres(mark, c1, la, lb, f, b + 'ESA.conv2',
-                                [EsaLayer(0, L.ACT_RELU, b + 'ESA.conv3_1'), EsaLayer(0, L.ACT_RELU, b + 'ESA.conv3_2'),
-                                 EsaLayer(0, L.ACT_NONE, b + 'ESA.conv3_3')])
-            plan.esa_apply(b + 'ESA.conv_f', b + 'ESA.conv4', u, c1, lb, g, nf, f)
+            c3 = esa.lowres(b + 'ESA.conv2', [(b + 'ESA.conv3_1', L.ACT_RELU), (b + 'ESA.conv3_2', L.ACT_RELU), (b + 'ESA.conv3_3', L.ACT_NONE)],
+                            self.fuse_esa_lowres)
+            plan.esa_apply(b + 'ESA.conv_f', b + 'ESA.conv4', u, c1, c3, g, nf, f)
         if s16:
             plan.conv(IDENT, g, last, nf, nf, k=1, res=cur, res_mode=L.RES_PRE_ACT, counted=False)
             plan.conv('upconv.0' + FOLD, cat, OUTPUT, nf + 16, co, cin_alg=nf + self.in_nc)
@@ -112,11 +100,11 @@ class ESAN(HipSRModel):
             plan.conv('upconv.0', last, OUTPUT, nf, co, res=up0, res_mode=L.RES_PRE_ACT)
 
     def _extra_pack(self, packed, device):
-        from .engine import pack_conv, pack_conv_s16, pack_dense
+        from .engine import pack_conv, pack_conv_s16
         store = self._store()
         eye, zero = torch.eye(self.nf)[:, :, None, None], torch.zeros(self.nf)
         packed[IDENT] = pack_conv(eye, zero).to(device)
-        conv_f = pack_dense(torch.eye(self.f)[:, :, None, None], torch.zeros(self.f), FP, FP).to(device)     # c3 + c1_ == c3 + conv_f(c1_), conv_f = identity
+        conv_f = identity_conv_f(self.f, device)
         for k in range(self.n_blocks):
             packed[f'recon_trunk.0.{k}.ESA.conv_f'] = conv_f
         if store != "f32":

@@ -7,10 +7,11 @@ tight pitch, as RFDN); the HFABs' 12 / 16-channel maps in buffers of pitch 16.  
 Per HFAB (team03_fmen.py:60-73): squeeze + lrelu, the BasicBlocks' convs (conv1 + lrelu, conv2; the last one gets the outer lrelu), excitate,
 sigmoid(.) * x as the conv's gate epilogue (L.RES_GATE).  16-bit plans with fuse_hfab: the four layers of a body HFAB as ONE launch
 (Plan.hfab -> hfab_kernel); the warmup HFAB (mid 12, two BasicBlocks, one layer without activation) stays on per-layer launches.
+The long skip (x = head(in), lr_conv(h) + x; team03_fmen.py:122-134) is the shared frame's (frame.py).
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, HipSRModel
-from .rlfn import _pad8
+from .engine import HipSRModel
+from .frame import LongSkip, _pad8, check_input, set_scale
 
 SLOPE = 0.1
 
@@ -48,8 +49,7 @@ class FMEN(HipSRModel):
 
     fuse_hfab = property(lambda self: self._fuse_hfab, lambda self, v: self._set_flag("_fuse_hfab", v))
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _hfab(self, plan, path, up_blocks, x, y, ta, tb, mid, fuse):
         """HFAB(x) -> y (team03_fmen.py:67-73): lrelu(squeeze), [conv1 + lrelu, conv2] x up_blocks with the outer lrelu on the last conv2,
@@ -67,8 +67,7 @@ class FMEN(HipSRModel):
             plan.hfab(mark)
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'FMEN expects {self.in_nc} input channels, got {c}')
+        check_input('FMEN', plan, c, self.in_nc, esa=False)
         if plan.store == "f16":
             # the checkpoint's HFAB intermediates reach ~2e7 on natural images (warmup.1.convs.1.conv2; the sigmoid saturates them): beyond
             # fp16's 65504, the forward would overflow to Inf / NaN.  bf16 has fp32's exponent range
@@ -77,17 +76,13 @@ class FMEN(HipSRModel):
         # 16-bit storage: nf-wide tensors at the tight pitch round_up(nf, 8) = 56 (esr_conv2d_s16: tight pitch; hfab_kernel reads cin channels)
         P = _pad8(nf) if (plan.esize == 2 and self.tight_pitch) else plan.cpad(nf)
         M = plan.cpad(self.mid_feats)
-        # bf16: x = head(in) and lr_conv(h) + x -- the long skip, team03_fmen.py:122-134 -- as hi + lo pairs (Plan.pair)
-        hl = self._skip_hilo(plan, nf)
-        x2 = plan.pair('x', P) if hl else None
-        x = x2.seg(0) if hl else plan.buffer('x', P)
-        out2 = plan.pair('out_lr', P) if hl else None
+        skip = LongSkip(plan, self, nf, P, name='x')
         ha, hb = plan.buffer('ha', P), plan.buffer('hb', P)
         ta, tb = plan.buffer('ta', M), plan.buffer('tb', M)
         act = dict(act=L.ACT_LRELU, slope=SLOPE)
         fuse = self.fuse_hfab and plan.esize == 2
-        plan.conv('head', INPUT, x2 if hl else x, self.in_nc, nf, hilo=L.HILO_OUT if hl else 0)
-        plan.conv('warmup.0', x, ha, nf, nf)
+        skip.head('head', self.in_nc)
+        plan.conv('warmup.0', skip.fea, ha, nf, nf)
         self._hfab(plan, 'warmup.1', self.up_blocks[0], ha, hb, ta, tb, self.mid_feats - 4, False)
         h, u = hb, ha
         for i in range(self.down_blocks):
@@ -96,12 +91,7 @@ class FMEN(HipSRModel):
             plan.conv(f'basic_blocks.{i}.conv2.rep_conv', u, h, nf, nf)
             self._hfab(plan, f'hfabs.{i}', self.up_blocks[i + 1], h, u, ta, tb, self.mid_feats, fuse and self.up_blocks[i + 1] == 1)
             h, u = u, h
-        if hl:
-            plan.conv('lr_conv', h, out2, nf, nf, res=x2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('tail.0', out2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('lr_conv', h, u, nf, nf, res=x, res_mode=L.RES_PRE_ACT)
-            plan.conv('tail.0', u, OUTPUT, nf, self.out_nc * 16)
+        skip.close('lr_conv', 'tail.0', h, u, self.out_nc * 16)
 
     def _counted_convs(self, plan, o):
         """FMEN's LeakyReLU is one module-level object (team03_fmen.py:6-7), not a submodule: utils/model_summary.py's hooks never see it, so the

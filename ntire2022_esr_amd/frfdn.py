@@ -24,10 +24,13 @@ The refinement path behind d2 has two forms (model.fuse_cascade):
            r3 stay in LDS.  Bit-identical to the per-op form.  OFF by default: in bf16 it is 14 % faster on one 339 x 510 image (0.659 against
            0.764 ms per forward) but not at 32 x 256 x 256 (4.486 against 4.476 ms, inside the spread between repeats); DESIGN.md 7f.
 Which form a plan takes depends on the per-image shape and esr_refine_cascade_supported only, never on the batch size.
+
+The long skip (FRFDN.py:46), the concats and ESA's low-resolution branch are the shared frame's (frame.py); d3 and r4, two halves of one concat
+segment, are this file's.
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Post
-from .rlfn import FP, _lowres
+from .engine import HipSRModel, Post
+from .frame import FP, Concat, EsaBranch, LongSkip, check_input, pack_c1d_apost, set_scale
 
 
 class FasterRFDN(HipSRModel):
@@ -63,44 +66,31 @@ class FasterRFDN(HipSRModel):
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'FasterRFDN expects {self.in_nc} input channels, got {c}')
-        if plan.h < 15 or plan.w < 15:
-            raise L.EsrError('ESA needs H, W >= 15 (3x3/s2 then 7x7/s3 pooling)')
+        check_input('FasterRFDN', plan, c, self.in_nc)
         nf, dc, qc, f = self.nf, self.dc, self.qc, self.f
         s16 = plan.esize == 2
         CW = 2 * dc + 2 * qc                              # the concat: 96 channels, no pad slot in any storage
-        h2, w2, h3, w3 = _lowres(plan.h, plan.w)
-        # bf16: `fea` and `out_lr` -- the long skip, FRFDN.py:46 -- are hi + lo pairs (Plan.pair: two dense tensors)
-        hl = self._skip_hilo(plan, nf)
-        fea2 = plan.pair('fea', nf) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', nf)
-        out_lr2 = plan.pair('out_lr', nf) if hl else None
+        skip = LongSkip(plan, self, nf, nf)
         # the four block outputs (FRFDN.py:45) and d1 | d2 | [d3, r4] (block.py:124): dense tensors in the 16-bit modes (engine.Planar), slices in fp32
-        bcat = plan.planar('bcat', 4, nf) if s16 else plan.buffer('bcat', 4 * nf)
-        cat = plan.planar('cat', 3, dc) if s16 else plan.buffer('cat', CW)
-        d1 = cat.seg(0) if s16 else cat[0:dc]
-        d2 = cat.seg(1) if s16 else cat[dc:2 * dc]
-        d3 = (cat.seg(2), 0, qc) if s16 else cat[2 * dc:2 * dc + qc]
-        r4 = (cat.seg(2), qc, qc) if s16 else cat[2 * dc + qc:CW]
+        bcat = Concat(plan, 'bcat', 4, nf, s16)
+        cat = Concat(plan, 'cat', 3, dc, s16, CW)
+        d1, d2 = cat.seg(0), cat.seg(1)
+        d3 = (cat.seg(2), 0, qc) if s16 else cat.whole[2 * dc:2 * dc + qc]
+        r4 = (cat.seg(2), qc, qc) if s16 else cat.whole[2 * dc + qc:CW]
         r1, r2, r3 = plan.buffer('r1', nf), plan.buffer('r2', dc), plan.buffer('r3', qc)
         v = plan.buffer('v', nf)
-        c1 = plan.buffer('esa_c1', FP)
-        lo2 = plan.buffer('esa_s2', FP, h2, w2)
-        la, lb = plan.buffer('esa_a', FP, h3, w3), plan.buffer('esa_b', FP, h3, w3)
+        esa = EsaBranch(plan, f)
+        c1 = esa.c1
         act = dict(act=L.ACT_LRELU, slope=0.05)
-        lo = dict(hw=(h3, w3))
         res = lambda t: dict(res=t, res_mode=L.RES_PRE_ACT)
         # 16-bit modes: block 1's c1_d (of fea) rides in the head convolution's epilogue, the other blocks' in the ESA apply launch that
         # produces their input (esr_esa_desc.post[])
         apply_d = s16 and bool(L.lib().esr_esa_apply_post_supported(nf, dc, 0))
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, post=Post('B1.c1_d', d1, dc, L.ACT_LRELU) if s16 else None,
-                  hilo=L.HILO_OUT if hl else 0)
-        cur = fea
+        skip.head('fea_conv', self.in_nc, post=Post('B1.c1_d', d1, dc, L.ACT_LRELU) if s16 else None)
+        cur = skip.fea
         for k in range(1, 5):
             b = f'B{k}.'
             if not (s16 and (k == 1 or apply_d)):
@@ -122,46 +112,18 @@ class FasterRFDN(HipSRModel):
                 plan.refine_cascade(mark)                 # (where the kernel takes the path; else the four launches stay)
             if s16:
                 # 16-bit storage: esa.conv1 rides in c5's epilogue on the fp32 tile (one launch less per block)
-                plan.conv(b + 'c5', cat, v, CW, nf, k=1, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
+                plan.conv(b + 'c5', cat.whole, v, CW, nf, k=1, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
-                plan.conv(b + 'c5', cat, v, CW, nf, k=1)
+                plan.conv(b + 'c5', cat.whole, v, CW, nf, k=1)
                 plan.conv(b + 'esa.conv1', v, c1, nf, f, k=1)
-            mark = len(plan.ops)
-            plan.conv3x3s2(b + 'esa.conv2', c1, lo2, f)
-            plan.maxpool7s3(lo2, la)
-            plan.conv(b + 'esa.conv_max', la, lb, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'esa.conv3', lb, la, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'esa.conv3_', la, lb, f, f, **lo)
-            if self.fuse_esa_lowres:
-                # the five launches above as one op of two (halo recompute; only the pooled map reaches memory)
-                plan.esa_lowres(mark, c1, la, lb, f, b + 'esa.conv2',
-                                [EsaLayer(0, L.ACT_RELU, b + 'esa.conv_max'), EsaLayer(0, L.ACT_RELU, b + 'esa.conv3'),
-                                 EsaLayer(0, L.ACT_NONE, b + 'esa.conv3_')])
-            out = bcat.seg(k - 1) if s16 else bcat[(k - 1) * nf:k * nf]
+            c3 = esa.lowres(b + 'esa.conv2', [(b + 'esa.conv_max', L.ACT_RELU), (b + 'esa.conv3', L.ACT_RELU), (b + 'esa.conv3_', L.ACT_NONE)],
+                            self.fuse_esa_lowres)
+            out = bcat.seg(k - 1)
             nxt_d = [Post(f'B{k + 1}.c1_d', d1, dc, L.ACT_LRELU, slope=0.05)] if (apply_d and k < 4) else None
-            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lb, out, nf, f, post=nxt_d)
+            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, c3, out, nf, f, post=nxt_d)
             cur = out
-        plan.conv('c.0', bcat, v, 4 * nf, nf, k=1, **act)
-        if hl:
-            plan.conv('LR_conv', v, out_lr2, nf, nf, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.0', out_lr2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('LR_conv', v, r1, nf, nf, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('upsampler.0', r1, OUTPUT, nf, self.out_nc * 16)
+        plan.conv('c.0', bcat.whole, v, 4 * nf, nf, k=1, **act)
+        skip.close('LR_conv', 'upsampler.0', v, r1, self.out_nc * 16)
 
     def _extra_pack(self, packed, device):
-        if self._store() != "f32" and L.lib().esr_esa_apply_post_supported(self.nf, self.dc, 0):
-            from .engine import pack_apply_post      # c1_d of blocks 2..4 as the post of the previous block's ESA apply launch
-            for k in range(2, 5):
-                leaf = self._leaf(f'B{k}.c1_d')
-                packed[f'B{k}.c1_d#apost'] = pack_apply_post(leaf.weight, leaf.bias, None, None, self._store()).to(device)
-
-    def _counted_convs(self, plan, o):
-        """logical channel counts as the reference's hooks see them: c5 reads cat(d1, d2, d3, r4) = 96 channels, c.0 the four block outputs =
-        256 (neither concat has a pad slot, so the physical counts are the logical ones in every storage and both forms)"""
-        r = super()._counted_convs(plan, o)
-        if o.kind == "conv" and o.w.endswith('.c5'):
-            return [(2 * self.dc + 2 * self.qc, o.cout, 1, plan.npix, o.act)] + r[1:]
-        if o.kind == "conv" and o.w == 'c.0':
-            return [(self.nf * self.num_modules, o.cout, 1, plan.npix, o.act)]
-        return r
+        pack_c1d_apost(self, packed, device)

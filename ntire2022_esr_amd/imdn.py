@@ -14,9 +14,11 @@ Forward = 3 + 4*nb kernel launches (3 + 5*nb when nc != 64), no split/cat/add ke
            1x1  4d->nc   + block input (residual)   -> ping-pong X   same launch    :264-265
   tail     nc->nc 3x3 + FEA (ShortcutBlock, basicblock.py:197-199)
   up       nc->out_nc*16 3x3 fused with PixelShuffle(4) -> NCHW output             basicblock.py:446-449
+The long skip (the ShortcutBlock, models/imdn_baseline.py:61, basicblock.py:191-205) and the concat are the shared frame's (frame.py).
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, HipSRModel, Tail
+from .engine import HipSRModel, Tail
+from .frame import Concat, LongSkip, check_input
 
 
 class IMDN(HipSRModel):
@@ -47,20 +49,14 @@ class IMDN(HipSRModel):
         self._add_conv('model.2', nc, out_nc * upscale * upscale, 3)
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'IMDN expects {self.in_nc} input channels, got {c}')
+        check_input('IMDN', plan, c, self.in_nc, esa=False)
         nc, d, r = self.nc, self.d_nc, self.r_nc
-        # bf16: `fea` and the LR conv's output -- the long skip of the ShortcutBlock, models/imdn_baseline.py:61, basicblock.py:191-205 -- are hi + lo pairs (Plan.pair)
-        hl = self._skip_hilo(plan, nc)
-        fea2 = plan.pair('fea', plan.cpad(nc)) if hl else None
-        out_lr2 = plan.pair('out_lr', plan.cpad(nc)) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', nc)
+        skip = LongSkip(plan, self, nc, nc)               # (nc is whole K chunks in every storage)
         fused = d == 16 and 48 < nc <= 64 and self.compute == 'f32'    # conv4 + 1x1 in one launch (16-bit modes keep conv4 on the 16-bit kernel)
         # fused: conv4's slot never reaches memory.  16-bit storage (d a multiple of 16): four dense tensors (engine.Planar) instead
         # of 32-byte slices of a 128-byte pixel -- partial-line stores cost 2.3x a dense one
-        planar = plan.esize == 2 and d % 16 == 0
-        cat = plan.planar('cat', 4, d) if planar else plan.buffer('cat', plan.cpad(3 * d if fused else 4 * d))
-        cs = (lambda j: cat.seg(j)) if planar else (lambda j: cat[j * d:(j + 1) * d])
+        cat = Concat(plan, 'cat', 4, d, plan.esize == 2 and d % 16 == 0, plan.cpad(3 * d if fused else 4 * d))
+        cs = cat.seg
         # pitches are whole K chunks of the plan's storage type (8 fp32 / 16 16-bit channels): r = 24 (nc = 32) needs 32 slots in bf16 / fp16
         # fused tail: its 3x3 input (conv3's remaining channels) is stored channel-blocked [n][r/8][h][w][8] -- imdb_tail_kernel
         # stages one 8-channel K chunk at a time, and in NHWC every 128-byte line of a 192-byte pixel would be fetched by four
@@ -77,8 +73,8 @@ class IMDN(HipSRModel):
         r1, r2 = plan.buffer('r1', plan.cpad(r), blocked=blk12), plan.buffer('r2', plan.cpad(r), blocked=blk12)
         r3 = plan.buffer('r3', r, blocked=True) if blk else r1
         act = dict(act=self.act, slope=self.slope)
-        plan.conv('model.0', INPUT, fea2 if hl else fea, self.in_nc, nc, hilo=L.HILO_OUT if hl else 0)
-        cur, nxt = fea, xa
+        skip.head('model.0', self.in_nc)
+        cur, nxt = skip.fea, xa
         for i in range(self.nb):
             p = f'model.1.sub.{i}.'
             plan.conv(p + 'conv1.0', cur, cs(0), nc, nc, split=d, dst1=r1, **act)
@@ -88,17 +84,12 @@ class IMDN(HipSRModel):
                 # conv4 -> cat -> conv1x1 -> + x in one kernel: the 16 conv4 channels go from the 3x3's accumulators
                 # straight into the 1x1's K loop and never reach memory
                 plan.conv(p + 'conv4', r3, nxt, r, d, res=cur, res_mode=L.RES_PRE_ACT,
-                          tail=Tail(p + 'conv1x1', cat[0:3 * d], 3 * d, 3 * d, nc))
+                          tail=Tail(p + 'conv1x1', cat.whole[0:3 * d], 3 * d, 3 * d, nc))
             else:
                 plan.conv(p + 'conv4', r1, cs(3), r, d)
-                plan.conv(p + 'conv1x1', cat, nxt, 4 * d, nc, k=1, res=cur, res_mode=L.RES_PRE_ACT)
+                plan.conv(p + 'conv1x1', cat.whole, nxt, 4 * d, nc, k=1, res=cur, res_mode=L.RES_PRE_ACT)
             cur = nxt
             nxt = xb if cur is xa else xa
         if lr is not None:
             nxt = lr                                   # the LR conv's epilogue (residual add) stores NHWC
-        if hl:
-            plan.conv(f'model.1.sub.{self.nb}', cur, out_lr2, nc, nc, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('model.2', out_lr2, OUTPUT, nc, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv(f'model.1.sub.{self.nb}', cur, nxt, nc, nc, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('model.2', nxt, OUTPUT, nc, self.out_nc * 16)
+        skip.close(f'model.1.sub.{self.nb}', 'model.2', cur, nxt, self.out_nc * 16)

@@ -5,16 +5,12 @@ zero pad channels); the 25-channel distilled maps are stored as 32-wide (one 128
 and the four block outputs as 56-wide slices of one 224-wide buffer, so neither torch.cat
 (rfdn_baseline/block.py:163, RFDN.py:36) exists as a kernel: the following 1x1 convs are packed with a
 `cin_map` that skips the pad slots.  Per RFDB (block.py:148-166): {1x1 distil + LeakyReLU, 3x3 + input
-residual + LeakyReLU} x3, 3x3 50->25 + LeakyReLU, 1x1 c5 over the concat, ESA.
+residual + LeakyReLU} x3, 3x3 50->25 + LeakyReLU, 1x1 c5 over the concat, ESA.  The long skip (RFDN.py:44-47), the two concats and ESA's
+low-resolution branch are the shared frame's (frame.py); specific to RFDN is which 1x1 rides in which launch, and the fused block tail.
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Planar, Post, Tail
-from .rlfn import FP, _lowres, _pad8
-
-
-def _slice_map(n_slices, logical, padded):
-    """physical slot -> logical channel for `n_slices` slices of `logical` channels padded to `padded`."""
-    return [(s // padded) * logical + s % padded if s % padded < logical else -1 for s in range(n_slices * padded)]
+from .engine import HipSRModel, Planar, Post, Tail
+from .frame import FP, Concat, EsaBranch, LongSkip, _pad8, _slice_map, block_cin_map, check_input, identity_conv_f, pack_c1d_apost, set_scale
 
 
 class RFDN(HipSRModel):
@@ -58,42 +54,30 @@ class RFDN(HipSRModel):
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'RFDN expects {self.in_nc} input channels, got {c}')
-        if plan.h < 15 or plan.w < 15:
-            raise L.EsrError('ESA needs H, W >= 15 (3x3/s2 then 7x7/s3 pooling)')
+        check_input('RFDN', plan, c, self.in_nc)
         nf, dc, f, DP = self.nf, self.dc, self.f, self.DP
         KP = plan.cpad(nf)                                # 56 fp32 channels / 64 16-bit channels: whole K chunks
         # 16-bit storage, round 6: the nf-wide tensors at a TIGHT pitch -- round_up(nf, 8) = 56 channels (112-byte pixels) instead of 64; a consumer's
         # last K chunk runs 8 channels into the next pixel against zero weight rows (esr_conv2d_s16).  12.5 % fewer bytes per launch of an
         # HBM-bound model
         P = _pad8(nf) if (plan.esize == 2 and self.tight_pitch) else KP
-        h2, w2, h3, w3 = _lowres(plan.h, plan.w)
-        # bf16: `fea` and `out_lr` -- the long skip, RFDN.py:44-47 -- are hi + lo pairs (Plan.pair: two dense tensors)
-        hl = self._skip_hilo(plan, nf)
-        fea2 = plan.pair('fea', P) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', P)
-        out_lr2 = plan.pair('out_lr', P) if hl else None
+        skip = LongSkip(plan, self, nf, P)
         # the four block outputs, RFDN.py:36: four dense tensors in the 16-bit modes (engine.Planar; same slot order as the padded
         # [.., 4 P] buffer, so c.0's weight blob does not change)
-        bplanar = plan.esize == 2
-        bcat = plan.planar('bcat', 4, P) if bplanar else plan.buffer('bcat', 4 * P)
+        planar = plan.esize == 2
+        bcat = Concat(plan, 'bcat', 4, P, planar)
         # d1 d2 d3 r4, block.py:163.  16-bit storage: four dense tensors (engine.Planar) -- a 32-channel slice of a 128-wide
         # buffer is a partial-line store there (64 of 256 bytes per pixel), 2.3x the cost of a dense one
-        planar = plan.esize == 2
-        cat = plan.planar('cat', 4, DP) if planar else plan.buffer('cat', _pad8(4 * DP))
-        cs = (lambda j: cat.seg(j)) if planar else (lambda j: cat[j * DP:(j + 1) * DP])
+        cat = Concat(plan, 'cat', 4, DP, planar, _pad8(4 * DP))
+        cs = cat.seg
         r1, r2 = plan.buffer('r1', P), plan.buffer('r2', P)
         v = plan.buffer('v', P)
-        c1 = plan.buffer('esa_c1', FP)
-        lo2 = plan.buffer('esa_s2', FP, h2, w2)
-        la, lb = plan.buffer('esa_a', FP, h3, w3), plan.buffer('esa_b', FP, h3, w3)
+        esa = EsaBranch(plan, f)
+        c1 = esa.c1
         act = dict(act=L.ACT_LRELU, slope=0.05)
-        lo = dict(hw=(h3, w3))
         res = (lambda v: dict(res=v, res_mode=L.RES_PRE_ACT)) if self.block_residual else (lambda v: {})
         fused_post = (48 < nf <= 64 and 16 < dc <= 32) if plan.esize == 4 else ((nf + 15) // 16 in (3, 4) and 16 < dc <= 32)
         # 16-bit modes: block 1's first distillation conv (c1_d of fea) rides in the head convolution's epilogue
@@ -101,11 +85,10 @@ class RFDN(HipSRModel):
         fused_tail = (self.fuse_tail and plan.esize == 2 and fused_post and planar and 48 < nf <= 64 and DP == 32 and f <= 16 and FP == 16
                       and plan.n * ((plan.w + 15) // 16) * ((plan.h + 15) // 16) >= 256)
         head_d = plan.esize == 2 and fused_post
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, post=Post('B1.c1_d', cs(0), dc, L.ACT_LRELU) if head_d else None,
-                  hilo=L.HILO_OUT if hl else 0)
+        skip.head('fea_conv', self.in_nc, post=Post('B1.c1_d', cs(0), dc, L.ACT_LRELU) if head_d else None)
         # ... and the other blocks' in the ESA apply launch that produces their input (esr_esa_desc.post[])
         apply_d = plan.esize == 2 and fused_post and bool(L.lib().esr_esa_apply_post_supported(nf, dc, 0))
-        cur = fea
+        cur = skip.fea
         for k in range(1, 5):
             b = f'B{k}.'
             if not ((head_d and k == 1) or (apply_d and k > 1)):
@@ -125,7 +108,7 @@ class RFDN(HipSRModel):
             if fused_tail:
                 # round 6 (ABI v12): c4 -> cat(d1, d2, d3, r4) -> c5 -> esa.conv1 in ONE launch (rfdb_tail_kernel; block.py:161-164, :117):
                 # r4 stays in registers, d1 .. d3 are read once, v and esa.conv1's map are the only stores
-                plan.conv(b + 'c4', r1, v, nf, dc, tail=Tail(b + 'c5#tail', Planar(cat.segs[:3]), 3 * DP, 3 * dc, nf, L.ACT_LRELU),
+                plan.conv(b + 'c4', r1, v, nf, dc, tail=Tail(b + 'c5#tail', Planar(cat.whole.segs[:3]), 3 * DP, 3 * dc, nf, L.ACT_LRELU),
                           post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
                 plan.conv(b + 'c4', r1, cs(3), nf, dc, **act)
@@ -133,37 +116,20 @@ class RFDN(HipSRModel):
                 pass
             elif plan.esize == 2 and (nf + 15) // 16 in (3, 4) and f <= 16:
                 # 16-bit storage: esa.conv1 rides in c5's epilogue on the fp32 tile (one launch less per block)
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc, post=Post(b + 'esa.conv1', c1, f, L.ACT_NONE))
             else:
-                plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
+                plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
                 plan.conv(b + 'esa.conv1', v, c1, nf, f, k=1)
-            mark = len(plan.ops)
-            plan.conv3x3s2(b + 'esa.conv2', c1, lo2, f)
-            plan.maxpool7s3(lo2, la)
-            plan.conv(b + 'esa.conv_max', la, lb, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'esa.conv3', lb, la, f, f, act=L.ACT_RELU, **lo)
-            plan.conv(b + 'esa.conv3_', la, lb, f, f, **lo)
-            if self.fuse_esa_lowres:
-                # the five launches above as one op of two (halo recompute; only the pooled map reaches memory)
-                plan.esa_lowres(mark, c1, la, lb, f, b + 'esa.conv2',
-                                [EsaLayer(0, L.ACT_RELU, b + 'esa.conv_max'), EsaLayer(0, L.ACT_RELU, b + 'esa.conv3'),
-                                 EsaLayer(0, L.ACT_NONE, b + 'esa.conv3_')])
-            out = bcat.seg(k - 1) if bplanar else bcat[(k - 1) * P:k * P]
+            c3 = esa.lowres(b + 'esa.conv2', [(b + 'esa.conv_max', L.ACT_RELU), (b + 'esa.conv3', L.ACT_RELU), (b + 'esa.conv3_', L.ACT_NONE)],
+                            self.fuse_esa_lowres)
+            out = bcat.seg(k - 1)
             nxt_d = [Post(f'B{k + 1}.c1_d', cs(0), dc, L.ACT_LRELU, slope=0.05)] if (apply_d and k < 4) else None
-            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lb, out, nf, f, post=nxt_d)
+            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, c3, out, nf, f, post=nxt_d)
             cur = out
-        plan.conv('c.0', bcat, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **act)
-        if hl:
-            plan.conv('LR_conv', v, out_lr2, nf, nf, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.0', out_lr2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('LR_conv', v, r1, nf, nf, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('upsampler.0', r1, OUTPUT, nf, self.out_nc * 16)
+        plan.conv('c.0', bcat.whole, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **act)
+        skip.close('LR_conv', 'upsampler.0', v, r1, self.out_nc * 16)
 
-    def _cin_map(self, path, cin_map, store):
-        if path == 'c.0':                                 # the block-output slices are as wide as the storage type's K chunks
-            return _slice_map(self.num_modules, self.nf, _pad8(self.nf) if store == "f32" else (self.nf + 15) // 16 * 16)
-        return cin_map
+    _cin_map = block_cin_map
 
     def _extra_pack(self, packed, device):
         if self._store() != "f32" and 48 < self.nf <= 64 and self.dc <= 32:
@@ -171,20 +137,13 @@ class RFDN(HipSRModel):
             for k in range(1, 5):
                 leaf = self._leaf(f'B{k}.c5')
                 packed[f'B{k}.c5#tail'] = pack_tail_s16(leaf.weight, leaf.bias, 3, self.dc, self.dc, self._store()).to(device)
-        if self._store() != "f32":               # c1_d of blocks 2..4 as the post of the previous block's ESA apply launch
-            from .engine import pack_apply_post
-            if L.lib().esr_esa_apply_post_supported(self.nf, self.dc, 0):
-                for k in range(2, 5):
-                    leaf = self._leaf(f'B{k}.c1_d')
-                    packed[f'B{k}.c1_d#apost'] = pack_apply_post(leaf.weight, leaf.bias, None, None, self._store()).to(device)
+        pack_c1d_apost(self, packed, device)
         if not self.esa_conv_f:                  # SFDN: c3 + c1_  ==  c3 + conv_f(c1_) with conv_f = identity
-            import torch
-            from .engine import pack_dense
             for k in range(1, 5):
-                packed[f'B{k}.esa.conv_f'] = pack_dense(torch.eye(self.f)[:, :, None, None], torch.zeros(self.f), FP, FP).to(device)
+                packed[f'B{k}.esa.conv_f'] = identity_conv_f(self.f, device)
 
     def _counted_convs(self, plan, o):
-        """logical channel counts for the padded-concat 1x1 convs (the reference sees 100 / 200 inputs)."""
+        """what the launches' own counts (Conv.cin_alg: c5 and c.0 carry their logical input channels) leave to say"""
         r = super()._counted_convs(plan, o)
         if o.kind == "apply" and not self.esa_conv_f:
             return r[1:]                         # no conv_f call in the reference graph
@@ -192,7 +151,5 @@ class RFDN(HipSRModel):
             return [(o.cin, o.cout, 3, plan.npix, L.ACT_LRELU), (self.dc * 4, o.tail.cout, 1, plan.npix, L.ACT_NONE),
                     (o.tail.cout, o.post.cout, 1, plan.npix, L.ACT_NONE)]
         if o.kind == "conv" and o.w.endswith('.c5'):
-            return [(self.dc * 4, o.cout, 1, plan.npix, o.act)]
-        if o.kind == "conv" and o.w == 'c.0':
-            return [(self.nf * self.num_modules, o.cout, 1, plan.npix, o.act)]
+            return r[:1]                         # (an esa.conv1 riding in c5's epilogue is not counted)
         return r

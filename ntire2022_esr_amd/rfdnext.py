@@ -31,13 +31,14 @@ The ConvNeXt block has two forms (model.fuse_cx):
            ON by default: in bf16 a forward takes 5.91 against 12.85 ms at 32 x 256 x 256 and 0.876 against 1.468 ms on one 339 x 510
            image, the repeats at most 0.6 % apart.
 Which form a plan takes depends on the per-image shape and esr_cx_block_supported only, never on the batch size.
+
+The long skip (RFDN.py:64) and the two concats are the shared frame's (frame.py).
 """
 import torch
 
 from . import _lib as L
-from .engine import CX1, CX2, INPUT, OUTPUT, S16, WINO, HipSRModel, fold_center, pack_conv, pack_conv_s16, pack_cx_pw, pack_dw7, pack_wino
-from .rfdn import _slice_map
-from .rlfn import _pad8
+from .engine import CX1, CX2, S16, WINO, HipSRModel, fold_center, pack_conv, pack_conv_s16, pack_cx_pw, pack_dw7, pack_wino
+from .frame import Concat, LongSkip, _pad8, _slice_map, block_cin_map, check_input, set_scale
 
 
 def _hidden_slices(cmid, store):
@@ -78,34 +79,29 @@ class RFDNeXt(HipSRModel):
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'RFDNeXt expects {self.in_nc} input channels, got {c}')
+        check_input('RFDNeXt', plan, c, self.in_nc, esa=False)
         nf, dc, cm, DP = self.nf, self.dc, self.cm, self.DP
         s16 = plan.esize == 2
         KP = plan.cpad(nf)                                # 56 fp32 channels / 64 16-bit channels: whole K chunks
         P = _pad8(nf) if (s16 and self.tight_pitch) else KP  # 16-bit storage: the nf-wide tensors at the tight pitch 56 (rfdn.py)
         HP = plan.cpad(cm)                                # the hidden tensor of the per-op ConvNeXt block: 200 fp32 / 208 16-bit channels
-        hl = self._skip_hilo(plan, nf)                    # bf16: `fea` and `out_lr` -- the long skip, RFDN.py:64 -- are hi + lo pairs
-        fea2 = plan.pair('fea', P) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', P)
-        out_lr2 = plan.pair('out_lr', P) if hl else None
-        bcat = plan.planar('bcat', 4, P) if s16 else plan.buffer('bcat', 4 * P)
-        cat = plan.planar('cat', 4, DP) if s16 else plan.buffer('cat', _pad8(4 * DP))
-        cs = (lambda j: cat.seg(j)) if s16 else (lambda j: cat[j * DP:(j + 1) * DP])
+        skip = LongSkip(plan, self, nf, P)
+        bcat = Concat(plan, 'bcat', 4, P, s16)
+        cat = Concat(plan, 'cat', 4, DP, s16, _pad8(4 * DP))
+        cs = cat.seg
         r1, r2, r3 = plan.buffer('r1', DP), plan.buffer('r2', DP), plan.buffer('r3', DP)
         v = plan.buffer('v', P)
-        lr = None if hl else plan.buffer('lr', P)
+        lr = None if skip.hl else plan.buffer('lr', P)
         act = dict(act=L.ACT_LRELU, slope=0.05)
         res = lambda x: dict(res=x, res_mode=L.RES_PRE_ACT)
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, hilo=L.HILO_OUT if hl else 0)      # (16-bit plans: allocates the packed input)
+        skip.head('fea_conv', self.in_nc)                 # (16-bit plans: allocates the packed input)
         # the per-op ConvNeXt block's t and hidden tensor: the plan's LAST allocations, so that a plan whose blocks all fused can give
         # their bytes back (Plan.release below; nothing behind this line allocates)
         t, hid = plan.buffer('t', P), plan.buffer('hid', HP)
-        cur = fea
+        cur = skip.fea
         for k in range(1, 5):
             b = f'B{k}.'
             plan.conv(b + 'c1_d', cur, cs(0), nf, dc, k=1, **act)         # lrelu(dc_1): what the concat holds
@@ -115,8 +111,8 @@ class RFDNeXt(HipSRModel):
             plan.conv(b + 'c3_d', r2, cs(2), dc, dc, k=1, **act)
             plan.conv(b + 'c3_r', r2, r3, dc, dc, **res(r2), **act)
             plan.conv(b + 'c4', r3, cs(3), dc, dc, **act)                 # lrelu(rc_4)
-            plan.conv(b + 'c5', cat, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
-            out = bcat.seg(k - 1) if s16 else bcat[(k - 1) * P:k * P]
+            plan.conv(b + 'c5', cat.whole, v, 4 * DP, nf, k=1, cin_alg=4 * dc)
+            out = bcat.seg(k - 1)
             # the ConvNeXt block in its per-layer form ...
             mark = len(plan.ops)
             plan.dwconv7(b + 'esa.conv.0', v, t, nf)
@@ -132,18 +128,10 @@ class RFDNeXt(HipSRModel):
             cur = out
         if not any(o.kind == "dw7" for o in plan.ops):    # every block fused: nothing reads or writes t and the hidden tensor
             plan.release([t, hid])
-        plan.conv('c.0', bcat, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **act)
-        if hl:
-            plan.conv('LR_conv', v, out_lr2, nf, nf, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.0', out_lr2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('LR_conv', v, lr, nf, nf, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('upsampler.0', lr, OUTPUT, nf, self.out_nc * 16)
+        plan.conv('c.0', bcat.whole, v, 4 * KP, nf, k=1, cin_alg=4 * nf, **act)
+        skip.close('LR_conv', 'upsampler.0', v, lr, self.out_nc * 16)
 
-    def _cin_map(self, path, cin_map, store):
-        if path == 'c.0':                                 # the block-output slices are as wide as the storage type's K chunks
-            return _slice_map(self.num_modules, self.nf, _pad8(self.nf) if store == "f32" else (self.nf + 15) // 16 * 16)
-        return cin_map
+    _cin_map = block_cin_map
 
     def _extra_pack(self, packed, device):
         store = self._store()
@@ -168,13 +156,8 @@ class RFDNeXt(HipSRModel):
                 packed[b + 'esa.conv.1' + CX1], packed[b + 'esa.conv.3' + CX2] = p1.to(device), p2.to(device)
 
     def _counted_convs(self, plan, o):
-        """logical channel counts as the reference's hooks see them: c5 reads 100 channels, c.0 200, the ConvNeXt block's first 1x1 is one
-        nn.Conv2d of 200 outputs however many slices launch it"""
-        r = super()._counted_convs(plan, o)
-        if o.kind == "conv" and o.w.endswith('.c5'):
-            return [(self.dc * 4, o.cout, 1, plan.npix, o.act)]
-        if o.kind == "conv" and o.w == 'c.0':
-            return [(self.nf * self.num_modules, o.cout, 1, plan.npix, o.act)]
+        """the ConvNeXt block's first 1x1 is one nn.Conv2d of 200 outputs however many slices launch it (c5 and c.0 carry their logical
+        input channels themselves: Conv.cin_alg)"""
         if o.kind == "conv" and o.w.endswith('esa.conv.1#o0'):
             return [(o.cin, self.cm, 1, plan.npix, o.act)]
-        return r
+        return super()._counted_convs(plan, o)

@@ -4,21 +4,12 @@ Same constructor keywords and the same 78 state_dict keys (`fea_conv`, `B{k}.{c1
 `B{k}.esa.{conv1,conv_f,conv2,conv3,conv4}`, `LR_conv`, `upsampler.0`).  nf=46 lives in NHWC buffers of
 pitch 48 with two zero pad channels.  Per RLFB (team04_rlfn.py:109-122): three fused 3x3+LeakyReLU (the third
 adds the block input AFTER the activation), the 1x1 c5, then ESA as 1x1 conv1 -> 3x3/s2 -> maxpool 7/3 ->
-3x3 at ~H/6 -> one fused full-resolution tail (bilinear + conv_f + conv4 + sigmoid * x).
+3x3 at ~H/6 -> one fused full-resolution tail (bilinear + conv_f + conv4 + sigmoid * x).  The long skip (team04_rlfn.py:149-150) and ESA's
+low-resolution branch with its one 3x3 are the shared frame's (frame.py); specific to RLFN are the epilogue 1x1s and the 3x3 chain below.
 """
 from . import _lib as L
-from .engine import INPUT, OUTPUT, EsaLayer, HipSRModel, Post
-
-FP = L.ESA_FP
-
-
-def _pad8(c):
-    return (c + 7) // 8 * 8
-
-
-def _lowres(h, w):
-    h2, w2 = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-    return h2, w2, (h2 - 7) // 3 + 1, (w2 - 7) // 3 + 1
+from .engine import HipSRModel, Post
+from .frame import FP, EsaBranch, LongSkip, check_input, set_scale
 
 
 class RLFN_cut(HipSRModel):
@@ -46,32 +37,21 @@ class RLFN_cut(HipSRModel):
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
-    def set_scale(self, scale_idx):
-        self.scale_idx = scale_idx
+    set_scale = set_scale
 
     def _build_plan(self, plan, c):
-        if c != self.in_nc:
-            raise L.EsrError(f'RLFN_cut expects {self.in_nc} input channels, got {c}')
-        if plan.h < 15 or plan.w < 15:
-            raise L.EsrError('ESA needs H, W >= 15 (3x3/s2 then 7x7/s3 pooling)')
+        check_input('RLFN_cut', plan, c, self.in_nc)
         nf, mf, f = self.nf, self.mf, self.esa_channels
         P, M = plan.cpad(nf), plan.cpad(mf)
-        h2, w2, h3, w3 = _lowres(plan.h, plan.w)
-        # bf16: `fea` and `out_lr` -- the long skip, team04_rlfn.py:149-150 -- are hi + lo pairs (Plan.pair: two dense tensors)
-        hl = self._skip_hilo(plan, nf)
-        fea2 = plan.pair('fea', P) if hl else None
-        fea = fea2.seg(0) if hl else plan.buffer('fea', P)
-        out_lr2 = plan.pair('out_lr', P) if hl else None
+        skip = LongSkip(plan, self, nf, P)
         xa, xb = plan.buffer('xa', P), plan.buffer('xb', P)
         t1, t2 = plan.buffer('t1', M), plan.buffer('t2', M)
         u, v = plan.buffer('u', P), plan.buffer('v', P)
-        c1 = plan.buffer('esa_c1', FP)
-        lo2 = plan.buffer('esa_s2', FP, h2, w2)
-        lo3 = plan.buffer('esa_pool', FP, h3, w3)
-        lo4 = plan.buffer('esa_c3', FP, h3, w3)
+        esa = EsaBranch(plan, f)
+        c1 = esa.c1
         act = dict(act=L.ACT_LRELU, slope=0.05)
-        plan.conv('fea_conv', INPUT, fea2 if hl else fea, self.in_nc, nf, hilo=L.HILO_OUT if hl else 0)
-        cur, nxt = fea, xa
+        skip.head('fea_conv', self.in_nc)
+        cur, nxt = skip.fea, xa
         for k in range(1, 5):
             b = f'B{k}.'
             mark_c = len(plan.ops)
@@ -91,18 +71,8 @@ class RLFN_cut(HipSRModel):
                 plan.conv(b + 'c3_r', t2, u, mf, nf, res=cur, res_mode=L.RES_POST_ACT, **act)
                 plan.conv(b + 'c5', u, v, nf, nf, k=1)
                 plan.conv(b + 'esa.conv1', v, c1, nf, f, k=1)
-            mark = len(plan.ops)
-            plan.conv3x3s2(b + 'esa.conv2', c1, lo2, f)
-            plan.maxpool7s3(lo2, lo3)
-            plan.conv(b + 'esa.conv3', lo3, lo4, f, f, hw=(h3, w3))
-            if self.fuse_esa_lowres:
-                plan.esa_lowres(mark, c1, lo3, lo4, f, b + 'esa.conv2', [EsaLayer(0, L.ACT_NONE, b + 'esa.conv3')])
-            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, lo4, nxt, nf, f)
+            c3 = esa.lowres(b + 'esa.conv2', [(b + 'esa.conv3', L.ACT_NONE)], self.fuse_esa_lowres)
+            plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, c3, nxt, nf, f)
             cur = nxt
             nxt = xb if cur is xa else xa
-        if hl:
-            plan.conv('LR_conv', cur, out_lr2, nf, nf, res=fea2, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-            plan.conv('upsampler.0', out_lr2, OUTPUT, nf, self.out_nc * 16, hilo=L.HILO_IN)
-        else:
-            plan.conv('LR_conv', cur, u, nf, nf, res=fea, res_mode=L.RES_PRE_ACT)
-            plan.conv('upsampler.0', u, OUTPUT, nf, self.out_nc * 16)
+        skip.close('LR_conv', 'upsampler.0', cur, u, self.out_nc * 16)

@@ -91,7 +91,7 @@ def test_fused_pool7_branch_matches_aten(storage, f, hw):
 def test_per_op_pool7_branch_matches_aten(storage, f, hw):
     """esr_maxpool7s7_f32, then conv_2 / conv_3 into the two 16-wide slices of a [.., 32] map and conv_23 over it with a cin_map"""
     from ntire2022_esr_amd import _lib as L, ops
-    from ntire2022_esr_amd.rfdn import _slice_map
+    from ntire2022_esr_amd.frame import _slice_map
     n = 2
     xq, ws, pool, ref = _branch_case(storage, f, n, hw)
     h7, w7 = pool.shape[2:]
