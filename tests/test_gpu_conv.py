@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _persist_cases as P
+
 pytestmark = pytest.mark.gpu
 
 ACTS = {0: lambda v: v, 1: lambda v: F.leaky_relu(v, 0.05), 2: F.relu, 3: F.gelu}
@@ -141,19 +143,10 @@ def _block_waves(n, h, w, cin, cout, k=3):
 def test_conv_8wave_tall_tiles(n, hw, cin, cout, act, res_mode):
     """Launches large enough for the 8-wave / 16x32-tile variant (ragged right and bottom edges, rows that are not a
     multiple of 32), all epilogue families, against ATen."""
-    from ntire2022_esr_amd import ops
-    dev = _dev()
+    _dev()
     assert _block_waves(n, *hw, cin, cout) == 8 and _block_waves(1, 64, 64, cin, cout) == 4
-    g = torch.Generator().manual_seed(n * 7 + hw[0] + act + 3 * res_mode)
-    x = torch.randn(n, cin, *hw, generator=g)
-    r = torch.randn(n, cout, *hw, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) * 0.1
-    b = torch.randn(cout, generator=g)
-    c = F.conv2d(x, w, b, padding=1)
-    ref = {0: ACTS[act](c), 1: ACTS[act](c + r), 2: ACTS[act](c) + r}[res_mode]
-    y = ops.conv2d(_nhwc(x).to(dev), w, b, act=act, slope=0.05,
-                   res=_nhwc(r).to(dev) if res_mode else None, res_mode=res_mode)
-    _check(y, ref)
+    case = P.conv_f32(n, hw, cin, cout, act, res_mode)
+    _check(case.outs[0], case.extra["ref32"])
 
 
 def test_conv_8wave_split_store_and_shuffle():
@@ -187,24 +180,11 @@ def test_conv3x3_with_fused_1x1_tail(n, hw, mid_act, res_mode, cat_c):
     """esr_conv_desc.tail_*: IMDBlock's conv4 -> cat -> conv1x1 -> + x (basicblock.py:263-265) in one launch, against
     the three ATen ops; the concat part is a channel slice of a wider buffer.  cat_c = 48 with no / a pre-activation residual is
     the network's own shape and runs on imdb_tail_kernel (csrc/imdb_tail.inc), the rest on conv_f32_kernel's TAIL variant."""
-    from ntire2022_esr_amd import ops
-    dev = _dev()
-    g = torch.Generator().manual_seed(n + hw[0] + 5 * mid_act + res_mode + cat_c)
-    x = torch.randn(n, 48, *hw, generator=g)
-    cat = torch.randn(n, 64, *hw, generator=g)                    # channels [8, 8 + cat_c) are the 1x1's other inputs
-    r = torch.randn(n, 64, *hw, generator=g)
-    w3 = torch.randn(16, 48, 3, 3, generator=g) * 0.1
-    b3 = torch.randn(16, generator=g)
-    w1 = torch.randn(64, cat_c + 16, 1, 1, generator=g) * 0.1
-    b1 = torch.randn(64, generator=g)
-    c4 = ACTS[mid_act](F.conv2d(x, w3, b3, padding=1))
-    y1 = F.conv2d(torch.cat([cat[:, 8:8 + cat_c], c4], 1), w1, b1)
-    ref = {0: y1, 1: y1 + r, 2: F.leaky_relu(y1, 0.05) + r}[res_mode]
-    y = ops.conv2d(_nhwc(x).to(dev), w3, b3, act=1 if res_mode == 2 else 0, slope=0.05,
-                   res=_nhwc(r).to(dev) if res_mode else None, res_mode=res_mode,
-                   tail_weight=w1, tail_bias=b1, tail_cat=_nhwc(cat).to(dev), tail_cat_coff=8, tail_mid_act=mid_act)
+    _dev()
+    case = P.imdb_tail(n, hw, mid_act, res_mode, cat_c)
+    y = case.outs[0]
     assert y.shape[-1] == 64
-    _check(y, ref)
+    _check(y, case.extra["ref32"])
 
 
 @pytest.mark.parametrize("n,h,wd", [(2, 19, 21), (6, 160, 144), (3, 37, 130)])

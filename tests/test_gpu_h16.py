@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _persist_cases as P
 from conftest import GOLD, load_sd_torch
 
 pytestmark = pytest.mark.gpu
@@ -69,23 +70,9 @@ def test_s16_conv_matches_fp64_reference(compute, cin, cout, k, hw, act, res_mod
     """16-bit storage conv (esr_conv2d_f32 with storage = bf16 / f16): inputs are exact 16-bit values, the reference uses
     the EFFECTIVE weights of the packed blob (error-diffused 3x3 taps / hi + lo 1x1) in fp64, so the only differences
     are fp32 accumulation order and the single rounding of the stored result."""
-    from ntire2022_esr_amd import ops
-    from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
     dt = DT[compute]
-    g = torch.Generator().manual_seed(cin + cout + hw[0] + k)
-    cp = (cin + 15) // 16 * 16
-    x = torch.randn(2, cin, *hw, generator=g).to(dt)
-    r = torch.randn(2, cout, *hw, generator=g).to(dt)
-    w = torch.randn(cout, cin, k, k, generator=g) * (0.1 if k == 3 else 0.2)
-    b = torch.randn(cout, generator=g)
-    blob = pack_conv_s16(w, b, compute, cin_phys=cp)
-    weff, _ = unpack_conv_s16(blob, cin, cout, k, compute, cin_phys=cp)
-    conv = F.conv2d(x.double(), weff.double(), b.double(), padding=k // 2)
-    ref = ACTS[act](conv + r.double()) if res_mode == 1 else (ACTS[act](conv) + r.double() if res_mode == 2 else ACTS[act](conv))
-    xin = F.pad(_nhwc(x), (0, ((cin + 7) // 8 * 8 if tight else cp) - cin)).to(DEV)
-    rp = F.pad(_nhwc(r), (0, (-cout) % 8)).to(DEV) if res_mode else None
-    with ops.kernel_trace() as names:
-        y = ops.conv2d(xin, w, b, act=act, res=rp, res_mode=res_mode, cin=cin, packed=blob.to(DEV))
+    case = P.s16_conv(compute, cin, cout, k, hw, act, res_mode, tight)
+    names, y, ref = case.names, case.outs[0], case.refs[0].cpu()
     assert len(names) == 1 and names[0].startswith("conv_s16_kernel<"), names
     assert y.dtype == dt and y.shape[-1] == (cout + 7) // 8 * 8
     got = y.float().cpu().permute(0, 3, 1, 2)
@@ -214,25 +201,9 @@ def test_s16_post_chain_rlfb(compute, n, hw, mf, nf, f):
     tile (hi + lo operands), only v and c1 are rounded -- against fp64 with the blob's effective 3x3 weights.  The small shape runs
     on conv_s16_kernel, the others (>= 256 tiles of 16 x 16, < 1024 of 16 x 32) on conv48rp_kernel: weights in registers, the residual
     staged by each wave for its own rows, ragged edges in both directions."""
-    from ntire2022_esr_amd import ops
-    from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
     dt = DT[compute]
-    g = torch.Generator().manual_seed(21 + n + hw[0])
-    x = torch.randn(n, mf, *hw, generator=g).to(dt)
-    r = torch.randn(n, nf, *hw, generator=g).to(dt)
-    w, b = torch.randn(nf, mf, 3, 3, generator=g) * 0.1, torch.randn(nf, generator=g)
-    w5, b5 = torch.randn(nf, nf, generator=g) * 0.2, torch.randn(nf, generator=g)
-    w1, b1 = torch.randn(f, nf, generator=g) * 0.2, torch.randn(f, generator=g)
-    weff, _ = unpack_conv_s16(pack_conv_s16(w, b, compute), mf, nf, 3, compute)
-    u = F.leaky_relu(F.conv2d(x.double(), weff.double(), b.double(), padding=1), 0.05) + r.double()
-    # bf16: hi + lo operands (the chain sees ~fp32 values and weights); fp16: the 11-bit high parts only -- operands of the
-    # chain's MFMAs are the fp16 roundings of the fp32 tile and of the weights (the network's own storage precision)
-    q = (lambda t: t) if compute == "bf16" else (lambda t: t.to(torch.float16).double())
-    v = F.conv2d(q(u), q(w5.double())[:, :, None, None], b5.double())
-    c1 = F.conv2d(q(v), q(w1.double())[:, :, None, None], b1.double())
-    rp = F.pad(_nhwc(r), (0, 48 - nf)).to(DEV)
-    y, yv, yc = ops.conv2d(F.pad(_nhwc(x), (0, 48 - mf)).to(DEV), w, b, act=1, res=rp, res_mode=2, post_weight=w5, post_bias=b5,
-                           post2_weight=w1, post2_bias=b1, store_main=False, cin=mf)
+    case = P.rlfb_post(compute, n, hw, mf, nf, f, 21 + n + hw[0])
+    y, (yv, yc), (v, c1) = case.extra["main"], case.outs, [t.cpu() for t in case.refs]
     assert y is None and yv.dtype == dt and yv.shape[-1] == (nf + 7) // 8 * 8 and yc.shape[-1] == (f + 7) // 8 * 8
     eps = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
 
@@ -370,22 +341,8 @@ def test_conv48r_equals_conv_s16(compute, cin, cout, act, res_in, border, hw, n)
     """conv48r_kernel (3x3 over 48 physical input channels, >= 256 tiles of 16 x 32: weights in registers, one wave per SIMD, row pairs
     as the outer loop) against conv_s16_kernel: the batch takes the new kernel (esr_conv_block_waves == 1), each image alone the old
     one (<= 72 tiles), same packed weights -- bit-identical results, and both within storage precision of the fp64 convolution."""
-    from ntire2022_esr_amd import ops, _lib as L
-    from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
+    from ntire2022_esr_amd import _lib as L
     dt = DT[compute]
-    g = torch.Generator().manual_seed(cin + cout + act + hw[0] + n)
-    cp = 48
-    x = torch.randn(n, cin, *hw, generator=g).to(dt)
-    w = torch.randn(cout, cin, 3, 3, generator=g) * 0.1
-    b = torch.randn(cout, generator=g)
-    table = (torch.randn(16, (cout + 15) // 16 * 16, generator=g) * 0.2) if border else None
-    if table is not None:
-        table[0] = 0                                    # row 0 = interior pixels of a border tile
-    blob = pack_conv_s16(w, b, compute, cin_phys=cp).to(DEV)
-    xin = F.pad(_nhwc(x), (0, cp - cin)).to(DEV)
-    kw = dict(act=act, cin=cin, packed=blob, border=None if table is None else table.to(DEV))
-    if res_in:
-        kw.update(res=xin, res_mode=L.RES_PRE_ACT)
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, hw[0], hw[1], cin, cout, 3
     d.in_layout = d.out_layout = L.NHWC
@@ -393,17 +350,14 @@ def test_conv48r_equals_conv_s16(compute, cin, cout, act, res_in, border, hw, n)
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 1
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) != 1
-    with ops.kernel_trace() as names:
-        y = ops.conv2d(xin, w, b, **kw)
+    case = P.conv48r(compute, n, hw, cin, cout, act, res_in, border)
+    names, y = case.names, case.outs[0]
     bf = "true" if compute == "bf16" else "false"
     want = f"conv64m_kernel<{bf}, false, false, 3, true>" if act == 3 and res_in and border and cout > 32 else \
         f"conv48r_kernel<{bf}, {(cout + 15) // 16}, {'true' if cout <= 32 or border or res_in or act == 3 else 'false'}, "
     assert len(names) == 1 and names[0].startswith(want), names
     for i in range(n):
-        kw1 = dict(kw)
-        if res_in:
-            kw1["res"] = xin[i:i + 1]
-        y1 = ops.conv2d(xin[i:i + 1].contiguous(), w, b, **kw1)
+        y1 = case.chunk(i, i + 1)[0][0]
         if act == 3 and res_in and border and cout > 32:
             # ESDB's c{j}_r shape: since round 6 the batch runs on conv64m_kernel<.., 3, true> (v_mfma_f32_32x32x16, another accumulation order;
             # its fp64-reference check: test_gpu_c64m.py) -- equal but for values on a rounding boundary, those one storage step apart
@@ -411,11 +365,7 @@ def test_conv48r_equals_conv_s16(compute, cin, cout, act, res_in, border, hw, n)
         else:
             assert torch.equal(y[i:i + 1], y1), i
     if not border:
-        weff, _ = unpack_conv_s16(blob.cpu(), cin, cout, 3, compute, cin_phys=cp)
-        conv = F.conv2d(x.double().to(DEV), weff.double().to(DEV), b.double().to(DEV), padding=1)
-        if res_in:
-            conv = conv + x.double().to(DEV)[:, :cout]
-        ref = ACTS[act](conv)
+        ref = case.refs[0]
         got = y.permute(0, 3, 1, 2)[:, :cout].double()
         eps = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
         tol = ref.abs() * eps * 1.01 + (3e-4 if act == 3 else 5e-5) * max(1.0, float(ref.abs().max()))
@@ -431,23 +381,14 @@ def test_conv48rp_equals_conv_s16(compute, hw, n, mf, nf, f):
     """conv48rp_kernel (RLFB c3_r + block input -> c5 -> esa.conv1: weights in registers, 16 x 16 tiles, the residual staged by each wave
     for its own rows, post images in LDS, the chain on both rows of a pair) against conv_s16_kernel: the batch takes the new kernel
     (>= 256 tiles of 16 x 16), each image alone the old one -- both outputs bit-identical, ragged edges included."""
-    from ntire2022_esr_amd import ops, _lib as L
-    dt = DT[compute]
-    g = torch.Generator().manual_seed(hw[0] + n)
-    x = F.pad(_nhwc(torch.randn(n, mf, *hw, generator=g).to(dt)), (0, 48 - mf)).to(DEV)
-    r = F.pad(_nhwc(torch.randn(n, nf, *hw, generator=g).to(dt)), (0, 48 - nf)).to(DEV)
-    w, b = torch.randn(nf, mf, 3, 3, generator=g) * 0.1, torch.randn(nf, generator=g)
-    w5, b5 = torch.randn(nf, nf, generator=g) * 0.2, torch.randn(nf, generator=g)
-    w1, b1 = torch.randn(f, nf, generator=g) * 0.2, torch.randn(f, generator=g)
-    kw = dict(act=1, res_mode=2, post_weight=w5, post_bias=b5, post2_weight=w1, post2_bias=b1, store_main=False, cin=mf)
     tiles16 = lambda nn: nn * ((hw[1] + 15) // 16) * ((hw[0] + 15) // 16)
     assert tiles16(n) >= 256 and tiles16(1) < 256
-    with ops.kernel_trace() as names:
-        y, yv, yc = ops.conv2d(x, w, b, res=r, **kw)
+    case = P.rlfb_post(compute, n, hw, mf, nf, f, hw[0] + n)
+    names, y, (yv, yc) = case.names, case.extra["main"], case.outs
     assert len(names) == 1 and names[0].startswith(f"conv48rp_kernel<{'true' if compute == 'bf16' else 'false'}, false>"), names
     assert y is None
     for i in range(n):
-        _, v1, c1 = ops.conv2d(x[i:i + 1].contiguous(), w, b, res=r[i:i + 1].contiguous(), **kw)
+        v1, c1 = case.chunk(i, i + 1)[0]
         assert torch.equal(yv[i:i + 1], v1) and torch.equal(yc[i:i + 1], c1), i
 
 
@@ -468,16 +409,10 @@ def test_s16_hilo_skip_convs(n, c, hw):
     upsampler:  y = shuffle(conv(x_hi + x_lo))  against the fp64 convolution of the SUM with the blob's effective weights"""
     from ntire2022_esr_amd import _lib as L, ops
     from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
-    g = torch.Generator().manual_seed(n * 1000 + c + hw[0])
     cp = (c + 15) // 16 * 16
-    x = torch.randn(n, c, *hw, generator=g).to(torch.bfloat16)
-    r32 = torch.randn(n, c, *hw, generator=g) * 3.0
-    w = torch.randn(c, c, 3, 3, generator=g) * 0.1
-    b = torch.randn(c, generator=g)
-    blob = pack_conv_s16(w, b, "bf16", cin_phys=cp)
-    weff, _ = unpack_conv_s16(blob, c, c, 3, "bf16", cin_phys=cp)
-    xin = F.pad(_nhwc(x), (0, cp - c)).to(DEV)
-    conv = F.conv2d(x.double(), weff.double(), b.double(), padding=1)
+    head = P.hilo_head(n, c, c, hw)
+    e = head.extra
+    g, x, r32, w, b, blob, xin, conv, plain = e["g"], e["x"], e["r32"], e["w"], e["b"], e["blob"], e["xin"], e["conv"].cpu(), e["plain"]
 
     def check(y, ref, what):
         assert y.dtype == torch.bfloat16 and tuple(y.shape) == (2, n, *hw, cp)
@@ -488,9 +423,7 @@ def test_s16_hilo_skip_convs(n, c, hw):
         assert float((lo.abs() > hi.abs() * 2.0 ** -7 + 1e-30).float().mean()) < 1e-3, what         # the low parts are remainders of the high ones
         return hi
 
-    plain = ops.conv2d(xin, w, b, cin=c, packed=blob.to(DEV))
-    y = ops.conv2d(xin, w, b, cin=c, packed=blob.to(DEV), hilo=L.HILO_OUT)
-    hi = check(y, conv, "head")
+    hi = check(head.outs[0], conv, "head")
     assert torch.equal(hi[..., :plain.shape[-1]], plain.float().cpu()), "the high parts are the plain kernel's output"
     rin = _hilo(r32, cp).to(DEV)
     rsum = (rin[0].double() + rin[1].double()).cpu().permute(0, 3, 1, 2)[:, :c]
@@ -549,19 +482,8 @@ def test_conv64r_equals_conv_s16(compute, cin, cout, act, res_in, hw, n):
     alone the general one (< 256 tiles), same packed weights.  Two output tiles: conv64r_kernel, bit-identical results; four: conv64m_kernel
     (round 6, 32x32x16 MFMAs and nine taps: another accumulation order), equal to one storage step.  Both within storage precision of the
     fp64 convolution."""
-    from ntire2022_esr_amd import ops, _lib as L
-    from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
+    from ntire2022_esr_amd import _lib as L
     dt = DT[compute]
-    g = torch.Generator().manual_seed(cin + cout + act + hw[0] + n)
-    cp = 64
-    x = torch.randn(n, cin, *hw, generator=g).to(dt)
-    w = torch.randn(cout, cin, 3, 3, generator=g) * 0.1
-    b = torch.randn(cout, generator=g)
-    blob = pack_conv_s16(w, b, compute, cin_phys=cp).to(DEV)
-    xin = F.pad(_nhwc(x), (0, cp - cin)).to(DEV)
-    kw = dict(act=act, cin=cin, packed=blob)
-    if res_in:
-        kw.update(res=xin, res_mode=L.RES_PRE_ACT)
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, hw[0], hw[1], cin, cout, 3
     d.in_layout = d.out_layout = L.NHWC
@@ -569,24 +491,17 @@ def test_conv64r_equals_conv_s16(compute, cin, cout, act, res_in, hw, n):
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 1
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) != 1
-    with ops.kernel_trace() as names:
-        y = ops.conv2d(xin, w, b, **kw)
+    case = P.conv64(compute, n, hw, cin, cout, act, res_in)
+    names, y = case.names, case.outs[0]
     bf = "true" if compute == "bf16" else "false"
     assert len(names) == 1 and names[0].startswith(f"conv64m_kernel<{bf}, false, false, 4, false>" if cout > 48 else f"conv64r_kernel<{bf}, 2,"), names
     for i in range(n):
-        kw1 = dict(kw)
-        if res_in:
-            kw1["res"] = xin[i:i + 1]
-        y1 = ops.conv2d(xin[i:i + 1].contiguous(), w, b, **kw1)
+        y1 = case.chunk(i, i + 1)[0][0]
         if cout > 48:      # 64 outputs: the batch runs on conv64m_kernel (32x32x16 MFMAs, nine taps, another accumulation order) since round 6
             assert _same_or_one_step(y[i:i + 1], y1, dt), i
         else:
             assert torch.equal(y[i:i + 1], y1), i
-    weff, _ = unpack_conv_s16(blob.cpu(), cin, cout, 3, compute, cin_phys=cp)
-    conv = F.conv2d(x.double().to(DEV), weff.double().to(DEV), b.double().to(DEV), padding=1)
-    if res_in:
-        conv = conv + x.double().to(DEV)[:, :cout]
-    ref = ACTS[act](conv)
+    ref = case.refs[0]
     got = y.permute(0, 3, 1, 2)[:, :cout].double()
     eps = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
     tol = ref.abs() * eps * 1.01 + (3e-4 if act == 3 else 5e-5) * max(1.0, float(ref.abs().max()))
@@ -600,18 +515,10 @@ def test_conv48rl_equals_conv_s16(hw, n, c, act):
     (conv + hi) + lo, hi / lo stores) against conv_s16_kernel's HILO instantiation: the batch takes the new kernel (>= 256 tiles of
     16 x 16, esr_conv_block_waves == 1), each image alone the old one -- both tensors of the output pair bit-identical, ragged edges
     included; and hi + lo is the fp64 result to two bf16 numbers."""
-    from ntire2022_esr_amd import _lib as L, ops
-    from ntire2022_esr_amd.engine import pack_conv_s16, unpack_conv_s16
-    g = torch.Generator().manual_seed(n * 100 + c + hw[0])
+    from ntire2022_esr_amd import _lib as L
     cp = 48
-    x = torch.randn(n, c, *hw, generator=g).to(torch.bfloat16)
-    r32 = torch.randn(n, c, *hw, generator=g) * 3.0
-    w = torch.randn(c, c, 3, 3, generator=g) * 0.1
-    b = torch.randn(c, generator=g)
-    blob = pack_conv_s16(w, b, "bf16", cin_phys=cp).to(DEV)
-    weff, _ = unpack_conv_s16(blob.cpu(), c, c, 3, "bf16", cin_phys=cp)
-    xin = F.pad(_nhwc(x), (0, cp - c)).to(DEV)
-    rin = _hilo(r32, cp).to(DEV)
+    case = P.lr_hilo(n, c, hw, act, cp)
+    names, y, rin = case.names, case.outs[0], case.extra["rin"]
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, hw[0], hw[1], c, c, 3
     d.in_layout = d.out_layout = L.NHWC
@@ -620,16 +527,12 @@ def test_conv48rl_equals_conv_s16(hw, n, c, act):
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 1
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 8
-    kw = dict(cin=c, packed=blob, act=act, res_mode=L.RES_PRE_ACT, hilo=L.HILO_RES | L.HILO_OUT)
-    with ops.kernel_trace() as names:
-        y = ops.conv2d(xin, w, b, res=rin, **kw)
     assert len(names) == 1 and names[0].startswith("conv48rp_kernel<true, true>"), names
     assert tuple(y.shape) == (2, n, *hw, cp)
     for i in range(n):
-        y1 = ops.conv2d(xin[i:i + 1].contiguous(), w, b, res=rin[:, i:i + 1].contiguous(), **kw)
+        y1 = case.chunk(i, i + 1)[0][0]
         assert torch.equal(y[:, i:i + 1], y1), i
-    rsum = (rin[0].double() + rin[1].double()).permute(0, 3, 1, 2)[:, :c]
-    ref = ACTS[act](F.conv2d(x.double().to(DEV), weff.double().to(DEV), b.double().to(DEV), padding=1) + rsum)
+    ref = case.refs[0]
     got = (y[0].double() + y[1].double()).permute(0, 3, 1, 2)[:, :c]
     tol = ref.abs() * 2.0 ** -15 + 3e-5 * max(1.0, float(ref.abs().max()))
     assert int(((got - ref).abs() > tol).sum()) == 0
@@ -660,22 +563,9 @@ def test_conv48rq_equals_conv_s16(hw, n, border, act, pact, c, pc):
     """conv48rq_kernel (fp16: ESDB c{j}_r as a dense BSConvU + input + GELU, stored, with the next distillation 1x1 + GELU as 87 micro-operations
     behind the next row pair's MFMAs) against conv_s16_kernel<3, 3, 8, .., 2, 0>: the batch takes the new kernel (>= 256 tiles of 16 x 16,
     esr_conv_block_waves == 1), each image alone the old one -- both outputs bit-identical, ragged edges and the border table included."""
-    from ntire2022_esr_amd import ops, _lib as L
-    from ntire2022_esr_amd.engine import pack_conv_s16
-    g = torch.Generator().manual_seed(n * 10 + hw[0])
-    x = F.pad(torch.randn(n, *hw, c, generator=g), (0, 48 - c)).to(torch.float16).to(DEV)
-    w, b = torch.randn(c, c, 3, 3, generator=g) * 0.1, torch.randn(c, generator=g)
-    wp, bp = torch.randn(pc, c, generator=g) * 0.2, torch.randn(pc, generator=g)
-    table = None
-    if border:
-        table = torch.randn(16, 48, generator=g) * 0.2
-        table[0] = 0
-        table[:, c:] = 0
-        table = table.to(DEV)
-    blob = pack_conv_s16(w, b, "f16").to(DEV)
-    kw = dict(act=act, packed=blob, border=table, res_mode=L.RES_PRE_ACT, post_weight=wp, post_bias=bp, post_act=pact, cin=c)
-    with ops.kernel_trace() as names:
-        y, yp = ops.conv2d(x, w, b, res=x, **kw)
+    from ntire2022_esr_amd import _lib as L
+    case = P.conv48rq(hw, n, border, act, pact, c, pc)
+    names, (y, yp), x, blob = case.names, case.outs, case.extra["x"], case.extra["blob"]
     assert len(names) == 1 and names[0].startswith("conv64m_kernel<false, true, false, 3, true>" if border and act == 3 and pact == 3 else "conv48rq_kernel<false,"), names
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, hw[0], hw[1], c, c, 3
@@ -688,8 +578,7 @@ def test_conv48rq_equals_conv_s16(hw, n, border, act, pact, c, pc):
     d.n = 1
     assert L.lib().esr_conv_block_waves(ctypes.byref(d)) == 8
     for i in range(n):
-        xi = x[i:i + 1].contiguous()
-        y1, p1 = ops.conv2d(xi, w, b, res=xi, **kw)
+        y1, p1 = case.chunk(i, i + 1)[0]
         if border and act == 3 and pact == 3:
             # (the batch: conv64m_kernel<false, true, false, 3, true> since round 6 -- another accumulation order, see test_conv48r_equals_conv_s16)
             assert _same_or_one_step(y[i:i + 1], y1, torch.float16) and _same_or_one_step(yp[i:i + 1], p1, torch.float16, frac=0.2, scale=10.0), i

@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _persist_cases as P
+
 pytestmark = pytest.mark.gpu
 
 ACTS = {0: lambda v: v, 1: lambda v: F.leaky_relu(v, 0.05), 2: F.relu, 3: F.gelu}
@@ -176,21 +178,9 @@ def _w8_on(on):
 def test_wino8_plain(cin, cout, n, h, w, act):
     """strip-autonomous kernel vs ATen fp32 on ragged sizes (partial strips on the right / bottom edge, several strips per wave, strips
     that straddle image boundaries of the batch), and vs wino_f32_kernel: the same fp32 operations per output -> bit-identical"""
-    from ntire2022_esr_amd import ops
-    dev = _dev()
-    g = torch.Generator().manual_seed(cin + cout + h)
-    x = torch.randn(n, cin, h, w, generator=g)
-    wt = torch.randn(cout, cin, 3, 3, generator=g) * 0.1
-    b = torch.randn(cout, generator=g)
-    ref = ACTS[act](F.conv2d(x, wt, b, padding=1))
-    xd = _nhwc(x).to(dev)
-    if cin % 8:
-        xd = F.pad(xd, (0, 8 - cin % 8))
-    _w8_on(True)
-    y8 = ops.conv2d(xd, wt, b, act=act, cin=cin, wino=True)
-    _w8_on(False)
-    y4 = ops.conv2d(xd, wt, b, act=act, cin=cin, wino=True)
-    _w8_on(True)
+    _dev()
+    case = P.wino8(cin, cout, n, h, w, act)
+    y8, y4, ref = case.outs[0], case.extra["general"][0], case.extra["ref32"]
     _check(y8, ref)
     assert torch.equal(y8, y4)
 
@@ -244,17 +234,11 @@ def test_wino8_blocked_input(n, h, w):
     NHWC input through the same kernel family"""
     from ntire2022_esr_amd import ops
     dev = _dev()
-    g = torch.Generator().manual_seed(31 + h)
-    x = torch.randn(n, 48, h, w, generator=g)
-    wt = torch.randn(64, 48, 3, 3, generator=g) * 0.1
-    b = torch.randn(64, generator=g)
-    ref = F.leaky_relu(F.conv2d(x, wt, b, padding=1), 0.05)
-    xb = x.view(n, 6, 8, h, w).permute(0, 1, 3, 4, 2).contiguous().to(dev)
-    cat = torch.zeros((n, h, w, 16), device=dev)
-    remb = torch.full((n, 6, h, w, 8), 9.0, device=dev)
-    ops.conv2d(xb, wt, b, act=1, blocked_in=True, split=16, out=cat, out1=remb, blocked_out1=True, wino=True)
+    case = P.wino8(48, 64, n, h, w, 1, blocked_out1=True, blocked_in=True, seed=31 + h)
+    x, wt, b, ref = case.extra["x"], case.extra["w"], case.extra["b"], case.extra["ref32"]
+    cat, rem = case.outs[0][..., :16], case.outs[0][..., 16:]                 # the 16 / 48 split, the blocked out1 read back as NHWC
     _check(cat.cpu(), ref[:, :16])
-    r = remb.cpu().permute(0, 1, 4, 2, 3).reshape(n, 48, h, w)
+    r = rem.cpu().permute(0, 3, 1, 2)
     assert float((r - ref[:, 16:]).abs().max()) / max(1.0, float(ref.abs().max())) < 2e-5
     y_nhwc = ops.conv2d(_nhwc(x).to(dev), wt, b, act=1, wino=True)
     assert torch.equal(y_nhwc[..., :16], cat) and torch.equal(y_nhwc[..., 16:].cpu(), r.permute(0, 2, 3, 1))
