@@ -420,7 +420,9 @@ typedef enum esr_op_kind {
     ESR_OP_RESBLOCK_HEAD = 11,  /* esr_resblock_head_s16 on esr_op.conv (additive within ABI v12) */
     ESR_OP_REFINE_CASCADE = 12, /* esr_refine_cascade_s16 on esr_op.chain (additive within ABI v12) */
     ESR_OP_DWCONV7 = 13,        /* esr_dwconv7x7 on esr_op.conv (additive within ABI v12) */
-    ESR_OP_CX_BLOCK = 14        /* esr_cx_block_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_CX_BLOCK = 14,       /* esr_cx_block_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_DWPW_PAIR = 15,      /* esr_dwpw_pair_s16 on esr_op.chain (additive within ABI v12) */
+    ESR_OP_ESA_UNSHUFFLE = 16   /* esr_esa_unshuffle_f32 on esr_op.esa (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -648,14 +650,61 @@ int    esr_pack_cx_pw2_s16(const float* w_out_mid, const float* bias, int cmid, 
 int    esr_cx_block_supported(const esr_chain_desc* d);
 int    esr_cx_block_s16(const esr_chain_desc* d, void* hip_stream);
 
+/*
+ * esr_dwpw_pair_s16 (additive within ABI v12; op kind ESR_OP_DWPW_PAIR on esr_op.chain) -- the refinement path of team 35's RFDB,
+ * `conv_four_layer(C)` and the block's `act(c_r(x) + x)` behind it (models/team35_rfdn/rmsrb1.py:22-27, :199-210), as ONE launch on 16-bit
+ * storage (dwpw_pair_kernel, csrc/esr_dwpw.hip):
+ *     u1  = dw3_a(in) + in                    depthwise 3x3, zero padding, bias, + its input; never stored
+ *     h   = relu(Wa . u1 + ba)                1x1, C -> C, never stored
+ *     u2  = dw3_b(h) + h                      never stored; dw3_b sees h zero-padded like a stored tensor (0 outside the image, not relu(ba))
+ *     out = act(Wb . u2 + bb + in)            1x1, C -> C, stored to post_out
+ * u1, h, u2 and out are each rounded once to the storage type, exactly where two esr_dwconv3x3_f32 launches (res = their input,
+ * ESR_RES_PRE_ACT) and two esr_conv2d_f32 1x1s would store them; Wa and Wb are rounded once to the storage type (the separate 1x1 launches
+ * multiply by hi + lo pairs), so the result is within one rounding per stage of those launches, not bit-identical to them.  An
+ * esr_chain_desc carries it, no field added:
+ *     n_layers            4
+ *     in, cin             the block input and its channels C, 33 .. 64 (round_up(C, 8) channels are read from coff)
+ *     cmid, cout          == cin
+ *     act, slope          ESR_ACT_LRELU and its slope (the last layer; the hidden activation is ReLU)
+ *     res_mode            ESR_RES_PRE_ACT: `in` is added to the last layer's result before the activation
+ *     storage, compute    ESR_STORE_BF16 / ESR_COMPUTE_BF16 or ESR_STORE_F16 / ESR_COMPUTE_F16
+ *     wpacked[0..3]       esr_pack_dw_f32 (dw3_a), esr_pack_cx_pw1_s16 (Wa [C, C], ba; cin = cmid = C), esr_pack_dw_f32 (dw3_b),
+ *                         esr_pack_cx_pw1_s16 (Wb, bb)
+ *     post_out, post_cout the result and the channels stored: a multiple of 8 in cout .. round_up(cout, 16); channels >= cout are zeros
+ *     post_wpacked, post2_wpacked   NULL
+ * The result may not be stored into `in`'s tensor: neighbouring tiles read its halo.
+ * esr_dwpw_pair_supported: 1 when the descriptor has this shape and a per-image input below 1 GiB; esr_dwpw_pair_s16 returns
+ * ESR_ERR_UNSUPPORTED for every other (fp32 storage and C outside 33 .. 64 included) and ESR_ERR_BAD_ARG for a null pointer, a view that is
+ * misaligned or does not hold its channels, or post_out.ptr == in.ptr.
+ */
+int    esr_dwpw_pair_supported(const esr_chain_desc* d);
+int    esr_dwpw_pair_s16(const esr_chain_desc* d, void* hip_stream);
+
+/*
+ * esr_esa_unshuffle_f32 (additive within ABI v12; op kind ESR_OP_ESA_UNSHUFFLE on esr_op.esa) -- the low-resolution branch of team 35's ESA
+ * (models/team35_rfdn/rmsrb1.py:137-144) in one launch (esa_unshuffle_kernel, csrc/esr_esa_unshuffle.hip):
+ *     c3 = relu(con_(relu(max_pool2d(pixel_unshuffle(c1_, 2), 7, stride 3))))
+ * pixel_unshuffle as the reference writes it, a stride-2 convolution: unshuffled channel 4 c + 2 dy + dx is channel c of c1_ at
+ * (2 y + dy, 2 x + dx), and an odd h or w is floored (h2 = h / 2).  con_ = nn.Conv2d(4 f, f, 1, padding 1): its output is two pixels larger
+ * each way than the pooled map and its border ring equals relu(bias).
+ *     n, h, w, f, storage  the conv1 map's dims, ESA width (<= 16) and esr_storage; h, w >= 14 (ESR_ERR_TOO_SMALL below)
+ *     x                    the conv1 map [n][h][w][pitch] in `storage`, f channels from coff
+ *     y, h_lo, w_lo        c3 [n][h_lo][w_lo][pitch >= 16] fp32 with h_lo = h3 + 2, h3 = (h / 2 - 7) / 3 + 1 (likewise w_lo): 16 channels are
+ *                          written from coff, the pad channels f .. 15 as zeros
+ *     w0                   esr_pack_dense_f32(con_, k = 1, cin_p = 4 f, cout_p = 16)
+ * ESR_ERR_BAD_ARG for a null pointer, f outside 1 .. 16, an unknown storage, a view that does not hold its channels, or h_lo / w_lo other
+ * than the above.
+ */
+int esr_esa_unshuffle_f32(const esr_esa_desc* d, void* hip_stream);
+
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
     esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD */
-    esr_esa_desc esa;           /* the four ESA kinds */
+    esr_esa_desc esa;           /* the four ESA kinds, ESR_OP_ESA_UNSHUFFLE */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */
-    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP, ESR_OP_REFINE_CASCADE, ESR_OP_CX_BLOCK */
+    esr_chain_desc chain;       /* ESR_OP_CONV_CHAIN (ABI v11), ESR_OP_DISTILL_STEP, ESR_OP_REFINE_CASCADE, ESR_OP_CX_BLOCK, ESR_OP_DWPW_PAIR */
 } esr_op;
 
 /* ABI v5 -- the network input for the 16-bit plans: NCHW fp32 [n, cin <= 4, h, w] (d->in.ptr) -> NHWC 16-bit (d->out0, pitch >= 16,

@@ -8,6 +8,7 @@ Package contents (only what the path needs):
 """
 from .bmdn import BMDN  # noqa: F401
 from .bsrn import BSRN  # noqa: F401
+from .dwrfdn import DWRFDN  # noqa: F401
 from .efdn import PLAINRFDN  # noqa: F401
 from .esan import ESAN  # noqa: F401
 from .fmen import FMEN  # noqa: F401
@@ -17,4 +18,4 @@ from .rfdn import RFDN  # noqa: F401
 from .rfdnext import RFDNeXt  # noqa: F401
 from .rlfn import RLFN_cut  # noqa: F401
 
-__all__ = ["BMDN", "BSRN", "ESAN", "FMEN", "FasterRFDN", "IMDN", "PLAINRFDN", "RFDN", "RFDNeXt", "RLFN_cut"]
+__all__ = ["BMDN", "BSRN", "DWRFDN", "ESAN", "FMEN", "FasterRFDN", "IMDN", "PLAINRFDN", "RFDN", "RFDNeXt", "RLFN_cut"]

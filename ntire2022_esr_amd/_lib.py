@@ -26,6 +26,8 @@ OP_RESBLOCK_HEAD = 11                                                     # ESAN
 OP_REFINE_CASCADE = 12                                                    # FasterRFDN's refinement cascade (esr_refine_cascade_s16 on Op.chain)
 OP_DWCONV7 = 13                                                           # depthwise 7x7 (esr_dwconv7x7 on Op.conv)
 OP_CX_BLOCK = 14                                                          # RFDNeXt's ConvNeXt block (esr_cx_block_s16 on Op.chain)
+OP_DWPW_PAIR = 15                                                         # team 35's depthwise-pointwise residual pair (esr_dwpw_pair_s16 on Op.chain)
+OP_ESA_UNSHUFFLE = 16                                                     # team 35's ESA low-resolution branch (esr_esa_unshuffle_f32 on Op.esa)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -150,6 +152,7 @@ EXPORTS = [
     "esr_resblock_head_supported", "esr_resblock_head_s16", "esr_refine_cascade_supported", "esr_refine_cascade_s16",
     "esr_packed_dw7_bytes", "esr_pack_dw7_f32", "esr_dwconv7x7_supported", "esr_dwconv7x7",
     "esr_packed_cx_pw1_bytes", "esr_pack_cx_pw1_s16", "esr_packed_cx_pw2_bytes", "esr_pack_cx_pw2_s16", "esr_cx_block_supported", "esr_cx_block_s16",
+    "esr_dwpw_pair_supported", "esr_dwpw_pair_s16", "esr_esa_unshuffle_f32",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -294,6 +297,12 @@ def lib():
     L.esr_cx_block_supported.restype = ci
     L.esr_cx_block_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
     L.esr_cx_block_s16.restype = ci
+    L.esr_dwpw_pair_supported.argtypes = [ctypes.POINTER(ChainDesc)]
+    L.esr_dwpw_pair_supported.restype = ci
+    L.esr_dwpw_pair_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
+    L.esr_dwpw_pair_s16.restype = ci
+    L.esr_esa_unshuffle_f32.argtypes = [ctypes.POINTER(EsaDesc), vp]
+    L.esr_esa_unshuffle_f32.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

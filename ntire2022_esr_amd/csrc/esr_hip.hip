@@ -1200,6 +1200,8 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_REFINE_CASCADE: return esr_refine_cascade_s16(&op.chain, hip_stream);
         case ESR_OP_DWCONV7: return esr_dwconv7x7(&op.conv, hip_stream);
         case ESR_OP_CX_BLOCK: return esr_cx_block_s16(&op.chain, hip_stream);
+        case ESR_OP_DWPW_PAIR: return esr_dwpw_pair_s16(&op.chain, hip_stream);
+        case ESR_OP_ESA_UNSHUFFLE: return esr_esa_unshuffle_f32(&op.esa, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

@@ -268,6 +268,46 @@ def cx_pw_fragments(blob1, blob2, cmid, compute):
     return tuple(out)
 
 
+def pack_dwpw_pw(weight, bias, compute):
+    """A C -> C 1x1 of team 35's refinement path for esr_dwpw_pair_s16: w [C, C(, 1, 1)] -> the esr_pack_cx_pw1_s16 blob with cin = cmid = C
+    (MFMA A fragments in natural K order, rounded once to the storage type; the bias stays fp32)."""
+    lib = L.lib()
+    a = _pack_args(weight, bias, compute=compute, flat=True)
+    cout, cin = a.w.shape
+    nbytes = lib.esr_packed_cx_pw1_bytes(cin, cout) if cin == cout else 0
+    if not nbytes:
+        raise L.EsrError("pack_dwpw_pw: a square 1x1 of at most 64 channels")
+    out = torch.empty(nbytes // 4, dtype=torch.float32)
+    L.check(lib.esr_pack_cx_pw1_s16(_ptr(a.w), _ptr(a.b), cin, cout, a.compute, _ptr(out), nbytes), "esr_pack_cx_pw1_s16")
+    return out
+
+
+def dwpw_pw_effective(blob, c, compute):
+    """EFFECTIVE weights [C, C] (what dwpw_pair_kernel multiplies by) and bias [C] of a pack_dwpw_pw blob, as float64 tensors (tests)."""
+    nt = (c + 31) // 32 * 2
+    dt = torch.bfloat16 if compute == "bf16" else torch.float16
+    raw = blob.detach().to("cpu").contiguous().view(torch.uint8)
+    img = raw[:nt * 2048].view(dt).to(torch.float64).reshape(nt, 2, 4, 16, 8)        # (mt, ks, kq, row, j)
+    w = img.permute(0, 3, 1, 2, 4).reshape(nt * 16, 64)                              # row mt * 16 + r, column ks * 32 + kq * 8 + j
+    b = raw[nt * 2048:nt * 2048 + 4 * 16 * nt].view(torch.float32).to(torch.float64)
+    return w[:c, :c].clone(), b[:c].clone()
+
+
+def pack_unshuffle(weight, bias):
+    """`con_` of team 35's ESA, nn.Conv2d(4 f, f, 1, padding 1), for esr_esa_unshuffle_f32: the esr_pack_dense_f32 blob [4 f][16] + bias[16]
+    (the pad outputs f .. 15: zero columns, zero bias)."""
+    w = _host(weight)
+    assert w.dim() == 4 and tuple(w.shape[2:]) == (1, 1) and w.shape[1] == 4 * w.shape[0] and w.shape[0] <= L.ESA_FP
+    return pack_dense(w, bias, w.shape[1], L.ESA_FP)
+
+
+def unpack_unshuffle(blob, f):
+    """[f, 4 f, 1, 1] weights and bias of a pack_unshuffle blob (tests)."""
+    blob = _host(blob)
+    img = blob[:4 * f * L.ESA_FP].reshape(4 * f, L.ESA_FP)
+    return img[:, :f].t().reshape(f, 4 * f, 1, 1).contiguous(), blob[4 * f * L.ESA_FP:4 * f * L.ESA_FP + f].clone()
+
+
 def fold_center(w_r, b_r, w_d, b_d):
     """A 3x3 and a 1x1 over the same input as ONE 3x3: W_r + the 1x1 on the centre tap, b_r + b_d, both summed in fp32
     (RFDNeXt: rc_1 = c1_r(x) + c1_d(x))."""
@@ -390,6 +430,7 @@ WINO = "#wino"     # esr_pack_wino_f32 blob of an fp32 3x3 (Winograd F(2x2, 3x3)
 DWPAD = "#pad16"   # pack_dw image of a depthwise 3x3 of fewer than 16 channels, zero-padded to 16 (Dw: low-resolution maps stored whole)
 CX1 = "#cx1"       # esr_pack_cx_pw1_s16 image of a ConvNeXt block's first 1x1 (CxBlock; pack_cx_pw)
 CX2 = "#cx2"       # esr_pack_cx_pw2_s16 image of its second 1x1
+DWPW = "#dwpw"     # pack_dwpw_pw image of a 1x1 of team 35's refinement path (DwPwPair)
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -694,6 +735,8 @@ class Dw(_Op):
     act: int = L.ACT_NONE
     slope: float = 0.05
     hw: tuple = None
+    res: object = None         # a view added before / behind the activation (res_mode), as Conv's
+    res_mode: int = L.RES_NONE
     kind = "dw"
 
     def encode(self, op, plan, base, weights):
@@ -707,6 +750,8 @@ class Dw(_Op):
         d.act, d.slope = self.act, self.slope
         d.in_layout = d.out_layout = L.NHWC
         d.inp, d.out0 = _view(self.src, base), _view(self.dst, base)
+        if self.res is not None:
+            d.res, d.res_mode = _view(self.res, base), self.res_mode
         d.storage = 0 if self.hw is not None else L.STORE[plan.store]
         w = self.w
         if (self.hw is not None and self.c < 16 and isinstance(self.src, Buffer) and isinstance(self.dst, Buffer)
@@ -719,8 +764,15 @@ class Dw(_Op):
 
     def cost(self, plan, desc):
         npix, e_act = (plan.npix, plan.esize) if self.hw is None else (plan.n * self.hw[0] * self.hw[1], 4)
-        return _cost(self.w, "dwconv3x3_kernel", self.c, self.c, 3, 2.0 * 9 * self.c * npix, float(npix * e_act * self.c),
+        # (a residual that IS the input is served by the caches, as in Conv.cost)
+        res_read = self.res is not None and not _same_view(self.res, self.src)
+        return _cost(self.w, "dwconv3x3_kernel", self.c, self.c, 3, 2.0 * 9 * self.c * npix, float(npix * e_act * self.c * (2 if res_read else 1)),
                      float(npix * e_act * self.c))
+
+    def dw_counted(self, plan):
+        """nn.Conv2d(c, c, 3, groups=c): one input channel per filter (for the networks that count their depthwise layers one by one)"""
+        npix = plan.npix if self.hw is None else plan.n * self.hw[0] * self.hw[1]
+        return [(1, self.c, 3, npix, self.act)]
 
 
 @dataclass
@@ -1169,6 +1221,82 @@ class CxBlock(_Fused):
 
 
 @dataclass
+class DwPwPair(_Fused):
+    """Team 35's refinement path as ONE esr_dwpw_pair_s16 op -- see Plan.dwpw_pair (dwpw_pair_kernel).  replaces: [dw_a, pw_a, dw_b, pw_b]."""
+    kind = "dwpw"
+    predicate, field, what = "esr_dwpw_pair_supported", "chain", "depthwise-pointwise pair"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 4 and [o.kind for o in sub] == ["dw", "conv", "dw", "conv"]
+        dwa, pwa, dwb, pwb = sub
+        assert all(o.k == 1 and o.post is None and o.tail is None and not o.hilo and o.hw is None and o.cin == dwa.c and o.cout == dwa.c for o in (pwa, pwb))
+        assert all(o.hw is None and o.act == L.ACT_NONE and o.c == dwa.c and o.res_mode == L.RES_PRE_ACT and _same_view(o.res, o.src) for o in (dwa, dwb))
+        assert pwa.act == L.ACT_RELU and pwa.res is None and pwb.act == L.ACT_LRELU
+        assert pwb.res_mode == L.RES_PRE_ACT and _same_view(pwb.res, dwa.src)       # + x in front of the last activation
+        assert _same_view(pwa.src, dwa.dst) and _same_view(dwb.src, pwa.dst) and _same_view(pwb.src, dwb.dst)
+        assert not _same_view(pwb.dst, dwa.src)
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        dwa, pwa, dwb, pwb = self.replaces
+        op.kind = L.OP_DWPW_PAIR
+        d = op.chain
+        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 4
+        d.cin = d.cmid = d.cout = dwa.c
+        d.act, d.slope, d.res_mode = L.ACT_LRELU, pwb.slope, L.RES_PRE_ACT
+        d.storage = d.compute = st
+        d.inp = _view(dwa.src, base)
+        d.wpacked[0] = weights[dwa.w].data_ptr()
+        d.wpacked[1] = weights[pwa.w + DWPW].data_ptr()
+        d.wpacked[2] = weights[dwb.w].data_ptr()
+        d.wpacked[3] = weights[pwb.w + DWPW].data_ptr()
+        d.post_out, d.post_cout = _view(pwb.dst, base), _stored_width(pwb.dst, pwb.cout)
+
+    def cost(self, plan, desc):             # x read once, the result written once
+        dwa, pwa, dwb, pwb = self.replaces
+        npix, es, c = plan.npix, plan.esize, dwa.c
+        flops = 2.0 * npix * 2 * (9 * c + c * c)
+        wb = 4.0 * 2 * (10 * c + c * c + c)
+        kern = f"dwpw_pair_kernel<{_tf(plan.store == 'bf16')}>"
+        stored = float(npix * es * (_stored_channels(dwa.src, c, 8) + _stored_channels(pwb.dst, c, 8))) + wb
+        return _cost(dwa.w, kern, c, c, 3, flops, float(npix * c * es) + wb, float(npix * es * c), stored)
+
+    def counted_convs(self, plan):
+        return [cv for o in self.replaces for cv in (o.dw_counted(plan) if o.kind == "dw" else o.counted_convs(plan))]
+
+
+@dataclass
+class Unshuffle(_Op):
+    """The low-resolution branch of team 35's ESA in one launch (esr_esa_unshuffle_f32) -- see Plan.esa_unshuffle"""
+    w: str
+    src: Buffer
+    dst: Buffer
+    f: int
+    kind = "unshuffle"
+
+    def encode(self, op, plan, base, weights):
+        op.kind = L.OP_ESA_UNSHUFFLE
+        e = op.esa
+        e.n, e.h, e.w, e.f, e.storage = plan.n, self.src.h, self.src.w, self.f, L.STORE[plan.store]
+        e.h_lo, e.w_lo = self.dst.h, self.dst.w
+        e.x, e.y = _view(self.src, base), _view(self.dst, base)
+        e.w0 = ctypes.c_void_p(weights[self.w].data_ptr())
+
+    def cost(self, plan, desc):             # the conv1 map read (about 49 / 36 times: the windows overlap), the small map written
+        f, npl = self.f, plan.n * self.dst.h * self.dst.w
+        return _cost(self.w, f"esa_unshuffle_kernel<{L.STORE[plan.store]}>", 4 * f, f, 1, 2.0 * 4 * f * f * npl,
+                     float(plan.n * self.src.h * self.src.w * f * self.src.esize) + 4.0 * (4 * f * f + f), float(npl * L.ESA_FP * 4))
+
+    def counted_convs(self, plan):            # con_ = nn.Conv2d(4 f, f, 1, padding 1): the reference's hooks see its padded output
+        return [(4 * self.f, self.f, 1, plan.n * self.dst.h * self.dst.w, L.ACT_RELU)]
+
+    def relu_elements(self, plan):
+        """elements of the ReLU in front of con_ (an nn.ReLU call on the pooled 4 f-channel map, which no convolution's count carries)"""
+        return 4 * self.f * plan.n * (self.dst.h - 2) * (self.dst.w - 2)
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1387,6 +1515,19 @@ class Plan:
         are rounded once where conv_s16_kernel multiplies by hi + lo pairs.  out must not be stored into v's tensor."""
         return self._fuse(mark, CxBlock)
 
+    def dwpw_pair(self, mark):
+        """The four ops appended since `mark = len(plan.ops)` -- the refinement path of team 35's RFDB in its per-op form, u1 = dw3_a(x) + x,
+        h = relu(pw_a(u1)), u2 = dw3_b(h) + h, r = lrelu(pw_b(u2) + x) (team35_rfdn/rmsrb1.py:22-27, :199-210) -- as ONE esr_dwpw_pair_s16 op
+        (16-bit plans): x is read once, r is written once, u1, h and u2 never exist.  The ops stay attached as `replaces`: complexity
+        counters and algorithmic costs are theirs; the 1x1 blobs are pack_dwpw_pw's (`<pw>#dwpw`).  Not bit-identical to the four launches:
+        the 1x1 weights are rounded once where conv_s16_kernel multiplies by hi + lo pairs.  r must not be stored into x's tensor."""
+        return self._fuse(mark, DwPwPair)
+
+    def esa_unshuffle(self, wname, c1, dst, f):
+        """c3 = relu(con_(relu(max_pool2d(pixel_unshuffle(c1, 2), 7, 3)))) (team35_rfdn/rmsrb1.py:140-144) in one launch, every storage
+        (esr_esa_unshuffle_f32); `wname` names a pack_unshuffle blob; dst is the low-resolution fp32 map [n][h3 + 2][w3 + 2][16]."""
+        self.ops.append(Unshuffle(wname, c1, dst, f))
+
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [Post(w, dst, cout, act, slope, res), ...] -- one or two 1x1 convolutions evaluated in the same launch
@@ -1522,6 +1663,7 @@ class HipSRModel(nn.Module):
         self._fuse_step = True     # 16-bit BMDN plans: a distillation step as one esr_distill_step_s16 launch (Plan.distill_step); measured: DESIGN.md 7d
         self._fuse_head = True     # 16-bit ESAN plans: a residual block's head as one esr_resblock_head_s16 launch (Plan.resblock_head); measured: DESIGN.md 7e
         self._fuse_cascade = False # 16-bit FasterRFDN plans: FRFDB's refinement path as one esr_refine_cascade_s16 launch (Plan.refine_cascade); OFF: faster on one image, not at 32 x 256 x 256
+        self._fuse_pair = True     # 16-bit DWRFDN plans: the depthwise-pointwise refinement path as one esr_dwpw_pair_s16 launch (Plan.dwpw_pair); measured: DESIGN.md 7h
         self._fuse_cx = True       # 16-bit RFDNeXt plans: the ConvNeXt block as one esr_cx_block_s16 launch (Plan.cx_block); measured: DESIGN.md 7g
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
@@ -1582,6 +1724,7 @@ class HipSRModel(nn.Module):
     fuse_head = property(lambda self: self._fuse_head, lambda self, v: self._set_flag("_fuse_head", v))
     fuse_cascade = property(lambda self: self._fuse_cascade, lambda self, v: self._set_flag("_fuse_cascade", v))
     fuse_cx = property(lambda self: self._fuse_cx, lambda self, v: self._set_flag("_fuse_cx", v))
+    fuse_pair = property(lambda self: self._fuse_pair, lambda self, v: self._set_flag("_fuse_pair", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels

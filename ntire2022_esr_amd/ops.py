@@ -7,7 +7,8 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .engine import pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw7, pack_post_s16, pack_wino
+from .engine import (pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_post_s16, pack_unshuffle,
+                     pack_wino)
 
 
 def _view(t, coff=0):
@@ -478,6 +479,92 @@ def cx_block(v, w0, b0, w1, b1, w2, b2, *, slope=0.05, in_coff=0, out=None, out_
         raise L.EsrError("cx_block: no kernel for this shape (esr_cx_block_supported)")
     stream = torch.cuda.current_stream(v.device).cuda_stream
     _launch("esr_cx_block_s16", "esr_cx_block_s16", d, stream, L.OP_CX_BLOCK, "chain")
+    return y
+
+
+def dwconv3x3(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.RES_NONE, in_coff=0, res_coff=0, out=None, out_coff=0):
+    """esr_dwconv3x3_f32: depthwise nn.Conv2d(C, C, 3, 1, 1, groups=C) with zero padding and bias on an NHWC tensor x [N, H, W, P] (C channels
+    from in_coff) in fp32, bf16 or fp16 storage, + res before / behind the activation (res_mode).  weight [C, 1, 3, 3].
+    out: a caller-provided NHWC tensor of x's dtype and device (another tensor than x) that receives round_up(C, 4) channels from out_coff;
+    default: freshly allocated zeros of pitch round_up(C, granule)."""
+    if not x.is_cuda:
+        raise L.EsrError("dwconv3x3: tensors must live on the GPU; there is no CPU fallback")
+    st = _STORE_OF[x.dtype]
+    gran = 4 if st == "f32" else 8
+    n, h, w, _ = x.shape
+    c = weight.shape[0]
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, h, w, c, c, 3
+    d.in_layout = d.out_layout = L.NHWC
+    d.act, d.slope, d.res_mode = act, slope, res_mode
+    d.storage = L.STORE[st]
+    d.inp = _view(x, in_coff)
+    if res is not None:
+        d.res = _view(res, res_coff)
+    keep = pack_dw(weight, bias).to(x.device)
+    d.wpacked = keep.data_ptr()
+    y = _zeros_or(out, "dwconv3x3: out", x, (n, h, w), (c + gran - 1) // gran * gran, gran)
+    d.out0 = _view(y, out_coff)
+    _launch("esr_dwconv3x3_f32", "esr_dwconv3x3_f32", d, torch.cuda.current_stream(x.device).cuda_stream, L.OP_DWCONV, "conv")
+    return y
+
+
+def dwpw_pair(x, wda, bda, wa, ba, wdb, bdb, wb, bb, *, slope=0.05, in_coff=0, out=None, out_coff=0, out_channels=None, store=None):
+    """esr_dwpw_pair_s16: the refinement path of team 35's RFDB (team35_rfdn/rmsrb1.py:22-27, :199-210) in ONE launch on a 16-bit NHWC tensor
+    x [N, H, W, P] (C channels from in_coff): u1 = dw3(x, wda, bda) + x, h = relu(wa . u1 + ba), u2 = dw3(h, wdb, bdb) + h,
+    out = lrelu(wb . u2 + bb + x), each of u1, h, u2 and out rounded once to the storage type, x and h zero-padded.  wda / wdb [C, 1, 3, 3],
+    wa / wb [C, C(, 1, 1)]; 33 <= C <= 64.
+    out: a caller-provided NHWC tensor of x's dtype and device, never x itself, that receives the result from channel out_coff; default:
+    freshly allocated zeros of pitch round_up(C, 8).  out_channels: the channels stored (default round_up(C, 8); those >= C are zeros).
+    store: "bf16" | "f16", if given it must be x's storage type."""
+    st = _s16_store(x, "dwpw_pair")
+    if store is not None and store != st:
+        raise L.EsrError(f"dwpw_pair: store {store!r}, x is stored as {st}")
+    lib = L.lib()
+    n, h, w, _ = x.shape
+    c = wda.shape[0]
+    d = L.ChainDesc()
+    d.n, d.h, d.w, d.n_layers = n, h, w, 4
+    d.cin = d.cmid = d.cout = c
+    d.act, d.slope, d.res_mode = L.ACT_LRELU, slope, L.RES_PRE_ACT
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x, in_coff)
+    if not lib.esr_packed_cx_pw1_bytes(c, c):
+        raise L.EsrError("dwpw_pair: no kernel for this shape (esr_dwpw_pair_supported)")
+    keep = [pack_dw(wda, bda).to(x.device), pack_dwpw_pw(wa, ba, st).to(x.device), pack_dw(wdb, bdb).to(x.device), pack_dwpw_pw(wb, bb, st).to(x.device)]
+    for i, k in enumerate(keep):
+        d.wpacked[i] = k.data_ptr()
+    d.post_cout = (c + 7) // 8 * 8 if out_channels is None else out_channels
+    y = _zeros_or(out, "dwpw_pair: out", x, (n, h, w), d.post_cout, 8)
+    d.post_out = _view(y, out_coff)
+    if not lib.esr_dwpw_pair_supported(ctypes.byref(d)):
+        raise L.EsrError("dwpw_pair: no kernel for this shape (esr_dwpw_pair_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_dwpw_pair_s16", "esr_dwpw_pair_s16", d, stream, L.OP_DWPW_PAIR, "chain")
+    return y
+
+
+def esa_unshuffle(c1, weight, bias, *, out=None):
+    """esr_esa_unshuffle_f32: c3 = relu(con_(relu(max_pool2d(pixel_unshuffle(c1, 2), 7, 3)))) (team35_rfdn/rmsrb1.py:140-144) in one launch.
+    c1: the conv1 map [N, H, W, 16] in fp32, bf16 or fp16 storage (f channels, the rest ignored), H, W >= 14; weight [f, 4 f, 1, 1] and bias
+    of con_ = nn.Conv2d(4 f, f, 1, padding 1).  Returns the fp32 map [N, h3 + 2, w3 + 2, 16], h3 = (H // 2 - 7) // 3 + 1: the ring is
+    relu(bias), the pad channels f .. 15 are zeros.  out: a caller-provided contiguous fp32 tensor of that shape on c1's device."""
+    if not c1.is_cuda:
+        raise L.EsrError("esa_unshuffle: tensors must live on the GPU; there is no CPU fallback")
+    n, h, w, _ = c1.shape
+    f = weight.shape[0]
+    if h < 14 or w < 14:
+        raise L.EsrError("esa_unshuffle: H, W >= 14 (one 7x7 pooling window of the half-resolution map)")
+    d = L.EsaDesc()
+    d.n, d.h, d.w, d.f, d.storage = n, h, w, f, L.STORE[_STORE_OF[c1.dtype]]
+    d.h_lo, d.w_lo = (h // 2 - 7) // 3 + 3, (w // 2 - 7) // 3 + 3
+    d.x = _view(c1)
+    keep = pack_unshuffle(weight, bias).to(c1.device)
+    d.w0 = keep.data_ptr()
+    like = torch.empty(0, dtype=torch.float32, device=c1.device)
+    y = _zeros_or(out, "esa_unshuffle: out", like, (n, d.h_lo, d.w_lo), L.ESA_FP, 4)
+    d.y = _view(y)
+    _launch("esr_esa_unshuffle_f32", "esr_esa_unshuffle_f32", d, torch.cuda.current_stream(c1.device).cuda_stream, L.OP_ESA_UNSHUFFLE, "esa")
     return y
 
 

@@ -17,6 +17,7 @@ Rule 4 -- conv64m_kernel, rfdb_tail_kernel (esr_c64m.hip), rlfb_chain_kernel (es
     And for resblock_head_kernel (esr_esan.hip): the 42 weight fragments of its two 3x3s and its 1x1 likewise.
     And for refine_cascade_kernel (esr_cascade.hip): the 32 weight fragments of its three 3x3s and its 1x1 likewise.
     And for cx_block_kernel (esr_cx.hip): the 49 x 2 depthwise weights of a thread's channel pair likewise.
+    And for dwpw_pair_kernel (esr_dwpw.hip): the 16 weight fragments of its two 1x1s and the 2 x 9 x 2 depthwise weights of a thread's channel pair likewise.
 Rule 5 -- rlfb_chain_kernel: the post wave's counted wait (PIECES + STORES) (D - 2) + STORES is in the code, and between two barriers
     of the step loop there are exactly PIECES LDS-DMA loads and exactly STORES stores (ChGeo<G>): an extra vector-memory instruction would loosen it.
 Rule 2 -- conv_s16_kernel's wait-count arithmetic (tools/lint_s16_isa.py, unchanged): no scratch / spills, no copies out of registers an
@@ -119,7 +120,8 @@ def lint_prologues(path, unit):
         if (unit == "esr_c64m.hip" and ("conv64m_kernel" in name or "rfdb_tail_kernel" in name)) or (unit == "esr_chain.hip" and "rlfb_chain_kernel" in name) or \
                 (unit == "esr_hfab.hip" and "hfab_kernel" in name) or (unit == "esr_esa_pool7.hip" and "esa_pool7_" in name) or \
                 (unit == "esr_distill.hip" and "distill_step_kernel" in name) or (unit == "esr_esan.hip" and "resblock_head_kernel" in name) or \
-                (unit == "esr_cascade.hip" and "refine_cascade_kernel" in name) or (unit == "esr_cx.hip" and "cx_block_kernel" in name):
+                (unit == "esr_cascade.hip" and "refine_cascade_kernel" in name) or (unit == "esr_cx.hip" and "cx_block_kernel" in name) or \
+                (unit == "esr_dwpw.hip" and "dwpw_pair_kernel" in name):
             bad = [t for t in ins if t.startswith(("scratch_", "s_set_gpr_idx", "s_movrel", "v_movrel"))]
             if bad:
                 problems.append(f"{unit}: {name}: {len(bad)} scratch / dynamic register index instruction(s), first: {bad[0]}")
