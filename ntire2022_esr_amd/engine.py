@@ -1640,6 +1640,12 @@ class _StreamCtx:
         self.profs = {}
 
 
+def _mark_dirty_hook(module, incompatible):
+    """HipSRModel's load_state_dict post hook.  A module-level function: the hook table is part of what copy.deepcopy / pickle carry, and
+    the hook marks the module it is called on -- a copy's load re-packs the copy, not its source."""
+    module._mark_dirty()
+
+
 class HipSRModel(nn.Module):
     """Base of the drop-in nn.Modules.  Subclasses register reference-compatible parameters
     with `_add_conv` and describe their forward with `_build_plan`."""
@@ -1670,7 +1676,22 @@ class HipSRModel(nn.Module):
         self._prof_passes = 0      # >0: record HIP events around every op (bench roofline leg)
         self.handle = next(_HANDLES)       # the `handle` argument of esr::sr_forward
         _LIVE[self.handle] = self
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
+        self.register_load_state_dict_post_hook(_mark_dirty_hook)
+
+    # -- copies: copy.copy / copy.deepcopy / pickle (torch.save(model)) all go through these two -----------------
+    def __getstate__(self):
+        """What a copy carries: parameters, specs, compute mode and flags.  Not the runtime state derived from them -- the packed blobs,
+        the per-stream workspaces, plans, esr_op arrays (raw device pointers), HIP graphs and event sets stay with the source, and the
+        `handle` names the source alone."""
+        state = self.__dict__.copy()
+        state.update(_packed=None, _packed_sig=None, _dirty=True, _ctxs={})
+        del state["handle"]
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.handle = next(_HANDLES)
+        _LIVE[self.handle] = self
 
     # -- parameter registration: same key names as the reference state_dict -------------------
     def _add_leaf(self, path, leaf):
@@ -1901,8 +1922,10 @@ class HipSRModel(nn.Module):
         raise NotImplementedError
 
     def _ensure_packed(self, device):
-        """Weights are re-packed after load_state_dict / .to() / set_compute (dirty flag) or when the blobs live on
-        another device.  In-place edits of a parameter's storage are not tracked: call repack() after them."""
+        """Weights are re-packed after load_state_dict ON THE MODEL / .to() / set_compute / a plan-shaping flag (dirty flag) or when
+        the blobs live on another device.  Not tracked: a load_state_dict on a sub-module (`model.B1.load_state_dict(...)`: the post
+        hook is the model's own, a container's load never reaches it) and in-place edits of a parameter's storage (`p.copy_()` under
+        no_grad, an optimizer step) -- the next forward still runs the old blobs.  Call repack(device) after them."""
         if self._packed is None or self._dirty or next(iter(self._packed.values())).device != device:
             self.repack(device)
 
@@ -1968,10 +1991,7 @@ class HipSRModel(nn.Module):
             # fifth of a graph-launched forward's host time).  torch.jit.trace, make_fx, any active TorchDispatchMode (FlopCounterMode,
             # profiler modes), FakeTensor and torch.compile go through esr::sr_forward below: they must SEE the operator
             return self._forward_impl(x)
-        if _LIVE.get(self.handle) is not self:          # a copy.deepcopy of a module carries its source's handle: take a fresh one
-            self.handle = next(_HANDLES)
-            _LIVE[self.handle] = self
-        return torch.ops.esr.sr_forward(x, self.handle)
+        return torch.ops.esr.sr_forward(x, self.handle)         # (a copy has a handle of its own: __setstate__)
 
     def _forward_impl(self, x):
         if not x.is_cuda:
