@@ -19,7 +19,8 @@ from conftest import GOLD
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ST = {"f32": (0, torch.float32), "bf16": (1, torch.bfloat16), "f16": (2, torch.float16)}
-# PSNR against the reference's (the fixture checkpoint is bf16-representable, tools/gen_golden_efdn.py), dB
+# PSNR against the reference's, dB.  The fixture checkpoint is the reference's ROUNDED TO BF16 (tools/gen_golden_efdn.py), so nothing here sees a
+# weight the storage types cannot hold; tests/test_gpu_true_weights.py holds the same budgets with the unrounded checkpoint
 BUDGET = {"f32": 0.002, "bf16": 0.01, "f16": 0.005}
 # max |y - y_ref| / data_range on the big goldens' ::9 sample, measured on the MI355X, with headroom
 MAX_REL = {"f32": 2e-5, "bf16": 1.5e-2, "f16": 2.5e-3}

@@ -22,7 +22,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 DT = {"bf16": torch.bfloat16, "f16": torch.float16}
 EPS = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11}
-# PSNR against the reference's (the fixture checkpoint is bf16-representable, tools/gen_golden_esan.py), dB: the project's budgets
+# PSNR against the reference's, dB: the project's budgets.  The fixture checkpoint is the reference's ROUNDED TO BF16 (tools/gen_golden_esan.py), so
+# nothing here sees a weight the storage types cannot hold; tests/test_gpu_true_weights.py holds the same budgets with the unrounded checkpoint
 BUDGET = {"f32": 0.002, "bf16": 0.01, "f16": 0.005}
 # max |y - y_ref| / data_range on the big goldens' ::9 sample.  f32: the project's bound.  bf16 / f16: twice the largest value measured on the
 # MI355X over both sizes and both forms of the head (bf16 9.76e-3 at 256 x 256, f16 1.19e-3 at 339 x 510, the two forms
