@@ -268,6 +268,10 @@ int esr_conv_block_waves(const esr_conv_desc* d);
  *   esr_maxpool7s3_f32  F.max_pool2d(kernel_size=7, stride=3)             H3 = (H2-7)/3+1 (block.py:120)
  *   esr_esa_apply_f32   y = x * sigmoid(conv4(bilinear(c3 -> HxW, align_corners=False) + conv_f(c1_)))
  *                       (block.py:124-129): one full-resolution pass, x read once, y written once.
+ *                       Needs w >= 8 in every storage type: both kernels derive (n, oy, ox) of 16 consecutive pixels from the first
+ *                       one and carry the column over at most two image rows, which is enough only from w = 8 on.  w < 8 returns
+ *                       ESR_ERR_UNSUPPORTED before anything is launched (a narrower image would be interpolated from wrong source
+ *                       coordinates, read past c3's rows included).
  */
 #define ESR_ESA_FP 16
 

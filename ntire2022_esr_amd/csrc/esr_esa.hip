@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void esa_apply_kernel(const EsaK p)
     int ox = (int)(pix0 - row0 * (unsigned)p.W) + pl;
     int oy = (int)(row0 - n0 * (unsigned)p.H);
     int n = (int)n0;
-    for (int wrap = 0; wrap < 2; ++wrap)
+    for (int wrap = 0; wrap < 2; ++wrap)                                        // W >= 8 (esr_esa_apply_f32 refuses less): two wraps are enough
         if (ox >= p.W) {
             ox -= p.W;
             if (++oy == p.H) { oy = 0; ++n; }
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256, ESA_APPLY_WAVES) void esa_apply_mfma_kernel(co
         int ox = (int)(pix0 - row0 * (unsigned)p.W) + px;
         int oy = (int)(row0 - n0 * (unsigned)p.H);
         int n = (int)n0;
-        if (ox >= p.W) {                                                 // W >= 15 here: at most two wraps
+        if (ox >= p.W) {                                                 // W >= 8 (esr_esa_apply_f32 refuses less): (W - 1) + 15 < 3 W, at most two wraps
             ox -= p.W;
             if (++oy == p.H) { oy = 0; ++n; }
         }
@@ -886,6 +886,10 @@ int esr_esa_apply_f32(const esr_esa_desc* d, void* hip_stream)
     if (!d || !d->x.ptr || !d->y.ptr || !d->c1 || !d->c3 || !d->w0 || !d->w1) return ESR_ERR_BAD_ARG;
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->c > 64 || d->f <= 0 || d->f > FP) return ESR_ERR_BAD_ARG;
     if (d->h_lo <= 0 || d->w_lo <= 0) return ESR_ERR_TOO_SMALL;
+    // Both kernels take (n, oy, ox) of a 16-pixel group from its first pixel and carry the column over AT MOST TWO image rows: the last lane's
+    // column is at most (W - 1) + 15, which two subtractions of W bring below W only for W >= 8.  A narrower image would get wrong bilinear
+    // source coordinates (and c3 indices past its rows), so it is refused here, in every storage type, before anything is launched.
+    if (d->w < 8) return ESR_ERR_UNSUPPORTED;
     const int cp4 = esr_round_up(d->c, 4);
     if (!esr_view_fits(d->x, 4, cp4) || !esr_view_fits(d->y, 4, cp4)) return ESR_ERR_BAD_ARG;
     if (d->storage != ESR_STORE_F32) {

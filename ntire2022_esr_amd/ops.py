@@ -758,11 +758,15 @@ def channel_attention(x, w1, b1, w2, b2, *, contrast=False, nchw=False, out=None
     return y
 
 
-def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False, post_out=None):
+def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False, post_out=None, x_coff=0, out_coff=0):
     """ESA's full-resolution tail in one launch (esr_esa_apply_f32): y = x * sigmoid(conv4(bilinear(c3 -> HxW) + conv_f(c1)))
     (models/rfdn_baseline/block.py:124-129).  x: NHWC [N,H,W,pitch] (fp32 / bf16 / fp16 storage), c channels = w4.shape[0];
     c1: NHWC [N,H,W,16] of the same dtype (conv1's output, f = wf.shape[0] <= 16 channels, pads zero); c3: fp32 NHWC [N,h_lo,w_lo,16];
     wf [f,f(,1,1)], w4 [c,f(,1,1)].
+    W >= 8: the kernels carry a 16-pixel group's column over at most two image rows; a narrower image raises EsrError (esr_esa_apply_f32
+    returns ESR_ERR_UNSUPPORTED) before anything is launched, in every storage type.
+    x_coff / out_coff: x is read from channel x_coff of its pitch, y written from channel out_coff of `out`'s (multiples of 4 for fp32, 8 for
+    16-bit storage); nothing outside [out_coff, out_coff + round_up(c, granule)) of a pixel is written.
     post (16-bit storage): one or two dicts(weight [cout, cin(,1,1)], bias, act, slope, res) -- 1x1 convolutions evaluated in the same
     launch (esr_esa_desc.post[]): the first on y as stored (+ res, NHWC of x's dtype), the second on the first's fp32 result.  Returns
     (y, [out0(, out1)]) then; skip_y: y is not stored.
@@ -779,7 +783,7 @@ def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False, p
     d = L.EsaDesc()
     d.n, d.h, d.w, d.c, d.f, d.h_lo, d.w_lo = n, h, w, c, f, c3.shape[1], c3.shape[2]
     d.storage = L.STORE[_STORE_OF[x.dtype]]
-    d.x, d.y = _view(x), _view(y)
+    d.x, d.y = _view(x, x_coff), _view(y, out_coff)
     d.c1, d.c3, d.w0, d.w1 = c1.data_ptr(), c3.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr()
     outs = []
     if post_out is not None and (not post or len(post_out) != len(post)):

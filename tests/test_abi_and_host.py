@@ -107,6 +107,37 @@ def test_descriptor_validation_without_gpu():
         assert lib.esr_conv2d_f32(ctypes.byref(d), None) == -3
 
 
+@pytest.mark.parametrize("storage", ["f32", "bf16", "f16"])
+def test_esa_apply_refuses_narrow_images_without_gpu(storage):
+    """esr_esa_apply_f32 needs W >= 8 (both kernels carry a 16-pixel group's column over at most two rows): W < 8 is ESR_ERR_UNSUPPORTED in
+    every storage type, with the other argument checks and before anything is launched -- on a CPU-only host as on a GPU box."""
+    from ntire2022_esr_amd import _lib as L
+    lib = L.lib()
+    buf = (ctypes.c_float * 64)()
+    a = ctypes.addressof(buf)
+
+    def desc(w, **kw):
+        d = L.EsaDesc()
+        d.n, d.h, d.w, d.c, d.f, d.h_lo, d.w_lo = 2, 19, w, 50, 12, 3, 1
+        d.storage = L.STORE[storage]
+        d.x, d.y = L.View(a, 56, 0), L.View(a, 56, 0)
+        d.c1 = d.c3 = d.w0 = d.w1 = a
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return lib.esr_esa_apply_f32(ctypes.byref(d), None)
+
+    for w in (1, 5, 7):
+        assert desc(w) == -2, w
+        assert desc(w, skip_y=1) == -2, w                # ahead of the checks behind it
+    assert desc(0) == -1 and desc(-3) == -1              # no width at all stays a bad argument
+    # w = 8 passes the width check: the descriptor goes on to a LATER check (skip_y without a post chain: ESR_ERR_BAD_ARG), which stops it
+    # in front of the launch on any host
+    assert desc(8, skip_y=1) == -1 and desc(9, skip_y=1) == -1
+    if torch.cuda.device_count() == 0:
+        # and the valid descriptor reaches the launch, which fails for want of a device (as test_descriptor_validation_without_gpu)
+        assert desc(8) == -3
+
+
 def test_hilo_descriptor_validation_without_gpu():
     """esr_conv_desc.hilo (ABI v10) is validated before anything is launched: unknown bits, a missing stride, fp16 storage, a 1x1, two output
     tiles, a segmented input and a post chain next to the input / residual flags are refused on a CPU-only host as on a GPU box."""

@@ -63,38 +63,19 @@ def test_conv3x3s2_and_maxpool(f, hw):
     assert lib.esr_conv3x3s2_f32(ctypes.byref(d), st) == -1          # inconsistent low-res dims rejected
 
 
-@pytest.mark.parametrize("c,f,hw,lo", [(50, 12, (40, 56), (5, 8)), (46, 16, (33, 17), (4, 1)), (48, 12, (64, 64), (9, 9)),
-                                       (50, 12, (20, 36), (1, 4))])
-def test_esa_apply(c, f, hw, lo):
-    """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1_)))  (rfdn_baseline/block.py:124-129)."""
-    from ntire2022_esr_amd import _lib as L
-    from ntire2022_esr_amd.engine import pack_dense
-    lib = L.lib()
-    g = torch.Generator().manual_seed(c + f + hw[0])
-    x = torch.randn(2, c, *hw, generator=g) * 30
-    c1 = torch.randn(2, f, *hw, generator=g)
-    c3 = torch.randn(2, f, *lo, generator=g)
-    wf, bf = torch.randn(f, f, 1, 1, generator=g) * 0.3, torch.randn(f, generator=g)
-    w4, b4 = torch.randn(c, f, 1, 1, generator=g) * 0.3, torch.randn(c, generator=g)
-    ref = x * torch.sigmoid(F.conv2d(F.interpolate(c3, hw, mode="bilinear", align_corners=False) + F.conv2d(c1, wf, bf), w4, b4))
-    pitch = (c + 7) // 8 * 8
-    xg = torch.zeros(2, *hw, pitch)
-    xg[..., :c] = x.permute(0, 2, 3, 1)
-    xg = xg.to(DEV)
-    y = torch.full((2, hw[0], hw[1], pitch + 8), 5.0, device=DEV)      # write into a slice of a wider buffer
-    cp4 = (c + 3) // 4 * 4
-    d = L.EsaDesc()
-    d.n, d.h, d.w, d.c, d.f, d.h_lo, d.w_lo = 2, hw[0], hw[1], c, f, lo[0], lo[1]
-    d.x = L.View(ctypes.c_void_p(xg.data_ptr()), pitch, 0)
-    d.y = L.View(ctypes.c_void_p(y.data_ptr()), pitch + 8, 8)
-    c1g, c3g = _nhwc16(c1), _nhwc16(c3)
-    pf, p4 = pack_dense(wf, bf, 16, 16).to(DEV), pack_dense(w4, b4, 16, cp4).to(DEV)
-    d.c1, d.c3, d.w0, d.w1 = c1g.data_ptr(), c3g.data_ptr(), pf.data_ptr(), p4.data_ptr()
-    L.check(lib.esr_esa_apply_f32(ctypes.byref(d), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "apply")
-    yc = y.cpu()
-    got = yc[..., 8:8 + c].permute(0, 3, 1, 2)
-    assert float((got - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
-    assert torch.all(yc[..., :8] == 5.0) and torch.all(yc[..., 8 + cp4:] == 5.0)
+# (test_esa_apply, the fp32 cases of the apply against ATen, lives in tests/test_gpu_esa_apply.py with the op's other value tests)
+
+
+def _post_ends():
+    """the ends of what esr_esa_apply_post_supported accepts: c = 33 and 64 (two channel pairs of tiles), one post of 1 / 32 outputs (one
+    pair), 33 / 64 outputs (two pairs) alone or with a second post of 1 / 32; storage, activations, residual and skip_y alternate"""
+    out, k = [], 0
+    for c in (33, 64):
+        for c0, c1 in [(1, 0), (32, 0)] + [(a, b) for a in (33, 64) for b in (0, 1, 32)]:
+            for store in ("bf16", "f16"):
+                out.append((store, c, c0, c1, ("lrelu", "none", "gelu")[k % 3], ("gelu", "lrelu")[k % 2] if c1 else None, k % 4 < 2, k % 3 == 1))
+                k += 1
+    return out
 
 
 @pytest.mark.parametrize("store,c,c0,c1,act0,act1,res,skip", [
@@ -102,12 +83,14 @@ def test_esa_apply(c, f, hw, lo):
     ("f16", 48, 48, 24, "none", "gelu", True, True),            # BSRN: conv_out + block input, then the next block's c1_d; y not stored
     ("bf16", 48, 48, 24, "none", "gelu", True, True),
     ("f16", 48, 48, 0, "none", None, True, True),               # BSRN's last block
-])
+] + _post_ends())
 def test_esa_apply_post_chain(store, c, c0, c1, act0, act1, res, skip):
     """esr_esa_desc.post[]: 1x1 convolutions riding in the ESA apply launch, against ATen on the values the launch stores
     (post 0 reads y as stored; post 1 reads post 0's fp32 result)."""
     from ntire2022_esr_amd import _lib as L
     from ntire2022_esr_amd import ops
+    import _esa_apply_ref as R
+    assert L.lib().esr_esa_apply_post_supported(c, c0, c1) == 1
     dt = torch.bfloat16 if store == "bf16" else torch.float16
     f, hw, lo = 12, (37, 45), (5, 7)
     g = torch.Generator().manual_seed(c + c0 + c1)
@@ -133,8 +116,11 @@ def test_esa_apply_post_chain(store, c, c0, c1, act0, act1, res, skip):
         post.append(dict(weight=w1, bias=b1, act=acts[act1], slope=0.05))
     ysent = torch.full((2, hw[0], hw[1], pitch), 7.0, dtype=dt, device=DEV)
     y, outs = ops.esa_apply(xg, c1g, c3g, wf, bf, w4, b4, out=ysent, post=post, skip_y=skip)
-    # reference on the rounded inputs; y as the kernel stores it = the plain launch's result (tested above), bit for bit
+    # y as the kernel stores it = the plain launch's result, bit for bit; and that result is held to the fp64 restatement of the op on the
+    # rounded inputs through the comparator of tests/_esa_apply_ref.py (as tests/test_gpu_esa_apply.py does for the plain launch's own matrix)
     yplain = ops.esa_apply(xg, c1g, c3g, wf, bf, w4, b4)
+    r = R.ref64(xg.cpu()[..., :c], c1g.cpu()[..., :f], c3.permute(0, 2, 3, 1), wf, bf, w4, b4, storage=store)
+    R.compare(yplain.cpu()[..., :c], r, f"esa apply {store} c={c} in front of posts ({c0}, {c1})")
     if skip:
         assert torch.all(y == 7.0)
     else:
