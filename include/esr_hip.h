@@ -426,7 +426,9 @@ typedef enum esr_op_kind {
     ESR_OP_DWCONV7 = 13,        /* esr_dwconv7x7 on esr_op.conv (additive within ABI v12) */
     ESR_OP_CX_BLOCK = 14,       /* esr_cx_block_s16 on esr_op.chain (additive within ABI v12) */
     ESR_OP_DWPW_PAIR = 15,      /* esr_dwpw_pair_s16 on esr_op.chain (additive within ABI v12) */
-    ESR_OP_ESA_UNSHUFFLE = 16   /* esr_esa_unshuffle_f32 on esr_op.esa (additive within ABI v12) */
+    ESR_OP_ESA_UNSHUFFLE = 16,  /* esr_esa_unshuffle_f32 on esr_op.esa (additive within ABI v12) */
+    ESR_OP_PA_GATE = 17,        /* esr_pa_gate on esr_op.conv (additive within ABI v12) */
+    ESR_OP_PA_TAIL = 18         /* esr_pa_tail on esr_op.conv (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -701,10 +703,61 @@ int    esr_dwpw_pair_s16(const esr_chain_desc* d, void* hip_stream);
  */
 int esr_esa_unshuffle_f32(const esr_esa_desc* d, void* hip_stream);
 
+/*
+ * esr_pa_gate (additive within ABI v12; op kind ESR_OP_PA_GATE on esr_op.conv) -- pixel attention and the long skip behind it, the end of
+ * RePAFDN's forward (models/team10_repafdn/block.py:151-166, repafdn.py:56-57), as one streaming launch in fp32, bf16 or fp16 storage
+ * (pa_gate_kernel, csrc/esr_pa.hip):
+ *     y = t (.) sigmoid(W . t + b) + s          W: 1x1, C -> C, gating its own input
+ * The 1x1 runs on the matrix cores with fp32 accumulation from the bias (16-bit storage: the stored t is the operand as it is, the weights
+ * a hi + lo pair of 16-bit images, w = hi + lo); the product t g and the sum with s are fp32 operations of their own; one rounding at the
+ * store.  An esr_conv_desc carries it, no field added:
+ *     cin                  C, 33 .. 64; channels of t and s at and beyond C are never used, whatever they hold
+ *     cout                 the channels stored: a multiple of the granule (4 fp32 / 8 16-bit) in C .. round_up(C, 16); those >= C as zeros
+ *     ksize, layouts       1, ESR_NHWC both;  act ESR_ACT_NONE
+ *     in                   t: round_up(C, granule) channels from coff
+ *     res, res_mode        s, ESR_RES_POST_ACT; ESR_RES_NONE: no s
+ *     out0                 y
+ *     storage, compute     ESR_STORE_F32 / ESR_COMPUTE_F32, BF16 / BF16 or F16 / F16
+ *     hilo, hilo_stride    16-bit storage: ESR_HILO_RES -- s is a hi + lo pair (s = fl(hi + lo) in fp32), ESR_HILO_OUT -- y becomes one
+ *                          (hi = rnd(v), lo = rnd(v - hi), as esr_conv2d_f32 splits); the low parts lie hilo_stride bytes behind the views
+ *     wpacked              esr_pack_pa_gate(W [C][C], b, C, storage)
+ * Every other feature field (split, tail_*, post_*, border_bias, blocked8, in_seg_stride, wino_wpacked, ESR_HILO_IN) must be zero.
+ * y is another tensor than t and s: the n h w pitch elements behind out0.ptr (and behind its low parts) may share no byte with those behind
+ * in.ptr, res.ptr and s's low parts -- ESR_ERR_BAD_ARG otherwise (a slice of t's own tensor included), as for a null pointer or a view that
+ * is misaligned or does not hold its channels.  esr_pa_gate_supported: 1 for such a descriptor; esr_pa_gate returns ESR_ERR_UNSUPPORTED for
+ * every other (C outside 33 .. 64 included).
+ * esr_pack_pa_gate: 16-bit storage -- [hi image | lo image | 64 fp32 biases], an image = [cout tile 4][K step 2][lane 64][8] 16-bit values,
+ * lane (row, kq) element e of (mt, ks) = W[16 mt + row][16 (2 ks + e / 4) + 4 kq + e % 4]; fp32 -- [cout tile 4][K step 16][lane 64] floats,
+ * lane (row, kq) of step 4 j + i = W[16 mt + row][16 j + 4 kq + i], then the biases.  Rows, columns and biases beyond C are zero.
+ */
+size_t esr_packed_pa_gate_bytes(int c, int storage);
+int    esr_pack_pa_gate(const float* w_oi, const float* bias, int c, int storage, void* out, size_t out_bytes);
+int    esr_pa_gate_supported(const esr_conv_desc* d);
+int    esr_pa_gate(const esr_conv_desc* d, void* hip_stream);
+/*
+ * esr_pa_tail (additive within ABI v12; op kind ESR_OP_PA_TAIL on esr_op.conv) -- the 3x3 in front of the pixel attention, the gate and the
+ * skip as ONE launch on 16-bit storage (pa_tail_kernel, csrc/esr_pa.hip): RePAFDN's LR_conv -> pa -> + out_fea (repafdn.py:55-57),
+ *     t = W3 (*) in + b3                        3x3, C -> C, zero padding; t stays in the fp32 accumulators and is never stored
+ *     y = t (.) sigmoid(W . rnd(t) + b) + s     the gate's matrix operand is t rounded once to the storage type; the fp32 t meets the product
+ * on a 16 x 16 output tile staged with a one-pixel halo, persistent over the tiles.  The descriptor is esr_pa_gate's with
+ *     ksize                3;  storage / compute BF16 / BF16 or F16 / F16 only
+ *     in                   the 3x3's input: round_up(C, 8) channels from coff; y is another tensor than `in` (neighbouring tiles read its halo)
+ *     wpacked              esr_pack_conv_s16(W3, b3, cin = cout = C, ksize 3, cin_phys = round_up(C, 16)): the weights conv_s16_kernel multiplies by
+ *     tail_wpacked         esr_pack_pa_gate(W, b, C, storage)                 (tail_cat / tail_cat_c stay zero)
+ * and cin, cout, res, res_mode, out0, hilo, hilo_stride as there.  Against esr_conv2d_f32 + esr_pa_gate the only difference in value is that
+ * t meets the product unrounded (the two launches store it once in between).  With g the gate, the two sums differ by at most half a
+ * storage step of t times g before the last rounding: without s that is at most ONE storage step of y; with s it is half a step of t times
+ * g plus one rounding of each result, which is many of y's own steps wherever t g and s cancel to something much smaller than t.  esr_pa_tail_supported: 1 for
+ * such a descriptor with a per-image input below 1 GiB; esr_pa_tail returns ESR_ERR_UNSUPPORTED for every other (fp32 storage included) and
+ * ESR_ERR_BAD_ARG as esr_pa_gate does.
+ */
+int    esr_pa_tail_supported(const esr_conv_desc* d);
+int    esr_pa_tail(const esr_conv_desc* d, void* hip_stream);
+
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
-    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD */
+    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL */
     esr_esa_desc esa;           /* the four ESA kinds, ESR_OP_ESA_UNSHUFFLE */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */

@@ -293,6 +293,38 @@ def dwpw_pw_effective(blob, c, compute):
     return w[:c, :c].clone(), b[:c].clone()
 
 
+def pack_pa_gate(weight, bias, store):
+    """The C -> C 1x1 of a pixel attention for esr_pa_gate: w [C, C(, 1, 1)] -> the esr_pack_pa_gate blob of storage `store` ("f32": fp32 MFMA
+    A fragments; "bf16" / "f16": a hi + lo pair of 16-bit images, w = hi + lo), its K axis in the order in which pa_gate_kernel holds a pixel's
+    channels; the bias stays fp32."""
+    lib = L.lib()
+    a = _pack_args(weight, bias, flat=True)
+    cout, cin = a.w.shape
+    nbytes = lib.esr_packed_pa_gate_bytes(cin, L.STORE[store]) if cin == cout else 0
+    if not nbytes:
+        raise L.EsrError("pack_pa_gate: a square 1x1 of at most 64 channels")
+    out = torch.empty(nbytes // 4, dtype=torch.float32)
+    L.check(lib.esr_pack_pa_gate(_ptr(a.w), _ptr(a.b), cin, L.STORE[store], _ptr(out), nbytes), "esr_pack_pa_gate")
+    return out
+
+
+def pa_gate_effective(blob, c, store):
+    """EFFECTIVE weights [C, C] (what pa_gate_kernel multiplies by: hi + lo in 16-bit storage) and bias [C] of a pack_pa_gate blob, as float64
+    tensors (tests)."""
+    raw = blob.detach().to("cpu").contiguous().view(torch.uint8)
+    if store == "f32":
+        nimg = 4 * 16 * 64 * 4
+        w = raw[:nimg].view(torch.float32).to(torch.float64).reshape(4, 4, 4, 4, 16).permute(0, 4, 1, 3, 2).reshape(64, 64)   # (mt, j, i, kq, row)
+    else:
+        dt = torch.bfloat16 if store == "bf16" else torch.float16
+        half = 4 * 2 * 64 * 16
+        nimg = 2 * half
+        img = raw[:nimg].view(dt).to(torch.float64).reshape(2, 4, 2, 4, 16, 2, 4)                # (hi | lo, mt, ks, kq, row, e / 4, e % 4)
+        w = (img[0] + img[1]).permute(0, 3, 1, 4, 2, 5).reshape(64, 64)
+    b = raw[nimg:nimg + 256].view(torch.float32).to(torch.float64)
+    return w[:c, :c].clone(), b[:c].clone()
+
+
 def pack_unshuffle(weight, bias):
     """`con_` of team 35's ESA, nn.Conv2d(4 f, f, 1, padding 1), for esr_esa_unshuffle_f32: the esr_pack_dense_f32 blob [4 f][16] + bias[16]
     (the pad outputs f .. 15: zero columns, zero bias)."""
@@ -431,6 +463,7 @@ DWPAD = "#pad16"   # pack_dw image of a depthwise 3x3 of fewer than 16 channels,
 CX1 = "#cx1"       # esr_pack_cx_pw1_s16 image of a ConvNeXt block's first 1x1 (CxBlock; pack_cx_pw)
 CX2 = "#cx2"       # esr_pack_cx_pw2_s16 image of its second 1x1
 DWPW = "#dwpw"     # pack_dwpw_pw image of a 1x1 of team 35's refinement path (DwPwPair)
+PAG = "#pag"       # pack_pa_gate image of a pixel attention's 1x1 in the plan's storage (PaGate)
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -1297,6 +1330,90 @@ class Unshuffle(_Op):
 
 
 @dataclass
+class PaGate(_Op):
+    """Pixel attention and the skip behind it in one launch (esr_pa_gate) -- see Plan.pa_gate.  The blob `w + PAG` is pack_pa_gate's."""
+    w: str
+    src: object
+    dst: object                # a Plan.pair() where hilo has L.HILO_OUT
+    c: int
+    s: object = None           # the tensor added behind the gate (a Plan.pair() where hilo has L.HILO_RES), or None
+    hilo: int = 0
+    kind = "pagate"
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        op.kind = L.OP_PA_GATE
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        s, dst = self.s, self.dst
+        if self.hilo:
+            pairs = [v for bit, v in ((L.HILO_RES, s), (L.HILO_OUT, dst)) if self.hilo & bit]
+            assert not self.hilo & L.HILO_IN and all(isinstance(v, Planar) and len(v.segs) == 2 for v in pairs), "hilo: Plan.pair() buffers"
+            strides = {v.stride for v in pairs}
+            assert len(strides) == 1, "hilo: pairs of one shape"
+            d.hilo_stride = strides.pop()
+            s, dst = (v.seg(0) if self.hilo & bit else v for bit, v in ((L.HILO_RES, s), (L.HILO_OUT, dst)))
+        d.cin, d.ksize = self.c, 1
+        d.cout = _stored_width(dst, self.c) if st else (self.c + 3) // 4 * 4
+        d.in_layout = d.out_layout = L.NHWC
+        d.inp, d.out0 = _view(self.src, base), _view(dst, base)
+        if s is not None:
+            d.res, d.res_mode = _view(s, base), L.RES_POST_ACT
+        d.hilo = self.hilo
+        d.storage = d.compute = st
+        d.wpacked = ctypes.c_void_p(weights[self.w + PAG].data_ptr())
+
+    def cost(self, plan, desc):             # t (and s) read once, y written once
+        npix, es, c = plan.npix, plan.esize, self.c
+        ns = 0 if self.s is None else (2 if self.hilo & L.HILO_RES else 1)
+        ny = 2 if self.hilo & L.HILO_OUT else 1
+        wb = 4.0 * (c * c + c)
+        half = lambda v: v.seg(0) if isinstance(v, Planar) else v
+        stored = float(npix * es * (_stored_channels(self.src, c, 8) + (ns * _stored_channels(half(self.s), c, 8) if ns else 0)
+                                    + ny * _stored_channels(half(self.dst), c, 8))) + wb
+        return _cost(self.w, f"pa_gate_kernel<{L.STORE[plan.store]}>", c, c, 1, 2.0 * npix * c * c, float(npix * es * c * (1 + ns)) + wb,
+                     float(npix * es * c * ny), stored)
+
+    def counted_convs(self, plan):            # PA.conv = nn.Conv2d(c, c, 1); its sigmoid and the product have no hook in the reference's counters
+        return [(self.c, self.c, 1, plan.npix, L.ACT_NONE)]
+
+
+@dataclass
+class PaTail(_Fused):
+    """A 3x3 and the pixel attention behind it as ONE esr_pa_tail op -- see Plan.pa_tail (pa_tail_kernel).  replaces: [conv, pagate]."""
+    kind = "patail"
+    predicate, field, what = "esr_pa_tail_supported", "conv", "pixel-attention tail"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 2 and [o.kind for o in sub] == ["conv", "pagate"]
+        cv, gate = sub
+        assert cv.k == 3 and cv.cin == cv.cout == gate.c and cv.act == L.ACT_NONE and cv.res is None and cv.post is None and cv.tail is None
+        assert not cv.hilo and cv.hw is None and cv.dst1 is None and cv.border is None and not isinstance(cv.src, (str, Planar))
+        assert _same_view(gate.src, cv.dst)                                         # the gate reads what the 3x3 stores, and nothing else does
+        assert not any(_same_view(v, cv.src) for v in ((gate.dst.seg(0), gate.dst.seg(1)) if isinstance(gate.dst, Planar) else (gate.dst,)))
+
+    def encode(self, op, plan, base, weights):
+        cv, gate = self.replaces
+        gate.encode(op, plan, base, weights)                                        # t's view is replaced by the 3x3's input
+        op.kind = L.OP_PA_TAIL
+        d = op.conv
+        d.ksize = 3
+        d.inp = _view(cv.src, base)
+        d.wpacked = ctypes.c_void_p(weights[cv.w + S16].data_ptr())
+        d.tail_wpacked = ctypes.c_void_p(weights[gate.w + PAG].data_ptr())
+
+    def cost(self, plan, desc):             # x (and s) read once, y written once; t never exists
+        cv, gate = self.replaces
+        g = gate.cost(plan, None)
+        c = gate.c
+        wb = 4.0 * (9 * c * c + c)
+        stored = g["stored_bytes"] - plan.npix * plan.esize * _stored_channels(gate.src, c, 8) + plan.npix * plan.esize * _stored_channels(cv.src, c, 16) + wb
+        return _cost(cv.w, f"pa_tail_kernel<{_tf(plan.store == 'bf16')}, {(c + 15) // 16}>", c, c, 3, g["flops"] + 2.0 * plan.npix * 9 * c * c,
+                     g["read_bytes"] + wb, g["write_bytes"], stored)
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1469,6 +1586,17 @@ class Plan:
         self.ops[mark:] = [o]
         return True
 
+    def post_supported(self, o):
+        """Does the 16-bit post chain of the Conv `o` (not appended yet) run fused?  esr_conv_post_supported, asked as _fuse asks: about the
+        descriptor `o.encode` fills against a null workspace and stand-in weights, with n = 1 -- a batch and its single images take the
+        same kernels.  A network appends `o` as it is (plan.ops.append) or its convolutions one by one."""
+        assert self.esize == 2 and o.kind == "conv" and o.post is not None
+        try:
+            o.encode(L.Op(), Plan(1, self.h, self.w, self.store), (0, 0), _AnyBlob())
+        except L.EsrError:
+            return False
+        return True
+
     def chain(self, mark):
         """The 3x3 convolutions appended since `mark = len(plan.ops)` -- a residual block's chain src -> t1 -> ... -> (+ src) -> post 1x1 ->
         post2 1x1, RLFB's c1_r -> c2_r -> c3_r -> c5 -> esa.conv1 (team04_rlfn.py:109-122) -- as ONE esr_conv_chain_s16 op (16-bit plans):
@@ -1527,6 +1655,21 @@ class Plan:
         """c3 = relu(con_(relu(max_pool2d(pixel_unshuffle(c1, 2), 7, 3)))) (team35_rfdn/rmsrb1.py:140-144) in one launch, every storage
         (esr_esa_unshuffle_f32); `wname` names a pack_unshuffle blob; dst is the low-resolution fp32 map [n][h3 + 2][w3 + 2][16]."""
         self.ops.append(Unshuffle(wname, c1, dst, f))
+
+    def pa_gate(self, wname, src, dst, c, s=None, hilo=0):
+        """dst = src * sigmoid(W . src + b) (+ s): a pixel attention (team10_repafdn/block.py:151-166) and the tensor added behind it in one
+        launch, every storage (esr_pa_gate); `wname + PAG` names a pack_pa_gate blob of the plan's storage.  hilo (16-bit plans): L.HILO_RES --
+        s is a Plan.pair(), L.HILO_OUT -- dst is one.  dst is another tensor than src and s."""
+        self.ops.append(PaGate(wname, src, dst, c, s, hilo))
+
+    def pa_tail(self, mark):
+        """The two ops appended since `mark = len(plan.ops)` -- a plain 3x3 and the pixel attention that reads its result, t = conv(x),
+        y = t * sigmoid(W . t + b) (+ s) (team10_repafdn/repafdn.py:55-57) -- as ONE esr_pa_tail op (16-bit plans): x (and s) are read once, y
+        is written once, t stays in the accumulators.  The ops stay attached as `replaces`: weights, complexity counters and algorithmic
+        costs are theirs.  Not bit-identical to the two launches, which round t once in between: the sums differ by at most half a storage
+        step of t times the gate before the last rounding -- one step of y without s, more of y's own steps where t g and s cancel
+        (include/esr_hip.h: esr_pa_tail).  y must not be stored into x's tensor."""
+        return self._fuse(mark, PaTail)
 
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
@@ -1670,6 +1813,7 @@ class HipSRModel(nn.Module):
         self._fuse_head = True     # 16-bit ESAN plans: a residual block's head as one esr_resblock_head_s16 launch (Plan.resblock_head); measured: DESIGN.md 7e
         self._fuse_cascade = False # 16-bit FasterRFDN plans: FRFDB's refinement path as one esr_refine_cascade_s16 launch (Plan.refine_cascade); OFF: faster on one image, not at 32 x 256 x 256
         self._fuse_pair = True     # 16-bit DWRFDN plans: the depthwise-pointwise refinement path as one esr_dwpw_pair_s16 launch (Plan.dwpw_pair); measured: DESIGN.md 7h
+        self._fuse_pa_tail = False # 16-bit RePAFDN plans: LR_conv and the pixel attention behind it as one esr_pa_tail launch (Plan.pa_tail); OFF: 2 % slower than the two launches at 32 x 256 x 256 and on one image
         self._fuse_cx = True       # 16-bit RFDNeXt plans: the ConvNeXt block as one esr_cx_block_s16 launch (Plan.cx_block); measured: DESIGN.md 7g
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
@@ -1745,6 +1889,7 @@ class HipSRModel(nn.Module):
     fuse_head = property(lambda self: self._fuse_head, lambda self, v: self._set_flag("_fuse_head", v))
     fuse_cascade = property(lambda self: self._fuse_cascade, lambda self, v: self._set_flag("_fuse_cascade", v))
     fuse_cx = property(lambda self: self._fuse_cx, lambda self, v: self._set_flag("_fuse_cx", v))
+    fuse_pa_tail = property(lambda self: self._fuse_pa_tail, lambda self, v: self._set_flag("_fuse_pa_tail", v))
     fuse_pair = property(lambda self: self._fuse_pair, lambda self, v: self._set_flag("_fuse_pair", v))
 
     def _skip_hilo(self, plan, c):

@@ -7,8 +7,8 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .engine import (pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_post_s16, pack_unshuffle,
-                     pack_wino)
+from .engine import (pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_pa_gate, pack_post_s16,
+                     pack_unshuffle, pack_wino)
 
 
 def _view(t, coff=0):
@@ -541,6 +541,84 @@ def dwpw_pair(x, wda, bda, wa, ba, wdb, bdb, wb, bb, *, slope=0.05, in_coff=0, o
         raise L.EsrError("dwpw_pair: no kernel for this shape (esr_dwpw_pair_supported)")
     stream = torch.cuda.current_stream(x.device).cuda_stream
     _launch("esr_dwpw_pair_s16", "esr_dwpw_pair_s16", d, stream, L.OP_DWPW_PAIR, "chain")
+    return y
+
+
+def _pa(what, t, weight, bias, s, pair_out, in_coff, s_coff, out, out_coff, out_channels):
+    """the descriptor esr_pa_gate and esr_pa_tail share -> (desc, y, the blob to keep alive)"""
+    if not t.is_cuda:
+        raise L.EsrError(f"{what}: tensors must live on the GPU; there is no CPU fallback")
+    lib = L.lib()
+    st = _STORE_OF[t.dtype]
+    gran = 4 if st == "f32" else 8
+    n, h, w, _ = t.shape
+    c = weight.shape[0]
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin, d.ksize = n, h, w, c, 1
+    d.cout = (c + gran - 1) // gran * gran if out_channels is None else out_channels
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(t, in_coff)
+    strides = set()
+    if s is not None:
+        pair = s.dim() == 5
+        if s.device != t.device or s.dtype != t.dtype or not s.is_contiguous() or tuple(s.shape[:-1]) != ((2,) if pair else ()) + (n, h, w):
+            raise L.EsrError(f"{what}: s must be a contiguous [{'2, ' if pair else ''}{n}, {h}, {w}, pitch] tensor of t's dtype on t's device")
+        d.res, d.res_mode = _view(s, s_coff), L.RES_POST_ACT
+        if pair:
+            d.hilo |= L.HILO_RES
+            strides.add(s[1].data_ptr() - s[0].data_ptr())
+    if not lib.esr_packed_pa_gate_bytes(c, d.storage) or tuple(weight.shape[:2]) != (c, c):
+        raise L.EsrError(f"{what}: no kernel for this shape (a square 1x1 of 33 .. 64 channels)")
+    keep = pack_pa_gate(weight, bias, st).to(t.device)
+    y = _zeros_or(out, f"{what}: out", t, ((2,) if pair_out else ()) + (n, h, w), d.cout, gran)
+    d.out0 = _view(y, out_coff)
+    if pair_out:
+        d.hilo |= L.HILO_OUT
+        strides.add(y[1].data_ptr() - y[0].data_ptr())
+    if len(strides) > 1:
+        raise L.EsrError(f"{what}: a pair s and a pair result must have one pitch")
+    if strides:
+        d.hilo_stride = strides.pop()
+    return d, y, keep
+
+
+def pa_gate(t, weight, bias, *, s=None, pair_out=False, in_coff=0, s_coff=0, out=None, out_coff=0, out_channels=None):
+    """esr_pa_gate: y = t * sigmoid(weight . t + bias) (+ s) -- a pixel attention (team10_repafdn/block.py:151-166) and the tensor added behind
+    it -- in ONE launch on an NHWC tensor t [N, H, W, P] (C channels from in_coff) in fp32, bf16 or fp16 storage.  weight [C, C(, 1, 1)],
+    33 <= C <= 64; the product and the sum are fp32, one rounding at the store.
+    s: None, an NHWC tensor [N, H, W, Ps] of t's dtype (C channels from s_coff), or -- 16-bit storage -- a hi + lo pair [2, N, H, W, Ps]
+    (s = hi + lo in fp32).  pair_out (16-bit storage): y is returned as such a pair [2, N, H, W, Py], hi = rnd(v), lo = rnd(v - hi); with a
+    pair s as well the two must have one pitch (the C ABI has one stride for both).
+    out: a caller-provided tensor of t's dtype and device, never t or s, that receives the result from channel out_coff; default: freshly
+    allocated zeros of pitch round_up(C, granule).  out_channels: the channels stored (default round_up(C, granule), granule 4 fp32 / 8
+    16-bit; those >= C are zeros)."""
+    d, y, keep = _pa("pa_gate", t, weight, bias, s, pair_out, in_coff, s_coff, out, out_coff, out_channels)
+    d.wpacked = keep.data_ptr()
+    if not L.lib().esr_pa_gate_supported(ctypes.byref(d)):
+        raise L.EsrError("pa_gate: no kernel for this shape (esr_pa_gate_supported)")
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    _launch("esr_pa_gate", "esr_pa_gate", d, stream, L.OP_PA_GATE, "conv")
+    return y
+
+
+def pa_tail(x, w3, b3, weight, bias, *, s=None, pair_out=False, in_coff=0, s_coff=0, out=None, out_coff=0, out_channels=None):
+    """esr_pa_tail: t = conv3x3(x, w3, b3) (zero padding), y = t * sigmoid(weight . rnd(t) + bias) (+ s) in ONE launch on a 16-bit NHWC
+    tensor x [N, H, W, P] (C channels from in_coff): t stays in fp32 and is never stored, only the gate's matrix operand is t rounded to the
+    storage type.  w3 [C, C, 3, 3], weight [C, C(, 1, 1)], 33 <= C <= 64.  s, pair_out, out, out_coff, out_channels: as ops.pa_gate; out is
+    never x (neighbouring tiles read its halo) or s."""
+    _s16_store(x, "pa_tail")
+    d, y, keep = _pa("pa_tail", x, weight, bias, s, pair_out, in_coff, s_coff, out, out_coff, out_channels)
+    c = d.cin
+    if tuple(w3.shape) != (c, c, 3, 3):
+        raise L.EsrError(f"pa_tail: w3 must be [{c}, {c}, 3, 3]")
+    keep3 = pack_conv_s16(w3, b3, _STORE_OF[x.dtype], cin_phys=(c + 15) // 16 * 16).to(x.device)
+    d.ksize = 3
+    d.wpacked, d.tail_wpacked = keep3.data_ptr(), keep.data_ptr()
+    if not L.lib().esr_pa_tail_supported(ctypes.byref(d)):
+        raise L.EsrError("pa_tail: no kernel for this shape (esr_pa_tail_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_pa_tail", "esr_pa_tail", d, stream, L.OP_PA_TAIL, "conv")
     return y
 
 
