@@ -428,7 +428,8 @@ typedef enum esr_op_kind {
     ESR_OP_DWPW_PAIR = 15,      /* esr_dwpw_pair_s16 on esr_op.chain (additive within ABI v12) */
     ESR_OP_ESA_UNSHUFFLE = 16,  /* esr_esa_unshuffle_f32 on esr_op.esa (additive within ABI v12) */
     ESR_OP_PA_GATE = 17,        /* esr_pa_gate on esr_op.conv (additive within ABI v12) */
-    ESR_OP_PA_TAIL = 18         /* esr_pa_tail on esr_op.conv (additive within ABI v12) */
+    ESR_OP_PA_TAIL = 18,        /* esr_pa_tail on esr_op.conv (additive within ABI v12) */
+    ESR_OP_ASYM_STEP = 19       /* esr_asym_step on esr_op.conv (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -753,11 +754,51 @@ int    esr_pa_gate(const esr_conv_desc* d, void* hip_stream);
  */
 int    esr_pa_tail_supported(const esr_conv_desc* d);
 int    esr_pa_tail(const esr_conv_desc* d, void* hip_stream);
+/*
+ * esr_asym_step (additive within ABI v12; op kind ESR_OP_ASYM_STEP on esr_op.conv) -- one step of ARFDN's block (models/team14_arfdn/
+ * block.py:233-254), a distillation 1x1 and two asymmetric convolution pairs, as ONE launch on 16-bit storage (asym_step_kernel,
+ * csrc/esr_asym.hip), with act(v) = max(v, slope v):
+ *     d   = act(W_d . in + b_d)                    1x1, cin -> c; stored, rounded once
+ *     a_l = act(W_l1 (3x1) in + b_l1)              never stored; rounded once to the storage type, as a stored tensor would be, and 0 outside
+ *     a_m = act(W_m1 (1x3) in + b_m1)              the image (the second convolution's zero padding), not act(bias)
+ *     out = act(W_l2 (1x3) a_l + W_m2 (3x1) a_m + (b_l2 + b_m2) [+ in] + d + p1 + p2)          stored, rounded once
+ * All sums are fp32; d, p1 and p2 are added as stored.  A 16 x 16 output tile is staged once with a one-pixel halo, persistent over the
+ * tiles; the matrix cores' K dimension is 32 channels x three taps.  An esr_conv_desc carries it, no field added and no struct changed
+ * (esr_chain_desc has three views, the step needs five):
+ *     cin                  17 .. 64 (with `+ in`: == c); channels of `in` at and beyond cin are never used, whatever they hold
+ *     post_cout            c, 17 .. 32: the logical channels of d, a_l, a_m, out, p1 and p2
+ *     cout                 the channels of out stored, c .. round_up(c, 16); out and d are written up to round_up(.., 8), those >= c as zeros
+ *     ksize, layouts       3, ESR_NHWC both;  act, slope: ESR_ACT_NONE / LRELU / RELU;  post_act == act
+ *     in                   round_up(cin, 8) channels from coff
+ *     out0, post_out       out, d
+ *     res, tail_cat        p1, p2: round_up(c, 8) channels from coff each; a null ptr: absent.  res_mode ESR_RES_PRE_ACT: `+ in`, else ESR_RES_NONE
+ *     storage, compute     BF16 / BF16 or F16 / F16
+ *     wpacked              esr_pack_asym_s16(...);  post_wpacked  esr_pack_conv_s16(W_d, b_d, cin, c, ksize 1, cin_phys = round_up(cin, 16))
+ * Every other feature field (split, out1, tail_wpacked, tail_cat_c, tail_cout, tail_mid_act, tail_seg_stride16, post2_*, border_bias,
+ * blocked8, in_seg_*, wino_wpacked, hilo, hilo_stride) must be zero.  No byte that the kernel writes through out0 or post_out may belong to
+ * what it reads through in, res or tail_cat, or to the other output: two views of one pixel grid (equal pitch, pointers a whole number
+ * of pixels apart) meet where their channel ranges do -- d may be a slice of the concat tensor that holds p1 and p2 --, any other two
+ * wherever the n h w pitch elements behind their pointers do; out never goes into `in`'s tensor in a plan (the neighbouring tiles read
+ * its halo).  ESR_ERR_BAD_ARG for that, for a null in / out0 / post_out / blob pointer, and for a view that is misaligned (pitch, coff:
+ * whole 16-byte granules) or does not hold its channels.  esr_asym_step_supported: 1 for such a descriptor with a per-image input below
+ * 1 GiB; esr_asym_step returns ESR_ERR_UNSUPPORTED for every other (fp32 storage included).
+ * esr_pack_asym_s16: the four 3-tap weights [c][cin or c][3] (a (3,1) or (1,3) nn.Conv2d weight as it lies in memory), rounded once (RNE) to
+ * the compute type -- [l1 | m1 | l2 | m2] images, an image = [tap 3][K pair (cin > 32 ? 2 : 1; l2 / m2: 1)][cout tile 2][lane 64][8] 16-bit values,
+ * lane (row, kq) element e of (tap, kp, o) = W[16 o + row][32 kp + 8 kq + e][tap] -- then 3 x 32 fp32 biases: b_l1, b_m1, b_l2 + b_m2.  Rows,
+ * columns and biases beyond c / cin are zero.  esr_unpack_asym_s16 reads the effective weights and the three bias rows [3][c] back (tests).
+ */
+size_t esr_packed_asym_s16_bytes(int cin, int c);
+int    esr_pack_asym_s16(const float* w_l1, const float* b_l1, const float* w_m1, const float* b_m1, const float* w_l2, const float* b_l2,
+                         const float* w_m2, const float* b_m2, int cin, int c, int compute, void* out, size_t out_bytes);
+int    esr_unpack_asym_s16(const void* packed, size_t packed_bytes, int cin, int c, int compute, float* w_l1, float* w_m1, float* w_l2, float* w_m2,
+                           float* bias3);
+int    esr_asym_step_supported(const esr_conv_desc* d);
+int    esr_asym_step(const esr_conv_desc* d, void* hip_stream);
 
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
-    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL */
+    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL, ESR_OP_ASYM_STEP */
     esr_esa_desc esa;           /* the four ESA kinds, ESR_OP_ESA_UNSHUFFLE */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */

@@ -6,6 +6,7 @@ Package contents (only what the path needs):
   engine.py    weight packing, workspace, op-list replay
   imdn.py ...  drop-in nn.Modules with the reference's ctor / state_dict surface
 """
+from .arfdn import ARFDN  # noqa: F401
 from .bmdn import BMDN  # noqa: F401
 from .bsrn import BSRN  # noqa: F401
 from .dwrfdn import DWRFDN  # noqa: F401
@@ -19,4 +20,4 @@ from .repafdn import RePAFDN  # noqa: F401
 from .rfdnext import RFDNeXt  # noqa: F401
 from .rlfn import RLFN_cut  # noqa: F401
 
-__all__ = ["BMDN", "BSRN", "DWRFDN", "ESAN", "FMEN", "FasterRFDN", "IMDN", "PLAINRFDN", "RFDN", "RFDNeXt", "RLFN_cut", "RePAFDN"]
+__all__ = ["ARFDN", "BMDN", "BSRN", "DWRFDN", "ESAN", "FMEN", "FasterRFDN", "IMDN", "PLAINRFDN", "RFDN", "RFDNeXt", "RLFN_cut", "RePAFDN"]

@@ -30,6 +30,7 @@ OP_DWPW_PAIR = 15                                                         # team
 OP_ESA_UNSHUFFLE = 16                                                     # team 35's ESA low-resolution branch (esr_esa_unshuffle_f32 on Op.esa)
 OP_PA_GATE = 17                                                           # RePAFDN's pixel attention + long skip (esr_pa_gate on Op.conv)
 OP_PA_TAIL = 18                                                           # ... with the 3x3 in front of it in the same launch (esr_pa_tail on Op.conv)
+OP_ASYM_STEP = 19                                                         # ARFDN's asymmetric-convolution step (esr_asym_step on Op.conv)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -156,6 +157,7 @@ EXPORTS = [
     "esr_packed_cx_pw1_bytes", "esr_pack_cx_pw1_s16", "esr_packed_cx_pw2_bytes", "esr_pack_cx_pw2_s16", "esr_cx_block_supported", "esr_cx_block_s16",
     "esr_dwpw_pair_supported", "esr_dwpw_pair_s16", "esr_esa_unshuffle_f32",
     "esr_packed_pa_gate_bytes", "esr_pack_pa_gate", "esr_pa_gate_supported", "esr_pa_gate", "esr_pa_tail_supported", "esr_pa_tail",
+    "esr_packed_asym_s16_bytes", "esr_pack_asym_s16", "esr_unpack_asym_s16", "esr_asym_step_supported", "esr_asym_step",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -318,6 +320,16 @@ def lib():
     L.esr_pa_tail_supported.restype = ci
     L.esr_pa_tail.argtypes = [ctypes.POINTER(ConvDesc), vp]
     L.esr_pa_tail.restype = ci
+    L.esr_packed_asym_s16_bytes.argtypes = [ci, ci]
+    L.esr_packed_asym_s16_bytes.restype = sz
+    L.esr_pack_asym_s16.argtypes = [vp] * 8 + [ci, ci, ci, vp, sz]
+    L.esr_pack_asym_s16.restype = ci
+    L.esr_unpack_asym_s16.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.esr_unpack_asym_s16.restype = ci
+    L.esr_asym_step_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_asym_step_supported.restype = ci
+    L.esr_asym_step.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_asym_step.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

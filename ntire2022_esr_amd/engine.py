@@ -325,6 +325,36 @@ def pa_gate_effective(blob, c, store):
     return w[:c, :c].clone(), b[:c].clone()
 
 
+def pack_asym_s16(w_l1, b_l1, w_m1, b_m1, w_l2, b_l2, w_m2, b_m2, compute):
+    """The four 3-tap convolutions of an ARFDB step -- c_l1 [c, cin, 3, 1], c_m1 [c, cin, 1, 3], c_l2 [c, c, 1, 3], c_m2 [c, c, 3, 1]
+    (team14_arfdn/block.py:203-206) -- as esr_asym_step's wpacked: each weight rounded once to the compute type in the fragment order of a
+    K dimension of 32 channels x three taps, then the biases b_l1, b_m1 and b_l2 + b_m2 in fp32 (esr_pack_asym_s16)."""
+    lib = L.lib()
+    ws = [_host(w) for w in (w_l1, w_m1, w_l2, w_m2)]
+    bs = [_host(b) for b in (b_l1, b_m1, b_l2, b_m2)]
+    c, cin = ws[0].shape[:2]
+    shapes = [(c, cin, 3, 1), (c, cin, 1, 3), (c, c, 1, 3), (c, c, 3, 1)]
+    if any(w.dim() != 4 or tuple(w.shape) != sh for w, sh in zip(ws, shapes)) or any(b is not None and tuple(b.shape) != (c,) for b in bs):
+        raise L.EsrError("pack_asym_s16: weights [c, cin, 3, 1], [c, cin, 1, 3], [c, c, 1, 3], [c, c, 3, 1] and biases [c]")
+    nbytes = lib.esr_packed_asym_s16_bytes(cin, c)
+    if not nbytes:
+        raise L.EsrError(f"esr_packed_asym_s16_bytes rejected cin={cin} c={c}")
+    out = torch.empty(nbytes // 4, dtype=torch.float32)
+    args = [x for w, b in zip(ws[:2], bs[:2]) for x in (_ptr(w), _ptr(b))] + [x for w, b in zip(ws[2:], bs[2:]) for x in (_ptr(w), _ptr(b))]
+    L.check(lib.esr_pack_asym_s16(*args, cin, c, L.COMPUTE[compute], _ptr(out), nbytes), "esr_pack_asym_s16")
+    return out
+
+
+def unpack_asym_s16(blob, cin, c, compute):
+    """EFFECTIVE weights of a pack_asym_s16 blob in the reference's shapes -- (w_l1, w_m1, w_l2, w_m2) -- and the bias rows (b_l1, b_m1,
+    b_l2 + b_m2), fp32 (tests)."""
+    blob = _host(blob)
+    ws = [torch.zeros(c, cin, 3), torch.zeros(c, cin, 3), torch.zeros(c, c, 3), torch.zeros(c, c, 3)]
+    b = torch.zeros(3, c)
+    L.check(L.lib().esr_unpack_asym_s16(_ptr(blob), blob.numel() * 4, cin, c, L.COMPUTE[compute], *(_ptr(w) for w in ws), _ptr(b)), "esr_unpack_asym_s16")
+    return (ws[0].reshape(c, cin, 3, 1), ws[1].reshape(c, cin, 1, 3), ws[2].reshape(c, c, 1, 3), ws[3].reshape(c, c, 3, 1)), (b[0], b[1], b[2])
+
+
 def pack_unshuffle(weight, bias):
     """`con_` of team 35's ESA, nn.Conv2d(4 f, f, 1, padding 1), for esr_esa_unshuffle_f32: the esr_pack_dense_f32 blob [4 f][16] + bias[16]
     (the pad outputs f .. 15: zero columns, zero bias)."""
@@ -464,6 +494,7 @@ CX1 = "#cx1"       # esr_pack_cx_pw1_s16 image of a ConvNeXt block's first 1x1 (
 CX2 = "#cx2"       # esr_pack_cx_pw2_s16 image of its second 1x1
 DWPW = "#dwpw"     # pack_dwpw_pw image of a 1x1 of team 35's refinement path (DwPwPair)
 PAG = "#pag"       # pack_pa_gate image of a pixel attention's 1x1 in the plan's storage (PaGate)
+ASYM = "#asym"     # pack_asym_s16 image of an ARFDB step's four 3-tap convolutions, under the name of c{j}_l1 (AsymStep)
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -1414,6 +1445,59 @@ class PaTail(_Fused):
 
 
 @dataclass
+class AsymStep(_Fused):
+    """An ARFDB step as ONE esr_asym_step op -- see Plan.asym_step (asym_step_kernel).  replaces: [c_d, the folded first convolutions of the
+    two pairs (in -> [a_l | a_m]), the folded second ones (+ the residuals)]; p: the earlier steps' distilled maps (views)."""
+    p: list = None
+    kind = "asym"
+    predicate, field, what = "esr_asym_step_supported", "conv", "asymmetric-convolution step"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 3 and all(o.kind == "conv" and o.post is None and o.tail is None and not o.hilo for o in sub) and len(self.p or ()) <= 2
+        cd, ca, cb = sub
+        assert cd.k == 1 and ca.k == 3 and cb.k == 3 and cd.act == ca.act == cb.act and cd.slope == ca.slope == cb.slope
+        assert _same_view(ca.src, cd.src) and cd.res is None and ca.res is None and ca.cout == 2 * cd.cout and cb.cout == cd.cout
+        assert cb.res is None or (_same_view(cb.res, cd.src) and cb.res_mode == L.RES_PRE_ACT and cd.cin == cd.cout)
+
+    def name(self):
+        """the step's name: c{j}_l1, under which `<name>#asym` is packed"""
+        return self.replaces[1].w.split("#")[0]
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        cd, ca, cb = self.replaces
+        op.kind = L.OP_ASYM_STEP
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        d.cin, d.cout, d.ksize = cd.cin, _stored_width(cb.dst, cb.cout), 3
+        d.act, d.slope, d.post_act = cd.act, cd.slope, cd.act
+        d.res_mode = L.RES_PRE_ACT if cb.res is not None else L.RES_NONE
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = st
+        d.inp, d.out0, d.post_out, d.post_cout = _view(cd.src, base), _view(cb.dst, base), _view(cd.dst, base), cd.cout
+        for v, dst in zip(self.p or (), ("res", "tail_cat")):
+            setattr(d, dst, _view(v, base))
+        d.wpacked = ctypes.c_void_p(weights[self.name() + ASYM].data_ptr())
+        d.post_wpacked = ctypes.c_void_p(weights[cd.w + S16].data_ptr())
+
+    def cost(self, plan, desc):             # the step's input (and the earlier distilled maps) read once, d and the result written once
+        cd, ca, cb = self.replaces
+        npix, es, c = plan.npix, plan.esize, cd.cout
+        macs = cd.cin_alg * c + 2 * 3 * cd.cin_alg * c + 2 * 3 * c * c         # the reference's five convolutions
+        nkp = 2 if cd.cin > 32 else 1
+        # executed: v_mfma_f32_16x16x32 steps (16 x 16 x 32 MACs) per 16 x 16 tile -- d's 16 pixel groups x 1x1 chunks, the 36 groups of a_l and
+        # a_m x three taps x K pairs, the 16 rows x six taps of the second convolutions -- x two output tiles
+        ntiles = plan.n * ((plan.h + 15) // 16) * ((plan.w + 15) // 16)
+        fexec = 2.0 * ntiles * 8192 * 2 * (16 * ((cd.cin + 15) // 16) + 36 * 3 * nkp + 16 * 6)
+        kern = f"asym_step_kernel<{_tf(plan.store == 'bf16')}, {nkp}, {_tf(cb.res is not None)}>"
+        np_ = len(self.p or ())
+        rd = float(npix * es * (cd.cin_alg + np_ * c)) + 4.0 * macs
+        stored = float(npix * es * (_stored_channels(cd.src, cd.cin, 16) + (2 + np_) * _stored_channels(cd.dst, c, 16))) + 4.0 * macs
+        return _cost(self.name(), kern, cd.cin, c, 3, 2.0 * npix * macs, rd, float(npix * es * 2 * c), stored, fexec)
+
+
+@dataclass
 class Apply(_Op):
     """ESA's full-resolution tail (esr_esa_apply_f32) -- see Plan.esa_apply"""
     wf: str
@@ -1671,6 +1755,16 @@ class Plan:
         (include/esr_hip.h: esr_pa_tail).  y must not be stored into x's tensor."""
         return self._fuse(mark, PaTail)
 
+    def asym_step(self, mark, p=None):
+        """The three convolutions appended since `mark = len(plan.ops)` -- an ARFDB step in its per-layer form, d = act(c_d(r)), [a_l | a_m] =
+        act(P (*) r), r' = act(Q (*) [d .. | a_l | a_m] (+ r)) (arfdn.py; team14_arfdn/block.py:233-254) -- as ONE esr_asym_step op (16-bit
+        plans): r is read once, d and r' are written once, a_l and a_m never exist; p: the views of the earlier steps' distilled maps that
+        Q adds through identity taps (at most two).  The Conv ops stay attached as `replaces`: complexity counters and algorithmic costs
+        are theirs; the 3-tap blob is pack_asym_s16's (`<c_l1>#asym`).  Not bit-identical to the three launches: another summation order,
+        and the 3-tap weights are rounded once where pack_conv_s16 diffuses the rounding error over a 3x3's taps.  r' must not be stored
+        into r's tensor."""
+        return self._fuse(mark, AsymStep, p=list(p or ()))
+
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [Post(w, dst, cout, act, slope, res), ...] -- one or two 1x1 convolutions evaluated in the same launch
@@ -1814,6 +1908,7 @@ class HipSRModel(nn.Module):
         self._fuse_cascade = False # 16-bit FasterRFDN plans: FRFDB's refinement path as one esr_refine_cascade_s16 launch (Plan.refine_cascade); OFF: faster on one image, not at 32 x 256 x 256
         self._fuse_pair = True     # 16-bit DWRFDN plans: the depthwise-pointwise refinement path as one esr_dwpw_pair_s16 launch (Plan.dwpw_pair); measured: DESIGN.md 7h
         self._fuse_pa_tail = False # 16-bit RePAFDN plans: LR_conv and the pixel attention behind it as one esr_pa_tail launch (Plan.pa_tail); OFF: 2 % slower than the two launches at 32 x 256 x 256 and on one image
+        self._fuse_asym = True     # 16-bit ARFDN plans: an ARFDB step as one esr_asym_step launch (Plan.asym_step); measured: DESIGN.md 7k
         self._fuse_cx = True       # 16-bit RFDNeXt plans: the ConvNeXt block as one esr_cx_block_s16 launch (Plan.cx_block); measured: DESIGN.md 7g
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
@@ -1891,6 +1986,7 @@ class HipSRModel(nn.Module):
     fuse_cx = property(lambda self: self._fuse_cx, lambda self, v: self._set_flag("_fuse_cx", v))
     fuse_pa_tail = property(lambda self: self._fuse_pa_tail, lambda self, v: self._set_flag("_fuse_pa_tail", v))
     fuse_pair = property(lambda self: self._fuse_pair, lambda self, v: self._set_flag("_fuse_pair", v))
+    fuse_asym = property(lambda self: self._fuse_asym, lambda self, v: self._set_flag("_fuse_asym", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels

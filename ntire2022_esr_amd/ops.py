@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .engine import (pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_pa_gate, pack_post_s16,
+from .engine import (pack_asym_s16, pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_pa_gate, pack_post_s16,
                      pack_unshuffle, pack_wino)
 
 
@@ -346,6 +346,47 @@ def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_cof
         raise L.EsrError("distill_step: no kernel for this shape (esr_distill_step_supported)")
     stream = torch.cuda.current_stream(x.device).cuda_stream
     _launch("esr_distill_step_s16", "esr_distill_step_s16", d, stream, L.OP_DISTILL_STEP, "chain")
+    return dd, y
+
+
+def asym_step(x, w_d, b_d, w_l1, b_l1, w_l2, b_l2, w_m1, b_m1, w_m2, b_m2, *, res=False, p1=None, p2=None, act=L.ACT_LRELU, slope=0.05, cin=None,
+              in_coff=0, p1_coff=0, p2_coff=0, d_out=None, d_coff=0, out=None, out_coff=0, out_channels=None):
+    """esr_asym_step: one step of ARFDN's block (team14_arfdn/block.py:233-254) in ONE launch on a 16-bit NHWC tensor x [N, H, W, P], with
+    a(v) = the activation `act` / `slope`: d = a(w_d . x + b_d) (1x1), a_l = a(conv(x, w_l1 [c, cin, 3, 1])), a_m = a(conv(x, w_m1 [c, cin, 1, 3])),
+    y = a(conv(a_l, w_l2 [c, c, 1, 3]) + conv(a_m, w_m2 [c, c, 3, 1]) (+ x if res) + d + p1 + p2) with d, a_l and a_m rounded to x's dtype
+    and a_l / a_m zero-padded.  Returns (d, y).  `cin` channels of x from `in_coff` are read (default: w_d's inputs); p1 / p2: NHWC tensors
+    of x's dtype whose c channels from p1_coff / p2_coff are added (None: absent).
+    d_out / out: caller-provided NHWC tensors (pitch a multiple of 8) that receive d / y from channel d_coff / out_coff; default: freshly
+    allocated zeros of pitch round_up(channels, 8).  out_channels: esr_conv_desc.cout, y's stored width (default c; up to
+    round_up(c, 16): the pad channels are written as zeros)."""
+    st = _s16_store(x, "asym_step")
+    lib = L.lib()
+    n, h, w, _ = x.shape
+    w1 = w_d if w_d.dim() == 4 else w_d[:, :, None, None]
+    c = w1.shape[0]
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.ksize = n, h, w, 3
+    d.cin = w1.shape[1] if cin is None else cin
+    d.post_cout, d.cout = c, (c if out_channels is None else out_channels)
+    d.act, d.post_act, d.slope = act, act, slope
+    d.res_mode = L.RES_PRE_ACT if res else L.RES_NONE
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x, in_coff)
+    if p1 is not None:
+        d.res = _view(p1, p1_coff)
+    if p2 is not None:
+        d.tail_cat = _view(p2, p2_coff)
+    keep = [pack_asym_s16(w_l1, b_l1, w_m1, b_m1, w_l2, b_l2, w_m2, b_m2, st).to(x.device),
+            pack_conv_s16(w1, b_d, st, cin_phys=(w1.shape[1] + 15) // 16 * 16).to(x.device)]
+    d.wpacked, d.post_wpacked = keep[0].data_ptr(), keep[1].data_ptr()
+    dd = _zeros_or(d_out, "asym_step: d_out", x, (n, h, w), (c + 7) // 8 * 8, 8)
+    y = _zeros_or(out, "asym_step: out", x, (n, h, w), (d.cout + 7) // 8 * 8, 8)
+    d.post_out, d.out0 = _view(dd, d_coff), _view(y, out_coff)
+    if not lib.esr_asym_step_supported(ctypes.byref(d)):
+        raise L.EsrError("asym_step: no kernel for this shape (esr_asym_step_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_asym_step", "esr_asym_step", d, stream, L.OP_ASYM_STEP, "conv")
     return dd, y
 
 
