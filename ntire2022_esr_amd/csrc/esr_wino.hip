@@ -80,7 +80,8 @@ struct WinoK {
     int tiles_x, tiles_y;
     unsigned magic_x, magic_y;   // floor(2^32 / d) + 1 (0 for d == 1): n / d == umulhi(n, magic) for n * d < 2^32 (host-checked)
     int y1_blk;
-    int first_share;             // 1/16ths of the items the first-dispatched half of the blocks takes (8 = even split)
+    int first_share;             // 1/16ths of the items the first-dispatched half of the blocks takes (8 = even split);
+                                 // wino8_f32_kernel: 1/16ths of a block's strips that waves 0..3 take (8 = even split, eight neighbours per step)
     // wino8_f32_kernel: input addressing for NHWC and for channel-blocked [n][C/8][h][w][8] inputs (esr_conv_desc.blocked8 & ESR_BLOCKED_IN)
     unsigned pix_floats;         // floats from one pixel to the next inside a chunk: in_pitch (NHWC) | 8 (blocked)
     unsigned in_base;            // byte offset of the first input channel inside an image: in_coff * 4 | (in_coff / 8) * H * W * 32
@@ -216,6 +217,14 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
     // first and gets through an item ~25 % sooner (tools/wino/abl.py probe: 4.6 k against 5.8 k cycles per stage), and the hardware
     // places blocks 0 .. G/2-1 first, so they are the older ones.  With an even split the younger block of every CU runs alone at the
     // end; the first half of the grid therefore takes first_share/16 of the items.  Speed only: any map is correct.
+    // SKIP: an item whose second cout tile lies wholly at or beyond cout_store (couts 48..63 of a 64 -> 48 layer: the upsampler) runs
+    // the first tile alone -- half the MFMAs, no bias / output transform / stores for the dead tile; the live tile's MFMAs keep their
+    // order.  Compiled in where the flagship's 64 -> 64 layers do not run (they have a residual or the blocked store), so those keep
+    // their instruction stream.  Such an item costs about half of a full one, and a block would see one parity of `work` only (off keeps
+    // its parity over k: GC and both class ranges are even), so with SKIP the cout half of an item is (work ^ k) & 1: every block
+    // alternates between the two kinds and the first_share split still counts equal blocks.  The two items of a tile lie in the same
+    // step k, so each (tile, half) is still taken exactly once.
+    constexpr bool SKIP = RES == ESR_RES_NONE && OUT != 1;
     const int nwork = p.N * p.tiles_y * p.tiles_x * p.nhalves;
     const int G = gridDim.x;
     const bool classes = p.first_share != 8 && (G & 15) == 0;
@@ -238,14 +247,14 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
     // the partial one (26 lanes: the others stay off, they would write into the neighbouring stage), its piece 2 does not exist:
     // it repeats piece 0 (same bytes to the same place) so that every wave issues the same number of instructions.
     struct Ctx { int n, x0, y0, half; unsigned voff[3]; };
-    auto setup = [&](int work, Ctx& c) {
+    auto setup = [&](int work, int k, Ctx& c) {
         if (work < 0) {                              // behind the last item: the DMAs still issue (uniform counts), all lanes out of range
             c.n = 0; c.x0 = 0; c.y0 = 0; c.half = 0;
             c.voff[0] = c.voff[1] = c.voff[2] = WN_OOB;
             return;
         }
         const unsigned t = p.nhalves == 2 ? (unsigned)work >> 1 : (unsigned)work;
-        c.half = p.nhalves == 2 ? work & 1 : 0;
+        c.half = p.nhalves == 2 ? (work ^ (SKIP ? k : 0)) & 1 : 0;
         const unsigned tq = wn_div(t, (unsigned)p.tiles_x, p.magic_x);
         const unsigned txi = t - tq * p.tiles_x;
         c.n = (int)wn_div(tq, (unsigned)p.tiles_y, p.magic_y);
@@ -325,9 +334,9 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
     int work = work_index(0);
     if (work < 0) return;
     Ctx cur, nxt;
-    setup(work, cur);
+    setup(work, 0, cur);
     int wn = work_index(1);
-    setup(wn, nxt);
+    setup(wn, 1, nxt);
 
     // ---- prologue: raw chunks 0..2 and U chunk 0 of the first item; V of chunk 0 is computed alone
     {
@@ -367,6 +376,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
     f32x4 acc[16][2];
     for (;;) {
         const bool has_next = wn >= 0;
+        const bool dead = SKIP && cur.half * 32 + 16 >= p.cout_store;          // wave-uniform: this item's second cout tile is all padding
         f32x4 biasv[2];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) biasv[ct] = *reinterpret_cast<const f32x4*>(smem + WN_BIAS_OFF + (cur.half * 32 + ct * 16 + g * 4) * 4);
@@ -376,8 +386,9 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
         // chunk h + 4; the barrier of stage g hands over U g + 1 and raw g + 2.
         // FIRST: the item's first stage -- the accumulators start from constants (A^T M A of a bias b placed at position (1, 1)
         // is b in all four outputs: no bias add in the epilogue, no accumulator clearing)
-        auto stage = [&](auto first_tag, int c, f32x2 (&Vc)[16], f32x2 (&Vn)[16]) __attribute__((always_inline)) {
-            constexpr bool FIRST = decltype(first_tag)::value;
+        // DEAD: the MFMAs of the first cout tile only (SKIP)
+        auto stage = [&](auto first_tag, auto dead_tag, int c, f32x2 (&Vc)[16], f32x2 (&Vn)[16]) __attribute__((always_inline)) {
+            constexpr bool FIRST = decltype(first_tag)::value, DEAD = decltype(dead_tag)::value;
             const bool rc = c + 3 < p.nchunks;
             const wn_i32x4 xr = image_rsrc(rc ? cur.n : nxt.n);
             const int rchunk = rc ? c + 3 : c + 3 - p.nchunks;
@@ -421,32 +432,42 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
                 if (pos >= WN_BARRIER_POS) issue_u(pos - WN_BARRIER_POS, us2, uhalf, uchunk, ulive);
                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                 const f32x4 c0 = FIRST ? (pos == 5 ? biasv[0] : zero) : acc[pos][0];
-                const f32x4 c1 = FIRST ? (pos == 5 ? biasv[1] : zero) : acc[pos][1];
                 const f32x4 af = a[pos & 3];
                 if (FIRST) {
                     acc[pos][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.x, Vc[pos].x, c0, 0, 0, 0);
-                    acc[pos][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.z, Vc[pos].x, c1, 0, 0, 0);
+                    if (!DEAD) acc[pos][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.z, Vc[pos].x, pos == 5 ? biasv[1] : zero, 0, 0, 0);
+                    else acc[pos][1] = zero;                   // never read; defined, so that nothing of the previous item stays live (hipcc spilled)
                 } else {                                       // in place (wn_mfma): no accumulator rotation, no WAR padding
                     wn_mfma(acc[pos][0], af.x, Vc[pos].x);
-                    wn_mfma(acc[pos][1], af.z, Vc[pos].x);
+                    if (!DEAD) wn_mfma(acc[pos][1], af.z, Vc[pos].x);
                 }
                 wn_mfma(acc[pos][0], af.y, Vc[pos].y);
-                wn_mfma(acc[pos][1], af.w, Vc[pos].y);
+                if (!DEAD) wn_mfma(acc[pos][1], af.w, Vc[pos].y);
                 __builtin_amdgcn_sched_barrier(0);
             }
             us = us1;
             rsn = rsn == 2 ? 0 : rsn + 1;
         };
-        stage(std::true_type{}, 0, V0, V1);
-        stage(std::false_type{}, 1, V1, V0);
-        for (int c = 2; c < p.nchunks; c += 2) {
-            stage(std::false_type{}, c, V0, V1);
-            stage(std::false_type{}, c + 1, V1, V0);
+        if (SKIP && dead) {
+            stage(std::true_type{}, std::true_type{}, 0, V0, V1);
+            stage(std::false_type{}, std::true_type{}, 1, V1, V0);
+            for (int c = 2; c < p.nchunks; c += 2) {
+                stage(std::false_type{}, std::true_type{}, c, V0, V1);
+                stage(std::false_type{}, std::true_type{}, c + 1, V1, V0);
+            }
+        } else {
+            stage(std::true_type{}, std::false_type{}, 0, V0, V1);
+            stage(std::false_type{}, std::false_type{}, 1, V1, V0);
+            for (int c = 2; c < p.nchunks; c += 2) {
+                stage(std::false_type{}, std::false_type{}, c, V0, V1);
+                stage(std::false_type{}, std::false_type{}, c + 1, V1, V0);
+            }
         }
 
         // ---- output transform  Y = A^T M A,  A^T = [1 1 1 0; 0 1 -1 -1], then residual / activation / store
         {
-            wn_mfma_drain(acc[15][1]);
+            if (SKIP && dead) wn_mfma_drain(acc[15][0]);
+            else wn_mfma_drain(acc[15][1]);
             const int ybase = cur.y0 + 4 * wv + 2 * ty, xbase = cur.x0 + 2 * tx;
             unsigned pix[2][2];
             bool pok[2][2];
@@ -460,6 +481,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
             const size_t hw = (size_t)p.H * p.W;
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
+                if (SKIP && dead && ct == 1) break;
                 const int cg = cur.half * 32 + ct * 16 + g * 4;            // this lane's first output channel
                 const bool to0 = cur.half * 32 + ct * 16 < p.split;        // uniform: host guarantees split % 16 == 0 or no split
                 const bool cok = cg < p.cout_store;
@@ -524,7 +546,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
         cur = nxt;
         ++k;
         wn = work_index(k + 1);
-        setup(wn, nxt);
+        setup(wn, k + 1, nxt);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the out-of-range DMAs issued behind the last item
 }
@@ -554,6 +576,7 @@ constexpr int W8_SLOT_BYTES = W8_SLOTS * 16;           // 3552
 constexpr int W8_LAST_LANES = W8_SLOTS - 192;
 constexpr int W8_EPI_STORES = 8;                       // buffer stores per wave and strip (2 cout tiles x 2 x 2 pixels)
 constexpr int W8_MAX_BLOCKS = 256;
+constexpr int W8_OLD_SHARE = 11;                       // WinoK.first_share of every wino8_f32_kernel launch: 8 .. 12 swept, LAB_NOTES.md 14.2
 #ifndef W8_TP
 #define W8_TP 2
 #endif
@@ -626,7 +649,17 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
     const int nstrips = p.N * p.tiles_y * p.tiles_x;                       // tiles_x = strips per row (16 px), tiles_y = strips per column (4 px)
     const int per_block = (nstrips + npair - 1) / npair;
     const int s_end = min((pidx + 1) * per_block, nstrips);
+    // The two waves of a SIMD (w and w + 4) do not share the MFMA pipe evenly: the older one (w) is served first (see wino_f32_kernel's work
+    // walk).  first_share != 8: waves 0..3 take the first first_share/16 of the run (rounded up to whole steps of 4 strips), waves 4..7 the
+    // rest, four horizontal neighbours per step each.  Speed only: any map that covers the run once is correct.
+    const int s_beg = min(pidx * per_block, s_end);
+    const int n_old = min(s_end - s_beg, ((int)((long)(s_end - s_beg) * p.first_share / 16) + 3) & ~3);
+    const int my_beg = wv < 4 ? s_beg : s_beg + n_old, my_end = wv < 4 ? s_beg + n_old : s_end;
     auto strip_index = [&](int k) -> int {
+        if (p.first_share != 8) {
+            const int s = my_beg + k * 4 + (wv & 3);
+            return s < my_end ? s : -1;
+        }
         const int s = pidx * per_block + k * 8 + wv;
         return s < s_end ? s : -1;
     };
@@ -936,7 +969,8 @@ int wn_launch(const WinoK& k, int grid, hipStream_t st)
     return esr_check_launch("wino_f32_kernel launch");
 }
 
-bool g_wino8_enabled = true;          // research switch (esr_dbg_wino8): A/B of the two Winograd kernels inside one process
+int g_wino8_mode = 1;                 // research switch (esr_dbg_wino8): A/B of the two Winograd kernels inside one process
+int g_wino8_share = 0;                // research switch (esr_dbg_wino8_share): 0 = W8_OLD_SHARE
 
 // G of F(2x2, 3x3)
 const double WN_G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
@@ -1042,8 +1076,11 @@ int esr_unpack_wino_f32(const void* packed, size_t bytes, int cin, int cout, con
     return ESR_OK;
 }
 
-/* research switch, not part of the ABI header: 0 = every Winograd launch on wino_f32_kernel */
-void esr_dbg_wino8(int on) { g_wino8_enabled = on != 0; }
+/* research switch, not part of the ABI header: 0 = every Winograd launch on wino_f32_kernel, 1 = the product's choice, 2 = wino8_f32_kernel
+ * also below its strip count (tests of its strip walk on small images) */
+void esr_dbg_wino8(int on) { g_wino8_mode = on < 0 || on > 2 ? 1 : on; }
+/* research switch, not part of the ABI header: WinoK.first_share of the next wino8_f32_kernel launches, 1..15; anything else = W8_OLD_SHARE */
+void esr_dbg_wino8_share(int s) { g_wino8_share = s >= 1 && s <= 15 ? s : 0; }
 
 }  // extern "C"
 
@@ -1091,16 +1128,17 @@ int esr_conv2d_wino(const esr_conv_desc* d, void* hip_stream)
     k.pix_floats = blocked_in ? 8u : (unsigned)d->in.pitch;
     k.in_base = blocked_in ? (unsigned)(d->in.coff / 8) * (unsigned)(d->h * d->w * 32) : (unsigned)d->in.coff * 4u;
     k.chunk_stride = blocked_in ? (unsigned)(d->h * d->w * 32) : 32u;
-    if ((k.nchunks == 4 || k.nchunks == 6) && d->res_mode == ESR_RES_NONE && d->out_layout == ESR_NHWC && g_wino8_enabled) {
+    if ((k.nchunks == 4 || k.nchunks == 6) && d->res_mode == ESR_RES_NONE && d->out_layout == ESR_NHWC && g_wino8_mode) {
         const long sx = (d->w + 15) / 16, sy = (d->h + 3) / 4;
         const long nstrips = (long)k.N * sx * sy;
         const double out_bytes = (double)d->h * d->w * 4.0 * (d->out0.pitch > d->out1.pitch ? d->out0.pitch : d->out1.pitch);
         const bool fits = (double)k.N * sx * sy * (sx > sy ? sx : sy) < 4294967296.0 && out_bytes < 2147482624.0;
-        if (fits && nstrips >= 4L * 8 * W8_MAX_BLOCKS / k.nhalves) {
+        if (fits && (nstrips >= 4L * 8 * W8_MAX_BLOCKS / k.nhalves || g_wino8_mode == 2)) {
             WinoK w = k;
             w.tiles_x = (int)sx; w.tiles_y = (int)sy;
             w.magic_x = sx == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)sx) + 1u;
             w.magic_y = sy == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)sy) + 1u;
+            w.first_share = g_wino8_share ? g_wino8_share : W8_OLD_SHARE;
             const int grid8 = W8_MAX_BLOCKS;
             const bool blk = k.y1_blk != 0;
             const bool lr = a == ESR_ACT_LRELU;
