@@ -429,7 +429,9 @@ typedef enum esr_op_kind {
     ESR_OP_ESA_UNSHUFFLE = 16,  /* esr_esa_unshuffle_f32 on esr_op.esa (additive within ABI v12) */
     ESR_OP_PA_GATE = 17,        /* esr_pa_gate on esr_op.conv (additive within ABI v12) */
     ESR_OP_PA_TAIL = 18,        /* esr_pa_tail on esr_op.conv (additive within ABI v12) */
-    ESR_OP_ASYM_STEP = 19       /* esr_asym_step on esr_op.conv (additive within ABI v12) */
+    ESR_OP_ASYM_STEP = 19,      /* esr_asym_step on esr_op.conv (additive within ABI v12) */
+    ESR_OP_PRELU = 20,          /* esr_prelu on esr_op.conv (additive within ABI v12) */
+    ESR_OP_RESDB_STEP = 21      /* esr_resdb_step on esr_op.conv (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -794,11 +796,59 @@ int    esr_unpack_asym_s16(const void* packed, size_t packed_bytes, int cin, int
                            float* bias3);
 int    esr_asym_step_supported(const esr_conv_desc* d);
 int    esr_asym_step(const esr_conv_desc* d, void* hip_stream);
+/*
+ * esr_prelu (additive within ABI v12; op kind ESR_OP_PRELU on esr_op.conv) -- a per-channel nn.PReLU in front of a convolution as ONE streaming
+ * launch in fp32, bf16 and fp16 storage (prelu_kernel, csrc/esr_resdb.hip): ResDN's block (models/team43_resdn.py:48-111) pre-activates every
+ * convolution, and the raw tensors are read again elsewhere, so the activation is the consumer's.  Up to four NHWC source views, one behind
+ * the other as a torch.cat would put them, go into one dense tensor:
+ *     out[c] = store(v >= 0 ? v : a[c] * v)                   v = the source channel that output channel c stands for
+ * NOT max(v, a v): slopes are any fp32 number (the checkpoint's span -1.82 .. +3.62).  A non-negative value passes through bit for bit; the
+ * product is rounded ONCE (RNE) to the storage type.  An esr_conv_desc carries it, no field added and no struct changed:
+ *     in / cin, res / split, tail_cat / tail_cat_c, out1 / tail_cout      source 0 .. 3 and its channel count (out1 is READ here); the sources are
+ *                          used in this order, the first zero count ends the list and nothing may follow it
+ *     cout                 the sum of the counts (<= 512);  out0: the result, cout channels from coff, the pad slots up to the 16-byte granule
+ *                          (4 fp32 / 8 16-bit channels) written as zeros, nothing behind them
+ *     ksize, layouts       1, ESR_NHWC both;  act ESR_ACT_NONE, res_mode ESR_RES_NONE;  storage == compute: F32, BF16 or F16
+ *     wpacked              esr_pack_prelu(slopes, cout): cout fp32 slopes in output-channel order
+ * Only a source's own channels are read: its pad slots and whatever lies behind the tensor never reach the output.  Every other feature
+ * field must be zero.  ESR_ERR_BAD_ARG for a null source / out0 / wpacked, a view whose pitch or coff is not whole 16-byte granules or that does not
+ * hold its channels, and for an output whose bytes meet a source's (two views of one pixel grid meet where their channel ranges do, any
+ * other two wherever the n h w pitch elements behind their pointers do); ESR_ERR_UNSUPPORTED where esr_prelu_supported says 0.
+ */
+size_t esr_packed_prelu_bytes(int c);
+int    esr_pack_prelu(const float* slopes, int c, void* out, size_t out_bytes);
+int    esr_unpack_prelu(const void* packed, size_t packed_bytes, int c, float* slopes);
+int    esr_prelu_supported(const esr_conv_desc* d);
+int    esr_prelu(const esr_conv_desc* d, void* hip_stream);
+/*
+ * esr_resdb_step (additive within ABI v12; op kind ESR_OP_RESDB_STEP on esr_op.conv) -- one step of ResDN's block (models/team43_resdn.py:93-106)
+ * as ONE launch on 16-bit storage (resdb_step_kernel, csrc/esr_resdb.hip), with prelu(v, a) = v >= 0 ? v : a v per channel and `~` = rounded
+ * once (RNE) to the storage type, as a stored tensor holds it:
+ *     u = (prelu(cat(x, e0, e1), a_e))~         e = W_e . u + b_e (fp32)         dists = e[48:]~  (stored)         r = e[:48]~
+ *     t = (prelu(r, a_c))~, and t = 0 outside the image (the 3x3's zero padding: a halo pixel is 0, not prelu(b_e); esr_distill_step_s16's rule)
+ *     y = (x + W_c (*) t + b_c)~  (stored)
+ * x is read once, dists and y are written once; u, e, r and t never reach memory.  A 16 x 16 output tile is staged once with a one-pixel
+ * halo, persistent over the tiles.  An esr_conv_desc carries it, no field added and no struct changed:
+ *     cin, cout            48, 48: x and y (n = 48);  ksize 3, ESR_NHWC both;  act, post_act ESR_ACT_NONE, res_mode ESR_RES_NONE
+ *     post_cout            16, 32 or 48: the distilled outputs (d = 16);  tail_cat_c  0, 16 or 32: the extra inputs, 16 channels each
+ *     in, out0, post_out   x, y, dists;  res, tail_cat: the first / second extra input (null where tail_cat_c says absent)
+ *     storage, compute     BF16 / BF16 or F16 / F16
+ *     wpacked              esr_pack_conv_s16(W_c, b_c, 48, 48, ksize 3): the 3x3 as the stand-alone launch rounds it
+ *     post_wpacked         esr_pack_conv_s16(W_e, b_e, 48 + tail_cat_c, 48 + post_cout, ksize 1): the hi + lo pairs the stand-alone 1x1 multiplies by
+ *     tail_wpacked         esr_pack_prelu(cat(a_e, a_c)): 48 + tail_cat_c, then 48 fp32 slopes
+ * esr_resdb_step_supported is exactly this set (it does not look at pointers); every other feature field must be zero.  No byte written
+ * through out0 or post_out may belong to what the launch reads through in, res or tail_cat, or to the other output (views of one pixel
+ * grid meet where their channel ranges do: dists and the extra inputs are slices of one buffer in a plan); y never goes into x's tensor
+ * (the neighbouring tiles read its halo).  ESR_ERR_BAD_ARG for that, for a null in / out0 / post_out / blob, an extra input that is null or
+ * set against tail_cat_c, and a view that is misaligned (pitch, coff: whole 16-byte granules) or does not hold its channels.
+ */
+int    esr_resdb_step_supported(const esr_conv_desc* d);
+int    esr_resdb_step(const esr_conv_desc* d, void* hip_stream);
 
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
-    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL, ESR_OP_ASYM_STEP */
+    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL, ESR_OP_ASYM_STEP, ESR_OP_PRELU, ESR_OP_RESDB_STEP */
     esr_esa_desc esa;           /* the four ESA kinds, ESR_OP_ESA_UNSHUFFLE */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */

@@ -31,6 +31,8 @@ OP_ESA_UNSHUFFLE = 16                                                     # team
 OP_PA_GATE = 17                                                           # RePAFDN's pixel attention + long skip (esr_pa_gate on Op.conv)
 OP_PA_TAIL = 18                                                           # ... with the 3x3 in front of it in the same launch (esr_pa_tail on Op.conv)
 OP_ASYM_STEP = 19                                                         # ARFDN's asymmetric-convolution step (esr_asym_step on Op.conv)
+OP_PRELU = 20                                                             # ResDN's per-channel PReLU in front of a convolution (esr_prelu on Op.conv)
+OP_RESDB_STEP = 21                                                        # a ResDB step of ResDN in one launch (esr_resdb_step on Op.conv)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -158,6 +160,7 @@ EXPORTS = [
     "esr_dwpw_pair_supported", "esr_dwpw_pair_s16", "esr_esa_unshuffle_f32",
     "esr_packed_pa_gate_bytes", "esr_pack_pa_gate", "esr_pa_gate_supported", "esr_pa_gate", "esr_pa_tail_supported", "esr_pa_tail",
     "esr_packed_asym_s16_bytes", "esr_pack_asym_s16", "esr_unpack_asym_s16", "esr_asym_step_supported", "esr_asym_step",
+    "esr_packed_prelu_bytes", "esr_pack_prelu", "esr_unpack_prelu", "esr_prelu_supported", "esr_prelu", "esr_resdb_step_supported", "esr_resdb_step",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -330,6 +333,20 @@ def lib():
     L.esr_asym_step_supported.restype = ci
     L.esr_asym_step.argtypes = [ctypes.POINTER(ConvDesc), vp]
     L.esr_asym_step.restype = ci
+    L.esr_packed_prelu_bytes.argtypes = [ci]
+    L.esr_packed_prelu_bytes.restype = sz
+    L.esr_pack_prelu.argtypes = [vp, ci, vp, sz]
+    L.esr_pack_prelu.restype = ci
+    L.esr_unpack_prelu.argtypes = [vp, sz, ci, vp]
+    L.esr_unpack_prelu.restype = ci
+    L.esr_prelu_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_prelu_supported.restype = ci
+    L.esr_prelu.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_prelu.restype = ci
+    L.esr_resdb_step_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_resdb_step_supported.restype = ci
+    L.esr_resdb_step.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_resdb_step.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

@@ -1205,6 +1205,8 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_PA_GATE: return esr_pa_gate(&op.conv, hip_stream);
         case ESR_OP_PA_TAIL: return esr_pa_tail(&op.conv, hip_stream);
         case ESR_OP_ASYM_STEP: return esr_asym_step(&op.conv, hip_stream);
+        case ESR_OP_PRELU: return esr_prelu(&op.conv, hip_stream);
+        case ESR_OP_RESDB_STEP: return esr_resdb_step(&op.conv, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

@@ -355,6 +355,27 @@ def unpack_asym_s16(blob, cin, c, compute):
     return (ws[0].reshape(c, cin, 3, 1), ws[1].reshape(c, cin, 1, 3), ws[2].reshape(c, c, 1, 3), ws[3].reshape(c, c, 3, 1)), (b[0], b[1], b[2])
 
 
+def pack_prelu(slopes):
+    """The slopes of one nn.PReLU(c), or of several one behind the other ([c] fp32), as esr_prelu's wpacked: c fp32 values in output-channel
+    order, zeros up to a multiple of 8 (esr_pack_prelu).  Slopes are never rounded, whatever the storage."""
+    a = _host(slopes).reshape(-1)
+    c = a.numel()
+    nbytes = L.lib().esr_packed_prelu_bytes(c)
+    if not nbytes:
+        raise L.EsrError(f"esr_packed_prelu_bytes rejected c={c}")
+    out = torch.empty(nbytes // 4, dtype=torch.float32)
+    L.check(L.lib().esr_pack_prelu(_ptr(a), c, _ptr(out), nbytes), "esr_pack_prelu")
+    return out
+
+
+def unpack_prelu(blob, c):
+    """the c slopes of a pack_prelu blob (tests)"""
+    blob = _host(blob)
+    a = torch.zeros(c)
+    L.check(L.lib().esr_unpack_prelu(_ptr(blob), blob.numel() * 4, c, _ptr(a)), "esr_unpack_prelu")
+    return a
+
+
 def pack_unshuffle(weight, bias):
     """`con_` of team 35's ESA, nn.Conv2d(4 f, f, 1, padding 1), for esr_esa_unshuffle_f32: the esr_pack_dense_f32 blob [4 f][16] + bias[16]
     (the pad outputs f .. 15: zero columns, zero bias)."""
@@ -495,6 +516,8 @@ CX2 = "#cx2"       # esr_pack_cx_pw2_s16 image of its second 1x1
 DWPW = "#dwpw"     # pack_dwpw_pw image of a 1x1 of team 35's refinement path (DwPwPair)
 PAG = "#pag"       # pack_pa_gate image of a pixel attention's 1x1 in the plan's storage (PaGate)
 ASYM = "#asym"     # pack_asym_s16 image of an ARFDB step's four 3-tap convolutions, under the name of c{j}_l1 (AsymStep)
+RSTEP = "#step"    # pack_prelu image of a ResDB step's slopes, cat(a_e, a_c), under the name of the expansion's nn.PReLU (ResdbStep)
+PRELU = "#prelu"   # pack_prelu image of the slopes in front of a convolution, under the name of the nn.PReLU (Prelu)
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -1410,6 +1433,102 @@ class PaGate(_Op):
 
 
 @dataclass
+class Prelu(_Op):
+    """A per-channel PReLU over a concat of up to four views as one streaming launch (esr_prelu) -- see Plan.prelu.  The blob `w + PRELU` is
+    pack_prelu's."""
+    w: str
+    srcs: list                 # [(view, channels), ...] in the concat's order
+    dst: object
+    kind = "prelu"
+    FIELDS = (("inp", "cin"), ("res", "split"), ("tail_cat", "tail_cat_c"), ("out1", "tail_cout"))
+
+    @property
+    def c(self):
+        return sum(c for _, c in self.srcs)
+
+    def encode(self, op, plan, base, weights):
+        assert 1 <= len(self.srcs) <= len(self.FIELDS)
+        op.kind = L.OP_PRELU
+        d = op.conv
+        d.n, d.h, d.w, d.ksize = plan.n, plan.h, plan.w, 1
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = L.STORE[plan.store]
+        for (v, c), (view, count) in zip(self.srcs, self.FIELDS):
+            setattr(d, view, _view(v, base))
+            setattr(d, count, c)
+        d.cout = self.c
+        d.out0 = _view(self.dst, base)
+        d.wpacked = ctypes.c_void_p(weights[self.w + PRELU].data_ptr())
+        if not L.lib().esr_prelu_supported(ctypes.byref(d)):
+            raise L.EsrError(f"{self.w}: esr_prelu does not take this descriptor")
+
+    def cost(self, plan, desc):             # every source read once, the dense result written once
+        npix, es, c = plan.npix, plan.esize, self.c
+        g = 16 // es
+        vec = all(n % g == 0 for _, n in self.srcs)
+        rd = float(npix * es * c) + 4.0 * c
+        return _cost(self.w, f"prelu_kernel<{L.STORE[plan.store]}, {_tf(vec)}>", c, c, 1, float(npix * c), rd, float(npix * es * c),
+                     rd + float(npix * es * _stored_channels(self.dst, c, g)))
+
+    def prelu_elements(self, plan):           # the reference's counters add one flop per element of an nn.PReLU's output
+        return self.c * plan.npix
+
+
+@dataclass
+class ResdbStep(_Fused):
+    """A ResDB step as ONE esr_resdb_step op -- see Plan.resdb_step (resdb_step_kernel).  replaces: [the PReLU over cat(x, earlier distilled
+    maps), the expansion 1x1's `res` part, its distilled part, the PReLU of res, the 3x3 with the residual x]."""
+    kind = "resdb"
+    predicate, field, what = "esr_resdb_step_supported", "conv", "ResDB step"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 5 and [o.kind for o in sub] == ["prelu", "conv", "conv", "prelu", "conv"]
+        pe, cr, cd, pc, c3 = sub
+        assert all(o.post is None and o.tail is None and not o.hilo and o.act == L.ACT_NONE for o in (cr, cd, c3))
+        assert cr.k == 1 and cd.k == 1 and c3.k == 3 and _same_view(cr.src, pe.dst) and _same_view(cd.src, pe.dst) and cr.res is None and cd.res is None
+        assert len(pc.srcs) == 1 and _same_view(pc.srcs[0][0], cr.dst) and _same_view(c3.src, pc.dst)
+        assert c3.res_mode == L.RES_PRE_ACT and _same_view(c3.res, pe.srcs[0][0]) and cr.cin == cd.cin == pe.c and pc.c == cr.cout == c3.cin
+
+    def name(self):
+        """the step's name: expansion{j}.0, under which `<name>#step` is packed"""
+        return self.replaces[0].w
+
+    def encode(self, op, plan, base, weights):
+        st = L.STORE[plan.store]
+        pe, cr, cd, pc, c3 = self.replaces
+        op.kind = L.OP_RESDB_STEP
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        d.cin, d.cout, d.ksize = pe.srcs[0][1], c3.cout, 3
+        d.post_cout, d.tail_cat_c = cd.cout, sum(c for _, c in pe.srcs[1:])
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = st
+        d.inp, d.out0, d.post_out = _view(pe.srcs[0][0], base), _view(c3.dst, base), _view(cd.dst, base)
+        for (v, _), dst in zip(pe.srcs[1:], ("res", "tail_cat")):
+            setattr(d, dst, _view(v, base))
+        whole = cr.w[:-len("#res")]                      # the expansion 1x1 as ONE blob: its `res` rows, then its distilled rows
+        d.wpacked = ctypes.c_void_p(weights[c3.w + S16].data_ptr())
+        d.post_wpacked = ctypes.c_void_p(weights[whole + S16].data_ptr())
+        d.tail_wpacked = ctypes.c_void_p(weights[self.name() + RSTEP].data_ptr())
+
+    def cost(self, plan, desc):             # x and the earlier distilled maps read once, the step's distilled maps and x' written once
+        pe, cr, cd, pc, c3 = self.replaces
+        npix, es = plan.npix, plan.esize
+        cin, n, nd = pe.c, c3.cout, cd.cout
+        macs = cin * (n + nd) + 9 * n * n
+        ntiles = plan.n * ((plan.h + 15) // 16) * ((plan.w + 15) // 16)
+        nch, nx = cin // 16, (cin - n) // 16
+        # executed: v_mfma_f32_16x16x32 steps per tile -- the `res` rows on the 21 pixel groups of the staged 18 x 18, the distilled rows and the
+        # 3x3's five tap pairs x three chunks on the tile's 16 rows
+        fexec = 2.0 * ntiles * 8192 * (21 * nch * 3 + 16 * nch * (nd // 16) + 16 * 15 * 3)
+        kern = f"resdb_step_kernel<{_tf(plan.store == 'bf16')}, {nx}, {nd // 16}>"
+        rd = float(npix * es * cin) + 4.0 * macs
+        wr = float(npix * es * (n + nd))
+        return _cost(self.name(), kern, cin, n, 3, 2.0 * npix * macs + npix * (cin + n), rd, wr, rd + wr, fexec)
+
+
+@dataclass
 class PaTail(_Fused):
     """A 3x3 and the pixel attention behind it as ONE esr_pa_tail op -- see Plan.pa_tail (pa_tail_kernel).  replaces: [conv, pagate]."""
     kind = "patail"
@@ -1746,6 +1865,21 @@ class Plan:
         s is a Plan.pair(), L.HILO_OUT -- dst is one.  dst is another tensor than src and s."""
         self.ops.append(PaGate(wname, src, dst, c, s, hilo))
 
+    def prelu(self, wname, srcs, dst):
+        """dst = prelu(cat(srcs), a): an nn.PReLU with one slope per channel in front of a convolution (team43_resdn.py:54-83), every storage
+        (esr_prelu), v >= 0 ? v : a v with any fp32 slope.  srcs: [(view, channels), ...], at most four, in the order of the torch.cat that
+        never runs; dst: a dense tensor that is none of the sources; `wname + PRELU` names a pack_prelu blob of all the channels' slopes."""
+        self.ops.append(Prelu(wname, list(srcs), dst))
+
+    def resdb_step(self, mark):
+        """The five ops appended since `mark = len(plan.ops)` -- a ResDB step in its per-layer form, u = prelu(cat(x, ..)), r = W_e[:48] . u,
+        dists = W_e[48:] . u, t = prelu(r), x' = x + W_c (*) t (resdn.py; team43_resdn.py:93-106) -- as ONE esr_resdb_step op (16-bit plans): x
+        and the earlier distilled maps are read once, dists and x' are written once, u, r and t never exist.  The ops stay attached as
+        `replaces`: complexity counters and algorithmic costs are theirs; the blobs are the 3x3's and the WHOLE expansion's esr_pack_conv_s16
+        images and pack_prelu(cat(a_e, a_c)) (`<expansion.0>#step`).  It stores what the five launches store, up to the summation order of
+        the fp32 sums.  x' must not be stored into x's tensor."""
+        return self._fuse(mark, ResdbStep)
+
     def pa_tail(self, mark):
         """The two ops appended since `mark = len(plan.ops)` -- a plain 3x3 and the pixel attention that reads its result, t = conv(x),
         y = t * sigmoid(W . t + b) (+ s) (team10_repafdn/repafdn.py:55-57) -- as ONE esr_pa_tail op (16-bit plans): x (and s) are read once, y
@@ -1909,6 +2043,7 @@ class HipSRModel(nn.Module):
         self._fuse_pair = True     # 16-bit DWRFDN plans: the depthwise-pointwise refinement path as one esr_dwpw_pair_s16 launch (Plan.dwpw_pair); measured: DESIGN.md 7h
         self._fuse_pa_tail = False # 16-bit RePAFDN plans: LR_conv and the pixel attention behind it as one esr_pa_tail launch (Plan.pa_tail); OFF: 2 % slower than the two launches at 32 x 256 x 256 and on one image
         self._fuse_asym = True     # 16-bit ARFDN plans: an ARFDB step as one esr_asym_step launch (Plan.asym_step); measured: DESIGN.md 7k
+        self._fuse_resdb = False   # 16-bit ResDN plans: a ResDB step as one esr_resdb_step launch (Plan.resdb_step); OFF: 1.8x slower than the five launches at 32 x 256 x 256, 1.5x on one image
         self._fuse_cx = True       # 16-bit RFDNeXt plans: the ConvNeXt block as one esr_cx_block_s16 launch (Plan.cx_block); measured: DESIGN.md 7g
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
@@ -1986,6 +2121,7 @@ class HipSRModel(nn.Module):
     fuse_cx = property(lambda self: self._fuse_cx, lambda self, v: self._set_flag("_fuse_cx", v))
     fuse_pa_tail = property(lambda self: self._fuse_pa_tail, lambda self, v: self._set_flag("_fuse_pa_tail", v))
     fuse_pair = property(lambda self: self._fuse_pair, lambda self, v: self._set_flag("_fuse_pair", v))
+    fuse_resdb = property(lambda self: self._fuse_resdb, lambda self, v: self._set_flag("_fuse_resdb", v))
     fuse_asym = property(lambda self: self._fuse_asym, lambda self, v: self._set_flag("_fuse_asym", v))
 
     def _skip_hilo(self, plan, c):

@@ -8,7 +8,7 @@ import torch
 
 from . import _lib as L
 from .engine import (pack_asym_s16, pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_pa_gate, pack_post_s16,
-                     pack_unshuffle, pack_wino)
+                     pack_prelu, pack_unshuffle, pack_wino)
 
 
 def _view(t, coff=0):
@@ -387,6 +387,73 @@ def asym_step(x, w_d, b_d, w_l1, b_l1, w_l2, b_l2, w_m1, b_m1, w_m2, b_m2, *, re
         raise L.EsrError("asym_step: no kernel for this shape (esr_asym_step_supported)")
     stream = torch.cuda.current_stream(x.device).cuda_stream
     _launch("esr_asym_step", "esr_asym_step", d, stream, L.OP_ASYM_STEP, "conv")
+    return dd, y
+
+
+def prelu(srcs, slopes, *, out=None, out_coff=0):
+    """esr_prelu: a per-channel nn.PReLU over the concat of up to four NHWC views in ONE streaming launch, fp32 / bf16 / fp16 tensors on the
+    GPU: y[c] = v >= 0 ? v : slopes[c] * v, the product rounded once to the tensors' dtype.  srcs: [(tensor [N, H, W, P], first channel, channels),
+    ...] (a bare tensor: all its channels) in the concat's order; slopes: fp32 [sum of the channels], any sign and size.
+    out: a caller-provided NHWC tensor (pitch a multiple of the 16-byte granule) that receives y from channel out_coff, none of the sources;
+    default: freshly allocated zeros of pitch round_up(channels, granule).  Returns y."""
+    srcs = [(s, 0, s.shape[-1]) if isinstance(s, torch.Tensor) else tuple(s) for s in srcs]
+    x = srcs[0][0]
+    if not x.is_cuda:
+        raise L.EsrError("prelu: tensors must live on the GPU; there is no CPU fallback")
+    if not 1 <= len(srcs) <= 4 or any(t.dtype != x.dtype or t.device != x.device or not t.is_contiguous() or tuple(t.shape[:3]) != tuple(x.shape[:3])
+                                      for t, _, _ in srcs):
+        raise L.EsrError("prelu: one to four contiguous NHWC tensors of one dtype, device and N x H x W")
+    st = _STORE_OF[x.dtype]
+    gran = 4 if st == "f32" else 8
+    n, h, w, _ = x.shape
+    ctot = sum(c for _, _, c in srcs)
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.ksize, d.cout = n, h, w, 1, ctot
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = d.compute = L.STORE[st]
+    for (t, coff, c), (view, count) in zip(srcs, (("inp", "cin"), ("res", "split"), ("tail_cat", "tail_cat_c"), ("out1", "tail_cout"))):
+        setattr(d, view, _view(t, coff))
+        setattr(d, count, c)
+    keep = pack_prelu(slopes).to(x.device)
+    d.wpacked = keep.data_ptr()
+    y = _zeros_or(out, "prelu: out", x, (n, h, w), (ctot + gran - 1) // gran * gran, gran)
+    d.out0 = _view(y, out_coff)
+    if not L.lib().esr_prelu_supported(ctypes.byref(d)):
+        raise L.EsrError("prelu: esr_prelu does not take this descriptor (esr_prelu_supported)")
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_prelu", "esr_prelu", d, stream, L.OP_PRELU, "conv")
+    return y
+
+
+def resdb_step(x, a_e, w_e, b_e, a_c, w_c, b_c, *, extras=(), x_coff=0, d_out=None, d_coff=0, out=None, out_coff=0):
+    """esr_resdb_step: one step of ResDN's block (team43_resdn.py:93-106) in ONE launch on 16-bit NHWC tensors: u = prelu(cat(x, extras), a_e),
+    e = w_e . u + b_e (1x1, [48 + 16 nd, 48 + 16 nx, 1, 1]), dists = e[48:], t = prelu(e[:48], a_c) zero-padded, y = x + conv3x3(t, w_c) + b_c, with
+    u, e[:48], t, dists and y rounded once to x's dtype.  x: [N, H, W, P] whose 48 channels from x_coff are read; extras: up to two
+    (tensor, first channel) pairs of 16 channels each.  Returns (dists, y).  d_out / out: caller-provided NHWC tensors that receive dists / y
+    from channel d_coff / out_coff; default: freshly allocated zeros."""
+    st = _s16_store(x, "resdb_step")
+    lib = L.lib()
+    n, h, w, _ = x.shape
+    nd, nx = w_e.shape[0] - 48, len(extras)
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.ksize, d.cin, d.cout = n, h, w, 3, 48, 48
+    d.post_cout, d.tail_cat_c = nd, 16 * nx
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x, x_coff)
+    for (t, coff), name in zip(extras, ("res", "tail_cat")):
+        setattr(d, name, _view(t, coff))
+    w1 = w_e if w_e.dim() == 4 else w_e[:, :, None, None]
+    keep = [pack_conv_s16(w_c, b_c, st).to(x.device), pack_conv_s16(w1, b_e, st).to(x.device),
+            pack_prelu(torch.cat([a_e.float().reshape(-1), a_c.float().reshape(-1)])).to(x.device)]
+    d.wpacked, d.post_wpacked, d.tail_wpacked = keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()
+    if not lib.esr_resdb_step_supported(ctypes.byref(d)) or w1.shape[1] != 48 + 16 * nx or a_e.numel() != 48 + 16 * nx or a_c.numel() != 48:
+        raise L.EsrError("resdb_step: no kernel for this shape (esr_resdb_step_supported: n = 48, d = 16, 1..3 distilled outputs, 0..2 extra inputs)")
+    dd = _zeros_or(d_out, "resdb_step: d_out", x, (n, h, w), nd, 8)
+    y = _zeros_or(out, "resdb_step: out", x, (n, h, w), 48, 8)
+    d.post_out, d.out0 = _view(dd, d_coff), _view(y, out_coff)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_resdb_step", "esr_resdb_step", d, stream, L.OP_RESDB_STEP, "conv")
     return dd, y
 
 

@@ -23,6 +23,7 @@ MODELS = {          # name -> (constructor, the flags its plans read besides hil
     "FasterRFDN": (pkg.FasterRFDN, ("fuse_esa_lowres", "fuse_cascade")), "RFDNeXt": (pkg.RFDNeXt, ("tight_pitch", "fuse_cx")),
     "DWRFDN": (pkg.DWRFDN, ("tight_pitch", "fuse_pair")), "RePAFDN": (pkg.RePAFDN, ("fuse_esa_lowres", "fuse_pa_tail")),
     "ARFDN": (pkg.ARFDN, ("fuse_esa_lowres", "tight_pitch", "fuse_asym")),
+    "ResDN": (pkg.ResDN, ("fuse_esa_lowres", "fuse_resdb")),
 }
 SHAPES = ((1, 15, 16), (2, 45, 70), (1, 339, 510), (32, 256, 256))      # the last one crosses the 256-tile threshold of the fused tails
 
