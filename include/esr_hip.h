@@ -431,7 +431,9 @@ typedef enum esr_op_kind {
     ESR_OP_PA_TAIL = 18,        /* esr_pa_tail on esr_op.conv (additive within ABI v12) */
     ESR_OP_ASYM_STEP = 19,      /* esr_asym_step on esr_op.conv (additive within ABI v12) */
     ESR_OP_PRELU = 20,          /* esr_prelu on esr_op.conv (additive within ABI v12) */
-    ESR_OP_RESDB_STEP = 21      /* esr_resdb_step on esr_op.conv (additive within ABI v12) */
+    ESR_OP_RESDB_STEP = 21,     /* esr_resdb_step on esr_op.conv (additive within ABI v12) */
+    ESR_OP_CONV_PRELU = 22,     /* esr_conv_prelu on esr_op.conv (additive within ABI v12) */
+    ESR_OP_MDSA_GATE = 23       /* esr_mdsa_gate on esr_op.conv (additive within ABI v12) */
 } esr_op_kind;
 
 /*
@@ -844,11 +846,67 @@ int    esr_prelu(const esr_conv_desc* d, void* hip_stream);
  */
 int    esr_resdb_step_supported(const esr_conv_desc* d);
 int    esr_resdb_step(const esr_conv_desc* d, void* hip_stream);
+/*
+ * esr_conv_prelu (additive within ABI v12; op kind ESR_OP_CONV_PRELU on esr_op.conv) -- a dense 64 -> 64 3x3 with a per-channel nn.PReLU BEHIND it,
+ * the layer MDGN's block is made of (models/team24_mdgn.py:8-10), as ONE launch on 16-bit storage (conv_prelu_kernel, csrc/esr_mdsa.hip):
+ *     v = b[c] + sum W[c,k,i,j] in[n, y+i-1, x+j-1, k]         fp32 accumulation from the bias on v_mfma_f32_16x16x32_{bf16,f16}; zero padding
+ *     out[c] = store(v >= 0 ? v : a[c] v)                      rounded ONCE (RNE) to the storage type
+ * The activation is an epilogue on the accumulators: a non-negative value is not multiplied at all, a negative one's product with the fp32 slope
+ * (any sign, any size: NOT max(v, a v)) is the exact product rounded once.  The weights live in the wave's registers, the input is staged by
+ * LDS-DMA in a ring of three 16 x 16 tiles with a one-pixel halo.  An esr_conv_desc carries it, no field added and no struct changed:
+ *     cin, cout            64, 64;  ksize 3, ESR_NHWC both;  act ESR_ACT_NONE, res_mode ESR_RES_NONE
+ *     in, out0             64 channels from coff each
+ *     storage, compute     BF16 / BF16 or F16 / F16
+ *     wpacked              esr_pack_conv_s16(W, b, 64, 64, ksize 3): the very blob the stand-alone launch multiplies by, error-diffused taps included
+ *     tail_wpacked         esr_pack_prelu(a, 64): 64 fp32 slopes
+ * Every other feature field (split, res, out1, tail_cat, tail_cat_c, tail_cout, tail_mid_act, tail_seg_stride16, post_*, post2_*, border_bias,
+ * blocked8, in_seg_*, wino_wpacked, hilo, hilo_stride) must be zero.  esr_conv_prelu_supported: 1 for such a descriptor with a per-image input
+ * below 1 GiB; esr_conv_prelu returns ESR_ERR_UNSUPPORTED for every other (fp32 storage and any other width included) and launches nothing.
+ * ESR_ERR_BAD_ARG for a null in / out0 / wpacked / tail_wpacked, for a view that is misaligned (pitch, coff: whole 16-byte granules) or does
+ * not hold its channels, and for an output whose bytes meet the input's (two views of one pixel grid meet where their channel ranges do,
+ * any other two wherever the n h w pitch elements behind their pointers do): the neighbouring tiles read `in` as halo.
+ */
+int    esr_conv_prelu_supported(const esr_conv_desc* d);
+int    esr_conv_prelu(const esr_conv_desc* d, void* hip_stream);
+/*
+ * esr_mdsa_gate (additive within ABI v12; op kind ESR_OP_MDSA_GATE on esr_op.conv) -- the end of MDGN's block (models/team24_mdgn.py:26-28) as ONE
+ * streaming launch on 16-bit storage (mdsa_gate_kernel, csrc/esr_mdsa.hip), with prelu(v, a) = v >= 0 ? v : a v per channel:
+ *     f[c] = prelu(b_f[c] + sum_k W_f[c,k] cat(f1, f2, f3)[k], a_f[c])      1x1, 192 -> 64, on the matrix cores: the stored f_i are the operands as
+ *                                                                          they are, the weights a hi + lo pair of 16-bit images (w = hi + lo),
+ *                                                                          fp32 accumulation from the bias
+ *     s    = 1 / (1 + exp(-(b_s + sum_k w_s[k] x[k])))                      fp32; ESR_RES_GATE's definition of the sigmoid
+ *     y[c] = store(f[c] s)                                                  the products are fp32 operations of their own; ONE rounding at the store
+ * f1, f2, f3 and x are read once, y is written once; cat(f1, f2, f3), the raw 1x1 result and f never reach memory.  An esr_conv_desc carries it,
+ * no field added and no struct changed:
+ *     cin, cout            192, 64;  ksize 1, ESR_NHWC both;  act ESR_ACT_NONE
+ *     in                   f1.  in_seg_stride != 0 (a multiple of 16) with in_seg_chunks == 4: f2 and f3 are dense tensors of `in`'s pitch and coff,
+ *                          in_seg_stride and twice in_seg_stride bytes behind it (64 channels from coff each); in_seg_stride == 0 (in_seg_chunks
+ *                          0): `in` is ONE view that holds the 192 channels one behind the other from coff
+ *     res, res_mode        x: 64 channels from coff, read only; ESR_RES_GATE
+ *     out0                 y: 64 channels from coff
+ *     storage, compute     BF16 / BF16 or F16 / F16
+ *     wpacked              esr_pack_mdsa_gate(W_f [64][192], b_f, a_f, w_s [64], b_s, storage)
+ * Every other feature field (split, out1, tail_*, post_*, post2_*, border_bias, blocked8, wino_wpacked, hilo, hilo_stride) must be zero.
+ * esr_mdsa_gate_supported: 1 for such a descriptor; esr_mdsa_gate returns ESR_ERR_UNSUPPORTED for every other (fp32 storage included) and
+ * launches nothing.  y is another tensor than f1 .. f3 and x: the n h w pitch elements behind out0.ptr may share no byte with those behind
+ * the sources' pointers -- ESR_ERR_BAD_ARG otherwise (a slice of a source's own tensor included), as for a null in / res / out0 / wpacked or
+ * a view that is misaligned or does not hold its channels (esr_pa_gate's rules).
+ * esr_pack_mdsa_gate (16-bit storage only; esr_packed_mdsa_gate_bytes(storage) bytes, 0 for fp32): [hi image | lo image | 64 fp32 b_f |
+ * 64 fp32 a_f | 64 fp32 w_s | fp32 b_s, 12 bytes of zeros]; an image = [cout tile 4][K step 6][lane 64][8] 16-bit values, lane (row, kq)
+ * element e of (mt, ks) = W_f[16 mt + row][32 ks + 8 kq + e]; hi = rnd(w), lo = rnd(w - hi).  b_f and b_s may be NULL (zeros).
+ * esr_unpack_mdsa_gate reads back the effective weights hi + lo [64][192] and the fp32 vectors (tests).
+ */
+size_t esr_packed_mdsa_gate_bytes(int storage);
+int    esr_pack_mdsa_gate(const float* w_f, const float* b_f, const float* a_f, const float* w_s, const float* b_s, int storage, void* out,
+                          size_t out_bytes);
+int    esr_unpack_mdsa_gate(const void* packed, size_t packed_bytes, int storage, float* w_f, float* b_f, float* a_f, float* w_s, float* b_s);
+int    esr_mdsa_gate_supported(const esr_conv_desc* d);
+int    esr_mdsa_gate(const esr_conv_desc* d, void* hip_stream);
 
 typedef struct esr_op {
     int32_t kind;               /* esr_op_kind */
     int32_t reserved;
-    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL, ESR_OP_ASYM_STEP, ESR_OP_PRELU, ESR_OP_RESDB_STEP */
+    esr_conv_desc conv;         /* ESR_OP_CONV, ESR_OP_DWCONV, ESR_OP_PACK_INPUT, ESR_OP_RESBLOCK_HEAD, ESR_OP_PA_GATE, ESR_OP_PA_TAIL, ESR_OP_ASYM_STEP, ESR_OP_PRELU, ESR_OP_RESDB_STEP, ESR_OP_CONV_PRELU, ESR_OP_MDSA_GATE */
     esr_esa_desc esa;           /* the four ESA kinds, ESR_OP_ESA_UNSHUFFLE */
     esr_bsconv_desc bs;         /* ESR_OP_BSCONV (ABI v3) */
     esr_esa_lowres_desc lo;     /* ESR_OP_ESA_LOWRES (ABI v7) */

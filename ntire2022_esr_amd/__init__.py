@@ -15,10 +15,11 @@ from .esan import ESAN  # noqa: F401
 from .fmen import FMEN  # noqa: F401
 from .frfdn import FasterRFDN  # noqa: F401
 from .imdn import IMDN  # noqa: F401
+from .mdgn import MDGN  # noqa: F401
 from .rfdn import RFDN  # noqa: F401
 from .repafdn import RePAFDN  # noqa: F401
 from .resdn import ResDN  # noqa: F401
 from .rfdnext import RFDNeXt  # noqa: F401
 from .rlfn import RLFN_cut  # noqa: F401
 
-__all__ = ["ARFDN", "BMDN", "BSRN", "DWRFDN", "ESAN", "FMEN", "FasterRFDN", "IMDN", "PLAINRFDN", "RFDN", "RFDNeXt", "RLFN_cut", "RePAFDN", "ResDN"]
+__all__ = ["ARFDN", "BMDN", "BSRN", "DWRFDN", "ESAN", "FMEN", "FasterRFDN", "IMDN", "MDGN", "PLAINRFDN", "RFDN", "RFDNeXt", "RLFN_cut", "RePAFDN", "ResDN"]

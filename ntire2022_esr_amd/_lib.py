@@ -33,6 +33,8 @@ OP_PA_TAIL = 18                                                           # ... 
 OP_ASYM_STEP = 19                                                         # ARFDN's asymmetric-convolution step (esr_asym_step on Op.conv)
 OP_PRELU = 20                                                             # ResDN's per-channel PReLU in front of a convolution (esr_prelu on Op.conv)
 OP_RESDB_STEP = 21                                                        # a ResDB step of ResDN in one launch (esr_resdb_step on Op.conv)
+OP_CONV_PRELU = 22                                                        # MDGN's 64 -> 64 3x3 with the PReLU in its epilogue (esr_conv_prelu on Op.conv)
+OP_MDSA_GATE = 23                                                         # the end of an MDSA block of MDGN in one launch (esr_mdsa_gate on Op.conv)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -161,6 +163,8 @@ EXPORTS = [
     "esr_packed_pa_gate_bytes", "esr_pack_pa_gate", "esr_pa_gate_supported", "esr_pa_gate", "esr_pa_tail_supported", "esr_pa_tail",
     "esr_packed_asym_s16_bytes", "esr_pack_asym_s16", "esr_unpack_asym_s16", "esr_asym_step_supported", "esr_asym_step",
     "esr_packed_prelu_bytes", "esr_pack_prelu", "esr_unpack_prelu", "esr_prelu_supported", "esr_prelu", "esr_resdb_step_supported", "esr_resdb_step",
+    "esr_conv_prelu_supported", "esr_conv_prelu", "esr_packed_mdsa_gate_bytes", "esr_pack_mdsa_gate", "esr_unpack_mdsa_gate", "esr_mdsa_gate_supported",
+    "esr_mdsa_gate",
     "esr_graph_create", "esr_graph_launch", "esr_graph_nodes", "esr_graph_destroy",
     "esr_event_pair_ms", "esr_bw_probe",
 ]
@@ -347,6 +351,20 @@ def lib():
     L.esr_resdb_step_supported.restype = ci
     L.esr_resdb_step.argtypes = [ctypes.POINTER(ConvDesc), vp]
     L.esr_resdb_step.restype = ci
+    L.esr_conv_prelu_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_conv_prelu_supported.restype = ci
+    L.esr_conv_prelu.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_conv_prelu.restype = ci
+    L.esr_packed_mdsa_gate_bytes.argtypes = [ci]
+    L.esr_packed_mdsa_gate_bytes.restype = sz
+    L.esr_pack_mdsa_gate.argtypes = [vp, vp, vp, vp, vp, ci, vp, sz]
+    L.esr_pack_mdsa_gate.restype = ci
+    L.esr_unpack_mdsa_gate.argtypes = [vp, sz, ci, vp, vp, vp, vp, vp]
+    L.esr_unpack_mdsa_gate.restype = ci
+    L.esr_mdsa_gate_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    L.esr_mdsa_gate_supported.restype = ci
+    L.esr_mdsa_gate.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.esr_mdsa_gate.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

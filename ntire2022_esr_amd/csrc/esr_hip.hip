@@ -1207,6 +1207,8 @@ static int run_one(const esr_op& op, void* hip_stream)
         case ESR_OP_ASYM_STEP: return esr_asym_step(&op.conv, hip_stream);
         case ESR_OP_PRELU: return esr_prelu(&op.conv, hip_stream);
         case ESR_OP_RESDB_STEP: return esr_resdb_step(&op.conv, hip_stream);
+        case ESR_OP_CONV_PRELU: return esr_conv_prelu(&op.conv, hip_stream);
+        case ESR_OP_MDSA_GATE: return esr_mdsa_gate(&op.conv, hip_stream);
         default: return ESR_ERR_BAD_ARG;
     }
 }

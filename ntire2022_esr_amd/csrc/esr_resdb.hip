@@ -40,26 +40,7 @@ struct PreluK {
     long long npix;
 };
 
-// fp64 -> bf16 (MB = 7, EB = 8) / fp16 (MB = 10, EB = 5), round to nearest even, ONE rounding: the value is scaled by a power of two so that
-// the storage type's step at its magnitude (the subnormal step below the smallest normal) is 1, and rounded to an integer by rint
-template <int MB, int EB>
-__device__ __forceinline__ unsigned prelu_round16(double x)
-{
-    constexpr int EMIN = 2 - (1 << (EB - 1));              // exponent of the smallest normal: -126 / -14
-    constexpr unsigned INF = ((1u << EB) - 1u) << MB;
-    const unsigned sign = x < 0.0 || (x == 0.0 && __builtin_signbit(x)) ? (1u << (MB + EB)) : 0u;
-    const double ax = fabs(x);
-    if (!(ax == ax)) return sign | INF | (1u << (MB - 1)); // NaN, quietened
-    if (ax == 0.0) return sign;
-    if (ax >= ldexp(1.0, 1 << (EB - 1))) return sign | INF;   // (also Inf)
-    const int e = ilogb(ax);
-    const int el = e < EMIN ? EMIN : e;
-    const unsigned r = (unsigned)rint(ldexp(ax, MB - el)); // 0 .. 2^(MB + 1): a carry into the next binade (or into the normals) lands on the right pattern
-    unsigned bits = e < EMIN ? r : (((unsigned)(el - EMIN + 1) << MB) + (r - (1u << MB)));
-    if (bits > INF) bits = INF;
-    return sign | bits;
-}
-
+// (prelu_round16 -- fp64 -> 16-bit with ONE rounding -- lives in esr_s16_dev.h: esr_mdsa.hip's epilogue rounds its products the same way)
 template <int ST>
 __device__ __forceinline__ unsigned prelu16(unsigned bits, float a)
 {

@@ -305,4 +305,80 @@ __device__ __forceinline__ i32x4 s16_swap16(uint2 X, uint2 Y)
     return i32x4{(int)a.x, (int)b.x, (int)a.y, (int)b.y};
 }
 
+// fp64 -> bf16 (MB = 7, EB = 8) / fp16 (MB = 10, EB = 5), round to nearest even, ONE rounding: the value is scaled by a power of two so that
+// the storage type's step at its magnitude (the subnormal step below the smallest normal) is 1, and rounded to an integer by rint
+// (esr_resdb.hip: prelu16; esr_mdsa.hip: prelu_store16 below)
+template <int MB, int EB>
+__device__ __forceinline__ unsigned prelu_round16(double x)
+{
+    constexpr int EMIN = 2 - (1 << (EB - 1));              // exponent of the smallest normal: -126 / -14
+    constexpr unsigned INF = ((1u << EB) - 1u) << MB;
+    const unsigned sign = x < 0.0 || (x == 0.0 && __builtin_signbit(x)) ? (1u << (MB + EB)) : 0u;
+    const double ax = fabs(x);
+    if (!(ax == ax)) return sign | INF | (1u << (MB - 1)); // NaN, quietened
+    if (ax == 0.0) return sign;
+    if (ax >= ldexp(1.0, 1 << (EB - 1))) return sign | INF;   // (also Inf)
+    const int e = ilogb(ax);
+    const int el = e < EMIN ? EMIN : e;
+    const unsigned r = (unsigned)rint(ldexp(ax, MB - el)); // 0 .. 2^(MB + 1): a carry into the next binade (or into the normals) lands on the right pattern
+    unsigned bits = e < EMIN ? r : (((unsigned)(el - EMIN + 1) << MB) + (r - (1u << MB)));
+    if (bits > INF) bits = INF;
+    return sign | bits;
+}
+
+// nn.PReLU on an fp32 ACCUMULATOR, stored: the 16-bit pattern of  v >= 0 ? v : a v  rounded ONCE (RNE) to the storage type.  A non-negative
+// value is not multiplied at all (-0 included); a negative one's product is the exact 48-bit product rounded once: p = RN(a v) and the exact
+// residual of one fma give the product rounded TO ODD in fp32, and rounding that to nearest even into a type with at least two bits less
+// equals rounding the exact product (esr_resdb.hip: prelu16, whose operand is a stored value).  The residual is exact while the product's
+// 48 bits lie above 2^-149: for |p| >= 2^-100; below that, and for a NaN or an Inf, fp64 holds the product exactly and prelu_round16 rounds it.
+template <bool BF16>
+__device__ __forceinline__ unsigned prelu_store16(float v, float a)
+{
+    float r = v;
+    if (!(v >= 0.f)) {
+        const float p = a * v;
+        const float ap = fabsf(p);
+        if (!(ap >= 0x1p-100f && ap < __builtin_inff())) {
+            const double pd = (double)a * (double)v;       // exact
+            return BF16 ? prelu_round16<7, 8>(pd) : prelu_round16<10, 5>(pd);
+        }
+        const float e = fmaf(a, v, -p);
+        unsigned pb = __builtin_bit_cast(unsigned, p);
+        if (e != 0.f) {
+            if ((e < 0.f) == (p > 0.f)) pb -= 1u;          // the exact product lies below |p|: its truncation is p's predecessor
+            pb |= 1u;
+        }
+        r = __builtin_bit_cast(float, pb);
+    }
+    if (BF16) return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)r);
+    return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)r);
+}
+
+// The same four stored values for one D fragment, with the common case first.  Rounding the fp32-ROUNDED product p = RN(a v) to the storage type
+// differs from rounding the exact product only where p lies exactly on a midpoint of the 16-bit grid: a midpoint is an fp32 number, so none
+// can lie strictly between the exact product and the fp32 number nearest to it.  In the normal range of the storage type that is one bit
+// pattern of p's low 16 (bf16) / 13 (fp16) bits.  A fragment with such a p, or with a value below the range in which that pattern and
+// prelu_store16's fma residual hold (2^-100 for bf16, fp16's smallest normal), takes prelu_store16 for its four values; every other one
+// costs a multiplication, a select and half a conversion per value.
+template <bool BF16>
+__device__ __forceinline__ uint2 prelu_store16x4(f32x4 v, f32x4 a)
+{
+    constexpr unsigned MASK = BF16 ? 0xffffu : 0x1fffu, HALF = BF16 ? 0x8000u : 0x1000u;
+    const float p0 = a.x * v.x, p1 = a.y * v.y, p2 = a.z * v.z, p3 = a.w * v.w;
+    const float r0 = v.x >= 0.f ? v.x : p0, r1 = v.y >= 0.f ? v.y : p1, r2 = v.z >= 0.f ? v.z : p2, r3 = v.w >= 0.f ? v.w : p3;
+    const unsigned t0 = (__builtin_bit_cast(unsigned, p0) & MASK) ^ HALF, t1 = (__builtin_bit_cast(unsigned, p1) & MASK) ^ HALF;
+    const unsigned t2 = (__builtin_bit_cast(unsigned, p2) & MASK) ^ HALF, t3 = (__builtin_bit_cast(unsigned, p3) & MASK) ^ HALF;
+    const unsigned tie = min(min(t0, t1), min(t2, t3));
+    const float small = fminf(fminf(fabsf(r0), fabsf(r1)), fminf(fabsf(r2), fabsf(r3)));
+    uint2 o;
+    if (tie == 0u || small < (BF16 ? 0x1p-100f : 0x1p-14f)) {
+        o.x = prelu_store16<BF16>(v.x, a.x) | (prelu_store16<BF16>(v.y, a.y) << 16);
+        o.y = prelu_store16<BF16>(v.z, a.z) | (prelu_store16<BF16>(v.w, a.w) << 16);
+    } else {
+        o.x = pack2<BF16>(r0, r1);
+        o.y = pack2<BF16>(r2, r3);
+    }
+    return o;
+}
+
 }  // namespace

@@ -376,6 +376,31 @@ def unpack_prelu(blob, c):
     return a
 
 
+def pack_mdsa_gate(w_f, b_f, a_f, w_s, b_s, store):
+    """The end of an MDSA block for esr_mdsa_gate: conv_fuse.0 [64, 192(, 1, 1)] as a hi + lo pair of 16-bit images (w = hi + lo), then its
+    bias, conv_fuse.1's 64 slopes, sa.0's weight [1, 64(, 1, 1)] and bias in fp32, never rounded (esr_pack_mdsa_gate; 16-bit storage only)."""
+    lib = L.lib()
+    wf, ws = _host(w_f), _host(w_s)
+    wf, ws = wf.reshape(wf.shape[0], -1), ws.reshape(-1)
+    bf, af, bs = (None if b_f is None else _host(b_f).reshape(-1)), _host(a_f).reshape(-1), (None if b_s is None else _host(b_s).reshape(-1))
+    nbytes = lib.esr_packed_mdsa_gate_bytes(L.STORE[store])
+    if not nbytes or tuple(wf.shape) != (64, 192) or ws.numel() != 64 or af.numel() != 64 or (bf is not None and bf.numel() != 64) or \
+            (bs is not None and bs.numel() != 1):
+        raise L.EsrError("pack_mdsa_gate: W_f [64, 192], b_f [64], a_f [64], w_s [64], b_s [1] in 16-bit storage")
+    out = torch.empty(nbytes // 4, dtype=torch.float32)
+    L.check(lib.esr_pack_mdsa_gate(_ptr(wf), _ptr(bf), _ptr(af), _ptr(ws), _ptr(bs), L.STORE[store], _ptr(out), nbytes), "esr_pack_mdsa_gate")
+    return out
+
+
+def unpack_mdsa_gate(blob, store):
+    """EFFECTIVE (W_f [64, 192] = hi + lo, b_f [64], a_f [64], w_s [64], b_s [1]) of a pack_mdsa_gate blob, fp32 (tests)"""
+    blob = _host(blob)
+    wf, bf, af, ws, bs = torch.zeros(64, 192), torch.zeros(64), torch.zeros(64), torch.zeros(64), torch.zeros(1)
+    L.check(L.lib().esr_unpack_mdsa_gate(_ptr(blob), blob.numel() * 4, L.STORE[store], _ptr(wf), _ptr(bf), _ptr(af), _ptr(ws), _ptr(bs)),
+            "esr_unpack_mdsa_gate")
+    return wf, bf, af, ws, bs
+
+
 def pack_unshuffle(weight, bias):
     """`con_` of team 35's ESA, nn.Conv2d(4 f, f, 1, padding 1), for esr_esa_unshuffle_f32: the esr_pack_dense_f32 blob [4 f][16] + bias[16]
     (the pad outputs f .. 15: zero columns, zero bias)."""
@@ -518,6 +543,7 @@ PAG = "#pag"       # pack_pa_gate image of a pixel attention's 1x1 in the plan's
 ASYM = "#asym"     # pack_asym_s16 image of an ARFDB step's four 3-tap convolutions, under the name of c{j}_l1 (AsymStep)
 RSTEP = "#step"    # pack_prelu image of a ResDB step's slopes, cat(a_e, a_c), under the name of the expansion's nn.PReLU (ResdbStep)
 PRELU = "#prelu"   # pack_prelu image of the slopes in front of a convolution, under the name of the nn.PReLU (Prelu)
+MGATE = "#mgate"   # pack_mdsa_gate image of the end of an MDSA block, under the name of the fuse 1x1 conv_fuse.0 (MdsaGate)
 FOLD = "#fold"     # pack_distill_s16 image of a distillation step's two 3x3s, under the name of the one over the step's input (Distill)
 
 
@@ -1529,6 +1555,92 @@ class ResdbStep(_Fused):
 
 
 @dataclass
+class ConvPrelu(_Fused):
+    """A dense 64 -> 64 3x3 and the per-channel PReLU behind it as ONE esr_conv_prelu op -- see Plan.conv_prelu (conv_prelu_kernel).
+    replaces: [conv, prelu]."""
+    kind = "convprelu"
+    predicate, field, what = "esr_conv_prelu_supported", "conv", "conv + PReLU"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 2 and [o.kind for o in sub] == ["conv", "prelu"]
+        cv, pl = sub
+        assert cv.k == 3 and cv.act == L.ACT_NONE and cv.res is None and cv.post is None and cv.tail is None and not cv.hilo and cv.hw is None
+        assert cv.dst1 is None and cv.border is None and not cv.split and not isinstance(cv.src, (str, Planar)) and cv.cin_alg == cv.cin
+        assert len(pl.srcs) == 1 and _same_view(pl.srcs[0][0], cv.dst) and pl.c == cv.cout      # the PReLU reads what the 3x3 stores ...
+        assert not _same_view(pl.dst, cv.src)                                                    # ... and the result is another tensor than the input
+
+    def encode(self, op, plan, base, weights):
+        cv, pl = self.replaces
+        op.kind = L.OP_CONV_PRELU
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        d.cin, d.cout, d.ksize = cv.cin, cv.cout, 3
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = L.STORE[plan.store]
+        d.inp, d.out0 = _view(cv.src, base), _view(pl.dst, base)
+        d.wpacked = ctypes.c_void_p(weights[cv.w + S16].data_ptr())
+        d.tail_wpacked = ctypes.c_void_p(weights[pl.w + PRELU].data_ptr())
+
+    def cost(self, plan, desc):             # the input read once, the activated result written once; the raw result never exists
+        cv, pl = self.replaces
+        npix, es, c = plan.npix, plan.esize, cv.cout
+        wb = 4.0 * (9 * cv.cin * c + 2 * c)
+        rd, wr = float(npix * es * cv.cin) + wb, float(npix * es * c)
+        ntiles = plan.n * ((plan.h + 15) // 16) * ((plan.w + 15) // 16)
+        fexec = 2.0 * ntiles * 256 * 10 * cv.cin * c       # five tap pairs (ten tap slots) per chunk on whole 16 x 16 tiles
+        return _cost(cv.w, f"conv_prelu_kernel<{_tf(plan.store == 'bf16')}>", cv.cin, c, 3, 2.0 * npix * 9 * cv.cin * c + npix * c, rd, wr, rd + wr, fexec)
+
+
+@dataclass
+class MdsaGate(_Fused):
+    """The end of an MDSA block as ONE esr_mdsa_gate op -- see Plan.mdsa_gate (mdsa_gate_kernel).  replaces: [the fuse 1x1 over
+    cat(f1, f2, f3), its PReLU, the replicated one-channel gate (a 1x1 of x with res_mode L.RES_GATE on the PReLU's result)]."""
+    kind = "mdsagate"
+    predicate, field, what = "esr_mdsa_gate_supported", "conv", "MDSA gate"
+
+    def check(self):
+        sub = self.replaces
+        assert len(sub) == 3 and [o.kind for o in sub] == ["conv", "prelu", "conv"]
+        cf, pl, gt = sub
+        assert all(o.act == L.ACT_NONE and o.post is None and o.tail is None and not o.hilo and o.hw is None and o.dst1 is None and o.border is None
+                   for o in (cf, gt))
+        assert cf.k == 1 and gt.k == 1 and cf.res is None and cf.cin_alg == cf.cin and gt.cin == gt.cout == cf.cout == pl.c
+        assert len(pl.srcs) == 1 and _same_view(pl.srcs[0][0], cf.dst)                           # the PReLU reads what the 1x1 stores ...
+        assert gt.res_mode == L.RES_GATE and _same_view(gt.res, pl.dst)                          # ... and the gate multiplies its result
+        assert not isinstance(gt.src, (str, Planar)) and not isinstance(gt.dst, (str, Planar))
+
+    def name(self):
+        """the fuse 1x1's name, under which `<name>#mgate` is packed"""
+        return self.replaces[0].w
+
+    def encode(self, op, plan, base, weights):
+        cf, pl, gt = self.replaces
+        op.kind = L.OP_MDSA_GATE
+        d = op.conv
+        d.n, d.h, d.w = plan.n, plan.h, plan.w
+        d.cin, d.cout, d.ksize = cf.cin, cf.cout, 1
+        d.in_layout = d.out_layout = L.NHWC
+        d.storage = d.compute = L.STORE[plan.store]
+        if isinstance(cf.src, Planar):
+            d.inp = _view(cf.src.seg(0), base)
+            d.in_seg_stride, d.in_seg_chunks = cf.src.stride, (cf.src.pitch + 15) // 16
+        else:
+            d.inp = _view(cf.src, base)
+        d.res, d.res_mode = _view(gt.src, base), L.RES_GATE                                      # x: the gate's operand
+        d.out0 = _view(gt.dst, base)
+        d.wpacked = ctypes.c_void_p(weights[self.name() + MGATE].data_ptr())
+
+    def cost(self, plan, desc):             # f1, f2, f3 and x read once, y written once; the raw 1x1 result and f never exist
+        cf, pl, gt = self.replaces
+        npix, es, c = plan.npix, plan.esize, cf.cout
+        wb = 4.0 * (cf.cin * c + 3 * c + 1)
+        rd, wr = float(npix * es * (cf.cin + c)) + wb, float(npix * es * c)
+        flops = 2.0 * npix * (cf.cin * c + c) + 2.0 * npix * c
+        return _cost(self.name(), f"mdsa_gate_kernel<{_tf(plan.store == 'bf16')}>", cf.cin, c, 1, flops, rd, wr, rd + wr, 2.0 * 2.0 * npix * cf.cin * c)
+
+
+@dataclass
 class PaTail(_Fused):
     """A 3x3 and the pixel attention behind it as ONE esr_pa_tail op -- see Plan.pa_tail (pa_tail_kernel).  replaces: [conv, pagate]."""
     kind = "patail"
@@ -1880,6 +1992,23 @@ class Plan:
         the fp32 sums.  x' must not be stored into x's tensor."""
         return self._fuse(mark, ResdbStep)
 
+    def conv_prelu(self, mark):
+        """The two ops appended since `mark = len(plan.ops)` -- a dense 64 -> 64 3x3 and the per-channel PReLU of its result, raw = conv(x),
+        f = prelu(raw, a) (mdgn.py; team24_mdgn.py:8-10) -- as ONE esr_conv_prelu op (16-bit plans): x is read once, f is written once, raw stays
+        in the accumulators.  The ops stay attached as `replaces`: complexity counters and algorithmic costs are theirs; the blobs are the
+        3x3's esr_pack_conv_s16 image and the PReLU's pack_prelu slopes, as the two launches read them.  Not bit-identical to the two launches,
+        which round raw once in between: here the activation meets the fp32 sum and the result is rounded once.  f must not be stored into
+        x's tensor."""
+        return self._fuse(mark, ConvPrelu)
+
+    def mdsa_gate(self, mark):
+        """The three ops appended since `mark = len(plan.ops)` -- the end of an MDSA block in its per-layer form, raw = W_f . cat(f1, f2, f3),
+        t = prelu(raw, a_f), y = sigmoid(w_s . x) * t (mdgn.py; team24_mdgn.py:26-28) -- as ONE esr_mdsa_gate op (16-bit plans): f1, f2, f3 and x
+        are read once, y is written once, raw and t never exist.  The ops stay attached as `replaces`: complexity counters and algorithmic
+        costs are theirs; the blob is pack_mdsa_gate's (`<conv_fuse.0>#mgate`).  Not bit-identical to the three launches, which round raw and
+        t: here one rounding, at the store.  y must not be stored into a source's tensor."""
+        return self._fuse(mark, MdsaGate)
+
     def pa_tail(self, mark):
         """The two ops appended since `mark = len(plan.ops)` -- a plain 3x3 and the pixel attention that reads its result, t = conv(x),
         y = t * sigmoid(W . t + b) (+ s) (team10_repafdn/repafdn.py:55-57) -- as ONE esr_pa_tail op (16-bit plans): x (and s) are read once, y
@@ -2044,6 +2173,8 @@ class HipSRModel(nn.Module):
         self._fuse_pa_tail = False # 16-bit RePAFDN plans: LR_conv and the pixel attention behind it as one esr_pa_tail launch (Plan.pa_tail); OFF: 2 % slower than the two launches at 32 x 256 x 256 and on one image
         self._fuse_asym = True     # 16-bit ARFDN plans: an ARFDB step as one esr_asym_step launch (Plan.asym_step); measured: DESIGN.md 7k
         self._fuse_resdb = False   # 16-bit ResDN plans: a ResDB step as one esr_resdb_step launch (Plan.resdb_step); OFF: 1.8x slower than the five launches at 32 x 256 x 256, 1.5x on one image
+        self._fuse_conv_prelu = True   # 16-bit MDGN plans: a 3x3 and the PReLU behind it as one esr_conv_prelu launch (Plan.conv_prelu); ON: 1.3 .. 1.5 % faster than the two launches at 32 x 256 x 256 (repeat spread 0.6 %), 5 .. 6 % on one image; next to fuse_mdsa_gate 1.4 % / 0.1 % (f16: inside the spread) and 9 %
+        self._fuse_mdsa_gate = True    # 16-bit MDGN plans: the fuse 1x1, its PReLU and the sigmoid gate as one esr_mdsa_gate launch (Plan.mdsa_gate); ON: 21 % faster than the three launches at 32 x 256 x 256, 29 % on one image
         self._fuse_cx = True       # 16-bit RFDNeXt plans: the ConvNeXt block as one esr_cx_block_s16 launch (Plan.cx_block); measured: DESIGN.md 7g
         self.use_graphs = True     # forwards of at most GRAPH_MAX_PIXELS input pixels replay a captured HIP graph (esr_graph_launch)
         self._lock = _ModelLock()       # plan / workspace bookkeeping and the pointer patch + enqueue of one forward (see _forward_impl)
@@ -2123,6 +2254,8 @@ class HipSRModel(nn.Module):
     fuse_pair = property(lambda self: self._fuse_pair, lambda self, v: self._set_flag("_fuse_pair", v))
     fuse_resdb = property(lambda self: self._fuse_resdb, lambda self, v: self._set_flag("_fuse_resdb", v))
     fuse_asym = property(lambda self: self._fuse_asym, lambda self, v: self._set_flag("_fuse_asym", v))
+    fuse_conv_prelu = property(lambda self: self._fuse_conv_prelu, lambda self, v: self._set_flag("_fuse_conv_prelu", v))
+    fuse_mdsa_gate = property(lambda self: self._fuse_mdsa_gate, lambda self, v: self._set_flag("_fuse_mdsa_gate", v))
 
     def _skip_hilo(self, plan, c):
         """bf16 plans: keep the long skip `upsampler(LR_conv(body) + fea)` in hi + lo pairs?  (c = its channel count; the hi + lo kernels

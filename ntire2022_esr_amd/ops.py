@@ -7,8 +7,8 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .engine import (pack_asym_s16, pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_pa_gate, pack_post_s16,
-                     pack_prelu, pack_unshuffle, pack_wino)
+from .engine import (pack_asym_s16, pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_mdsa_gate, pack_pa_gate,
+                     pack_post_s16, pack_prelu, pack_unshuffle, pack_wino)
 
 
 def _view(t, coff=0):
@@ -455,6 +455,61 @@ def resdb_step(x, a_e, w_e, b_e, a_c, w_c, b_c, *, extras=(), x_coff=0, d_out=No
     stream = torch.cuda.current_stream(x.device).cuda_stream
     _launch("esr_resdb_step", "esr_resdb_step", d, stream, L.OP_RESDB_STEP, "conv")
     return dd, y
+
+
+def conv_prelu(x, w, b, a, *, x_coff=0, out=None, out_coff=0):
+    """esr_conv_prelu: a dense 64 -> 64 3x3 (zero padding) with the per-channel nn.PReLU behind it in ONE launch on 16-bit NHWC tensors:
+    y[c] = prelu(conv3x3(x, w)[c] + b[c], a[c]) with prelu(v, a) = v >= 0 ? v : a v, fp32 accumulation, rounded once to x's dtype.  x: [N, H, W, P]
+    whose 64 channels from x_coff are read; w: [64, 64, 3, 3], packed as the stand-alone convolution packs it; a: 64 fp32 slopes of any sign
+    and size.  out: a caller-provided NHWC tensor that receives y from channel out_coff and shares no byte with x's channels; default:
+    freshly allocated zeros.  Returns y."""
+    st = _s16_store(x, "conv_prelu")
+    n, h, wd, _ = x.shape
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.ksize, d.cin, d.cout = n, h, wd, 3, w.shape[1], w.shape[0]
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = d.compute = L.STORE[st]
+    d.inp = _view(x, x_coff)
+    if not L.lib().esr_conv_prelu_supported(ctypes.byref(d)) or tuple(w.shape) != (64, 64, 3, 3) or a.numel() != 64:
+        raise L.EsrError("conv_prelu: no kernel for this shape (esr_conv_prelu_supported: 64 -> 64, 3x3, 16-bit storage)")
+    keep = [pack_conv_s16(w, b, st).to(x.device), pack_prelu(a).to(x.device)]
+    d.wpacked, d.tail_wpacked = keep[0].data_ptr(), keep[1].data_ptr()
+    y = _zeros_or(out, "conv_prelu: out", x, (n, h, wd), 64, 8)
+    d.out0 = _view(y, out_coff)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_conv_prelu", "esr_conv_prelu", d, stream, L.OP_CONV_PRELU, "conv")
+    return y
+
+
+def mdsa_gate(f, x, w_f, b_f, a_f, w_s, b_s, *, f_coff=0, x_coff=0, out=None, out_coff=0):
+    """esr_mdsa_gate: the end of an MDSA block (team24_mdgn.py:26-28) in ONE streaming launch on 16-bit NHWC tensors:
+    y = prelu(w_f . cat(f1, f2, f3) + b_f, a_f) * sigmoid(w_s . x + b_s), the weights of the 192 -> 64 1x1 as hi + lo pairs, everything else
+    fp32, one rounding to the tensors' dtype.  f: ONE tensor [N, H, W, P] whose 192 channels from f_coff are cat(f1, f2, f3), or a stacked
+    tensor [3, N, H, W, P] whose three dense tensors hold f1, f2, f3 in their 64 channels from f_coff (what a plan's planar concat is).
+    x: [N, H, W, Q], 64 channels from x_coff.  out: a caller-provided NHWC tensor that receives y from channel out_coff, another tensor than
+    f and x; default: freshly allocated zeros.  Returns y."""
+    st = _s16_store(x, "mdsa_gate")
+    n, h, w, _ = x.shape
+    planar = f.dim() == 5
+    if not f.is_cuda or f.dtype != x.dtype or not f.is_contiguous() or not x.is_contiguous() or tuple(f.shape[-4:-1]) != (n, h, w) or (planar and f.shape[0] != 3):
+        raise L.EsrError("mdsa_gate: f [N, H, W, P] or [3, N, H, W, P] and x [N, H, W, Q], contiguous, one dtype and device")
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.ksize, d.cin, d.cout = n, h, w, 1, 192, 64
+    d.in_layout = d.out_layout = L.NHWC
+    d.storage = d.compute = L.STORE[st]
+    d.res_mode = L.RES_GATE
+    d.inp, d.res = _view(f, f_coff), _view(x, x_coff)
+    if planar:
+        d.in_seg_stride, d.in_seg_chunks = f.stride(0) * f.element_size(), 4
+    keep = pack_mdsa_gate(w_f, b_f, a_f, w_s, b_s, st).to(x.device)
+    d.wpacked = keep.data_ptr()
+    if not L.lib().esr_mdsa_gate_supported(ctypes.byref(d)):
+        raise L.EsrError("mdsa_gate: esr_mdsa_gate does not take this descriptor (esr_mdsa_gate_supported)")
+    y = _zeros_or(out, "mdsa_gate: out", x, (n, h, w), 64, 8)
+    d.out0 = _view(y, out_coff)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _launch("esr_mdsa_gate", "esr_mdsa_gate", d, stream, L.OP_MDSA_GATE, "conv")
+    return y
 
 
 def resblock_head(x, w1, b1, w2, b2, wc, bc, *, g=None, in_coff=0, g_coff=0, x_out=None, x_coff=0, u_out=None, u_coff=0,

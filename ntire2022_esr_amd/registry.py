@@ -40,9 +40,11 @@ def _more_entries():
     checkpoints live with the tests (tests/golden/<ckpt>_f32.safetensors, the unrounded tensors), so supported_ids() -- the ids whose
     exported weights ship in weights/ -- does not list them."""
     from .arfdn import ARFDN
+    from .mdgn import MDGN
     from .resdn import ResDN
     return {
         14: ("ARFDN", "team14_arfdn", 1.0, None, lambda: ARFDN()),                             # test_demo.py:118-128
+        24: ("MDGN", "team24_mdgn", 255.0, None, lambda: MDGN()),                               # test_demo.py:189-195
         43: ("ResDN", "team43_resdn", 1.0, None, lambda: ResDN(upscale_factor=4, in_channels=3, n_feats=48, out_channels=3)),   # test_demo.py:318-324
     }
 
@@ -64,9 +66,10 @@ def load_checkpoint(stem, model_zoo=None):
     for p in (os.path.join(_REPO, "weights", stem + ".safetensors"), os.path.join(_REPO, "tests", "golden", stem + "_f32.safetensors")):
         if os.path.exists(p):
             sd = load_file(p)
-            p2 = p[:-len(".safetensors")] + ".part2.safetensors"                     # (a fixture checkpoint above the file size limit: two files)
-            if os.path.exists(p2):
-                sd.update(load_file(p2))
+            k = 2                                                                    # (a fixture checkpoint above the file size limit: .part2, .part3, ...)
+            while os.path.exists(p[:-len(".safetensors")] + f".part{k}.safetensors"):
+                sd.update(load_file(p[:-len(".safetensors")] + f".part{k}.safetensors"))
+                k += 1
             return sd
     raise FileNotFoundError(f"no checkpoint for {stem}: pass model_zoo")
 

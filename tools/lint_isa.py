@@ -23,6 +23,8 @@ Rule 4 -- conv64m_kernel, rfdb_tail_kernel (esr_c64m.hip), rlfb_chain_kernel (es
     And for asym_step_kernel (esr_asym.hip): the 24 / 36 fragments of its four 3-tap convolutions likewise, next to an LDS-DMA stage.
     And for prelu_kernel (esr_resdb.hip): the channels a thread gathers one by one stay in registers (a streaming kernel that spills moves its bytes twice);
     and for resdb_step_kernel: its nine accumulators and the activated B fragment stay in registers (276 .. 284 VGPRs).
+    And for conv_prelu_kernel (esr_mdsa.hip): its 80 weight fragments, 16 accumulators and 16 slopes fill the 512 registers of a wave next to a counted
+    LDS-DMA ring; and for mdsa_gate_kernel: the six B fragments and the slopes stay in registers.
 Rule 5 -- rlfb_chain_kernel: the post wave's counted wait (PIECES + STORES) (D - 2) + STORES is in the code, and between two barriers
     of the step loop there are exactly PIECES LDS-DMA loads and exactly STORES stores (ChGeo<G>): an extra vector-memory instruction would loosen it.
 Rule 2 -- conv_s16_kernel's wait-count arithmetic (tools/lint_s16_isa.py, unchanged): no scratch / spills, no copies out of registers an
@@ -127,7 +129,8 @@ def lint_prologues(path, unit):
                 (unit == "esr_distill.hip" and "distill_step_kernel" in name) or (unit == "esr_esan.hip" and "resblock_head_kernel" in name) or \
                 (unit == "esr_cascade.hip" and "refine_cascade_kernel" in name) or (unit == "esr_cx.hip" and "cx_block_kernel" in name) or \
                 (unit == "esr_dwpw.hip" and "dwpw_pair_kernel" in name) or (unit == "esr_pa.hip" and ("pa_tail_kernel" in name or "pa_gate_kernel" in name)) or \
-                (unit == "esr_asym.hip" and "asym_step_kernel" in name) or (unit == "esr_resdb.hip" and ("prelu_kernel" in name or "resdb_step_kernel" in name)):
+                (unit == "esr_asym.hip" and "asym_step_kernel" in name) or (unit == "esr_resdb.hip" and ("prelu_kernel" in name or "resdb_step_kernel" in name)) or \
+                (unit == "esr_mdsa.hip" and ("conv_prelu_kernel" in name or "mdsa_gate_kernel" in name)):
             bad = [t for t in ins if t.startswith(("scratch_", "s_set_gpr_idx", "s_movrel", "v_movrel"))]
             if bad:
                 problems.append(f"{unit}: {name}: {len(bad)} scratch / dynamic register index instruction(s), first: {bad[0]}")
