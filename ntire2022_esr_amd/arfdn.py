@@ -38,7 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import ASYM, S16, HipSRModel, Post, Conv, pack_asym_s16, pack_conv, pack_conv_s16
+from .engine import S16, HipSRModel, Post, Conv, pack_conv, pack_conv_s16
 from .frame import FP, Concat, EsaBranch, LongSkip, _pad8, _slice_map, block_cin_map, check_input, set_scale
 
 SEG = 32                                                   # slice width of the block's maps
@@ -86,7 +86,7 @@ class ARFDN(HipSRModel):
             for j in (1, 2, 3):
                 cin = nf if j == 1 else dc
                 self._add_conv(b + f'c{j - 1}_d', cin, dc, 1)
-                # the asymmetric pairs: parameter holders with the reference's shapes, packed by _extra_pack
+                # the asymmetric pairs: parameter holders with the reference's shapes, folded by _extra_pack; as they are: Plan.asym_step
                 self._add_leaf(b + f'c{j}_l1', nn.Conv2d(cin, dc, (3, 1), 1, (1, 0)))
                 self._add_leaf(b + f'c{j}_l2', nn.Conv2d(dc, dc, (1, 3), 1, (0, 1)))
                 self._add_leaf(b + f'c{j}_m1', nn.Conv2d(cin, dc, (1, 3), 1, (0, 1)))
@@ -149,7 +149,7 @@ class ARFDN(HipSRModel):
                 plan.conv(b + f'c{j}_l1' + FOLD_A, r, S[A:A + 2 * SEG], cin, 2 * dc, counted=False, **act)
                 plan.conv(b + f'c{j}_l2' + FOLD_B, S[lo:hi], out, hi - lo, dc, counted=False, **res, **act)
                 # (where the kernel takes the step; else the three launches stay)
-                fused = self.fuse_asym and s16 and plan.asym_step(mark, p=[S[s:s + SEG] for s in ps])
+                fused = self.fuse_asym and s16 and plan.asym_step(mark, [b + f'c{j}_{n}' for n in ('l1', 'm1', 'l2', 'm2')], p=[S[s:s + SEG] for s in ps])
                 if s16 and j == 3 and not fused:                                      # 160 slots: q = d_2 + d_1 first (_step)
                     _, _, (lo, hi), _ = self._step(j, True)
                     del plan.ops[-1]
@@ -184,16 +184,12 @@ class ARFDN(HipSRModel):
                 wa, ba = fold_a(cpu(l1.weight), cpu(l1.bias), cpu(m1.weight), cpu(m1.bias))
                 fb = lambda s16: fold_b(cpu(l2.weight), cpu(l2.bias), cpu(m2.weight), cpu(m2.bias), self._step(j, s16)[2][1] - self._step(j, s16)[2][0],
                                         A - self._step(j, s16)[2][0], [s - self._step(j, s16)[2][0] for s in self._step(j, s16)[3]])
-                wb, bb = fb(False)
-                packed[b + 'l1' + FOLD_A] = pack_conv(wa, ba).to(device)
-                packed[b + 'l2' + FOLD_B] = pack_conv(wb, bb).to(device)
+                self._pack_own(packed, device, b + 'l1' + FOLD_A, wa, ba)
+                packed[b + 'l2' + FOLD_B] = pack_conv(*fb(False)).to(device)
                 if store != "f32":
-                    packed[b + 'l1' + FOLD_A + S16] = pack_conv_s16(wa, ba, store).to(device)
                     packed[b + 'l2' + FOLD_B + S16] = pack_conv_s16(*fb(True), store).to(device)
                     if j == 3:
                         packed[b + 'l2' + FOLD_Q + S16] = pack_conv_s16(torch.eye(self.dc)[:, :, None, None], torch.zeros(self.dc), store).to(device)
-                    if self.fuse_asym:
-                        packed[b + 'l1' + ASYM] = pack_asym_s16(*(cpu(t) for m in (l1, m1, l2, m2) for t in (m.weight, m.bias)), store).to(device)
 
     def _complexity_terms(self, plan, o):
         """the folded 3x3s stand for two nn.Conv2d calls of three taps each (block.py:236-254); the activation of a step's sum is a call of

@@ -23,7 +23,7 @@ Which form a plan takes depends on the per-image shape and esr_distill_step_supp
 The long skip (team37_bmdn.py:214), the concats and ESA's low-resolution branch are the shared frame's (frame.py).
 """
 from . import _lib as L
-from .engine import FOLD, HipSRModel, Post
+from .engine import HipSRModel, Post
 from .frame import FP, Concat, EsaBranch, LongSkip, _pad8, _slice_map, block_cin_map, check_input, set_scale
 
 
@@ -112,11 +112,3 @@ class BMDN(HipSRModel):
         skip.close('LR_conv', 'upsampler.0', v, lr, self.out_nc * 16)
 
     _cin_map = block_cin_map
-
-    def _extra_pack(self, packed, device):
-        if self._store() != "f32" and self.fuse_step:
-            from .engine import pack_distill_s16     # c{j}_r and c{j}_b as one 3x3 over cat[r, d_j] (esr_distill_step_s16)
-            for k in range(1, 5):
-                for j in (1, 2, 3):
-                    cr, cb = self._leaf(f'B{k}.c{j}_r'), self._leaf(f'B{k}.c{j}_b')
-                    packed[f'B{k}.c{j}_r' + FOLD] = pack_distill_s16(cr.weight, cr.bias, cb.weight, cb.bias, self._store()).to(device)

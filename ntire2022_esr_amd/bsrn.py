@@ -127,14 +127,12 @@ class BSRN(HipSRModel):
             packed['fea_conv#bs3#border'] = table.to(device)
         for k in range(1, self.nb + 1):
             co = self._leaf(f'B{k}.conv_out')
-            cw = self._leaf(f'B{k}').cw.detach().float().reshape(1, C)
-            packed[f'B{k}.conv_out'] = pack_conv(co.weight.detach().float() * cw, co.bias).to(device)
-            if self._store() != "f32":
-                packed[f'B{k}.conv_out#s16'] = pack_conv_s16(co.weight.detach().float() * cw, co.bias, self._store()).to(device)
-                if L.lib().esr_esa_apply_post_supported(C, C, self.dc):      # the chain of the ESA apply launch (engine.Plan.esa_apply)
-                    nd = self._leaf(f'B{k + 1}.c1_d') if k < self.nb else None
-                    packed[f'B{k}.conv_out#apost'] = pack_apply_post(co.weight.detach().float() * cw, co.bias, None if nd is None else nd.weight,
-                                                                     None if nd is None else nd.bias, self._store()).to(device)
+            w = co.weight.detach().float() * self._leaf(f'B{k}').cw.detach().float().reshape(1, C)
+            self._pack_own(packed, device, f'B{k}.conv_out', w, co.bias)
+            if self._store() != "f32" and L.lib().esr_esa_apply_post_supported(C, C, self.dc):      # the chain of the ESA apply launch (engine.Plan.esa_apply)
+                nd = self._leaf(f'B{k + 1}.c1_d') if k < self.nb else None
+                packed[f'B{k}.conv_out#apost'] = pack_apply_post(w, co.bias, None if nd is None else nd.weight, None if nd is None else nd.bias,
+                                                                 self._store()).to(device)
 
     def _build_plan(self, plan, c):
         check_input('BSRN', plan, c, self.in_nc)

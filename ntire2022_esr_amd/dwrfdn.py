@@ -31,7 +31,7 @@ the block outputs as four 56-wide tensors read by c.0, the long skip as a hi + l
 (rfdn.py:38) and the two concats are the shared frame's (frame.py).
 """
 from . import _lib as L
-from .engine import DWPW, HipSRModel, Post, pack_dwpw_pw, pack_unshuffle
+from .engine import HipSRModel, Post
 from .frame import FP, Concat, LongSkip, _pad8, _slice_map, block_cin_map, check_input, set_scale
 
 
@@ -65,7 +65,7 @@ class DWRFDN(HipSRModel):
             self._add_conv(b + 'esa.conv1', nf, f, 1)
             self._add_conv(b + 'esa.conv_f', f, f, 1, dense=(FP, FP))
             self._add_conv(b + 'esa.conv_max', f, f, 3)                               # never launched (rmsrb1.py:137-150 does not call it)
-            self._add_conv(b + 'esa.con_', 4 * f, f, 1, padding=1, custom=True)       # packed by _extra_pack (pack_unshuffle)
+            self._add_conv(b + 'esa.con_', 4 * f, f, 1, padding=1, custom=True)       # packed for Plan.esa_unshuffle (pack_unshuffle)
             self._add_conv(b + 'esa.conv4', f, nf, 1, dense=(FP, cp4))
         self._add_conv('c.0', nf * num_modules, nf, 1, cin_map=_slice_map(num_modules, nf, _pad8(nf)))
         self._add_conv('LR_conv', nf, nf, 3)
@@ -132,18 +132,6 @@ class DWRFDN(HipSRModel):
         skip.close('LR_conv', 'upsampler.0', v, r1, self.out_nc * 16)
 
     _cin_map = block_cin_map
-
-    def _extra_pack(self, packed, device):
-        store = self._store()
-        for k in range(1, 5):
-            b = f'B{k}.'
-            leaf = self._leaf(b + 'esa.con_')
-            packed[b + 'esa.con_'] = pack_unshuffle(leaf.weight, leaf.bias).to(device)
-            if store != "f32":
-                for j in (1, 2, 3):
-                    for half in (0, 2):
-                        leaf = self._leaf(b + f'c{j}_r.{half}.1')
-                        packed[b + f'c{j}_r.{half}.1' + DWPW] = pack_dwpw_pw(leaf.weight, leaf.bias, store).to(device)
 
     def _counted_convs(self, plan, o):
         """the depthwise layers are nn.Conv2d calls of their own here (Dw counts nothing by itself: BSRN's ride in its BSConvU counts); an

@@ -12,7 +12,7 @@ frame's (frame.py); the stride-7 ESA branch and its maps are this file's.
 """
 from . import _lib as L
 from .engine import EsaLayer, HipSRModel, Post
-from .frame import FP, Concat, LongSkip, _pool7, _slice_map, check_input, pack_c1d_apost, set_scale
+from .frame import FP, Concat, LongSkip, _pool7, _slice_map, check_input, set_scale
 
 
 class PLAINRFDN(HipSRModel):
@@ -103,6 +103,3 @@ class PLAINRFDN(HipSRModel):
             plan.esa_apply(b + 'esa.conv_f', b + 'esa.conv4', v, c1, c3, out, nf, f, post=nxt_d)
             cur = out
         skip.close('LR_conv', 'upsampler.0', cur, r1, self.out_nc * 16)
-
-    def _extra_pack(self, packed, device):
-        pack_c1d_apost(self, packed, device)

@@ -529,13 +529,20 @@ def _blocked(v):
     return v is not None and v is not INPUT and v is not OUTPUT and not isinstance(v, Planar) and (v if isinstance(v, Buffer) else v[0]).blocked
 
 
-# Names of the weight blobs derived from a parameter path: HipSRModel._repack builds `<path><suffix>`, the ops' encode reads it.
+# Kinds of the weight blobs an op reads, most of them the suffix of the blob's name `<path><suffix>`.  The op that reads a blob names it, its kind
+# and the leaves it is made from (_Op.blobs); HipSRModel._repack walks the ops of one small plan and builds each with the kind's packer (_PACKERS).
+# What is not a leaf's own image (folded, scaled, sliced, replicated weights, border tables) a network packs in _extra_pack, under the name its ops read.
+BASE = ""          # the image under the leaf's own name that _repack builds for every registered leaf (pack_conv / pack_dense / pack_dw), or a network's own blob
 S16 = "#s16"       # esr_pack_conv_s16 image (conv_s16_kernel; BSConvU pointwise / distillation 1x1s)
 POST = "#post"     # esr_pack_post_s16 image of a 1x1 in a 16-bit conv's epilogue (Post)
 HEAD = "#head"     # a 16-bit plan's head conv reads `<path>#head#s16` (pack_head_s16; Plan.conv)
+APOST = "#apost"   # pack_apply_post image of the 1x1 riding in an ESA apply launch, under its name (Apply)
 DENSE = "#dense"   # esr_pack_dense_f32 blob of a layer of the fused ESA branch (EsaLayer)
-WINO = "#wino"     # esr_pack_wino_f32 blob of an fp32 3x3 (Winograd F(2x2, 3x3))
+DENSE_CAT = "#dense (cat)"  # the `#dense` blob of a kind-3 layer: a 3x3 over the pair's concat, the two halves' inputs at rows 0 and 16
+WINO = "#wino"     # esr_pack_wino_f32 blob of an fp32 3x3 (Winograd F(2x2, 3x3)): built with the leaf's own image, looked up by Conv.encode where it exists
 DWPAD = "#pad16"   # pack_dw image of a depthwise 3x3 of fewer than 16 channels, zero-padded to 16 (Dw: low-resolution maps stored whole)
+DW7 = "dw7"        # pack_dw7 image of a depthwise 7x7, under the leaf's own name (Dw7)
+UNSHUFFLE = "unshuffle"  # pack_unshuffle image of team 35's con_, under the leaf's own name (Unshuffle)
 CX1 = "#cx1"       # esr_pack_cx_pw1_s16 image of a ConvNeXt block's first 1x1 (CxBlock; pack_cx_pw)
 CX2 = "#cx2"       # esr_pack_cx_pw2_s16 image of its second 1x1
 DWPW = "#dwpw"     # pack_dwpw_pw image of a 1x1 of team 35's refinement path (DwPwPair)
@@ -589,10 +596,21 @@ class EsaLayer:
 class _Op:
     """What every op kind provides: encode(op, plan, base, weights) fills its esr_op (Plan.finalize), cost(plan, desc) is its
     HipSRModel.op_costs entry (desc: the finalized esr_op or None), counted_convs(plan) the nn.Conv2d calls of the reference it
-    stands for (HipSRModel._counted_convs)."""
+    stands for (HipSRModel._counted_convs), blobs(plan) the weight blobs its encode reads as `weights[name]`: [(name, kind, source leaf
+    paths), ...] -- what HipSRModel._repack builds for the op (_PACKERS[kind]) or expects from the network's _extra_pack."""
 
     def counted_convs(self, plan):
         return []
+
+    reads = ()             # ((the field that holds a leaf's path, kind), ...): the blobs of an op that reads one image per field
+
+    def blobs(self, plan):
+        return [_blob(getattr(self, field), kind) for field, kind in self.reads]
+
+
+def _blob(leaf, kind=BASE, *more):
+    """the _Op.blobs entry of the `kind` image of `leaf` (and the leaves `more`), named `<leaf><kind>`, or `<leaf>` where the kind is no suffix"""
+    return (leaf + kind if kind.startswith("#") else leaf, kind, (leaf,) + more)
 
 
 @dataclass
@@ -648,6 +666,13 @@ class Conv(_Op):
     def s16(self, plan):
         """runs on conv_s16_kernel with the `w + S16` blob: every full-resolution NHWC conv of a 16-bit plan"""
         return plan.esize == 2 and self.hw is None and self.src is not INPUT
+
+    def blobs(self, plan):
+        s16 = self.s16(plan)                              # (a head: Plan.conv appended HEAD to the leaf's name)
+        out = [(self.w + S16, HEAD, (self.w.removesuffix(HEAD),))] if (s16 and self.head) else [_blob(self.w, S16 if s16 else BASE)]
+        psfx = POST if (plan.esize == 2 and self.hw is None) else BASE      # the 1x1s evaluated in the conv's epilogue
+        posts = [p for p in (self.post, self.post and self.post.post2) if p is not None]
+        return out + [_blob(w) for w in (self.border, self.tail and self.tail.w) if w is not None] + [_blob(p.w, psfx) for p in posts]
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -852,6 +877,13 @@ class Dw(_Op):
     res_mode: int = L.RES_NONE
     kind = "dw"
 
+    def blobs(self, plan):
+        # a low-resolution map that is a whole dense buffer is stored whole, pad channels (zeros: zero weights, zero bias) included:
+        # _stored_width.  The pointwise conv in front of it stored its pad channels the same way
+        pad = (self.hw is not None and self.c < 16 and isinstance(self.src, Buffer) and isinstance(self.dst, Buffer)
+               and min(self.src.pitch, self.dst.pitch) >= 16)
+        return [_blob(self.w, DWPAD if pad else BASE)]
+
     def encode(self, op, plan, base, weights):
         op.kind = L.OP_DWCONV
         d = op.conv
@@ -866,13 +898,9 @@ class Dw(_Op):
         if self.res is not None:
             d.res, d.res_mode = _view(self.res, base), self.res_mode
         d.storage = 0 if self.hw is not None else L.STORE[plan.store]
-        w = self.w
-        if (self.hw is not None and self.c < 16 and isinstance(self.src, Buffer) and isinstance(self.dst, Buffer)
-                and min(self.src.pitch, self.dst.pitch) >= 16 and w + DWPAD in weights):
-            # a low-resolution map that is a whole dense buffer is stored whole, pad channels (zeros: zero weights, zero bias) included:
-            # _stored_width.  The pointwise conv in front of it stored its pad channels the same way
+        (w, kind, _), = self.blobs(plan)
+        if kind == DWPAD:
             d.cin = d.cout = 16
-            w += DWPAD
         d.wpacked = ctypes.c_void_p(weights[w].data_ptr())
 
     def cost(self, plan, desc):
@@ -896,6 +924,7 @@ class Dw7(_Op):
     dst: object
     c: int
     kind = "dw7"
+    reads = (("w", DW7),)
 
     def encode(self, op, plan, base, weights):
         op.kind = L.OP_DWCONV7
@@ -935,6 +964,10 @@ class Bs(_Op):
     distill: Post = None
     kind = "bs"
 
+    def blobs(self, plan):                                    # 16-bit storage: hi + lo 1x1 blobs (esr_pack_conv_s16)
+        sfx = S16 if plan.esize == 2 else BASE
+        return [_blob(self.pw, sfx), _blob(self.dw)] + ([_blob(self.distill.w, sfx)] if self.distill is not None else [])
+
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
         op.kind = L.OP_BSCONV
@@ -971,6 +1004,7 @@ class S2(_Op):
     dst: Buffer
     f: int
     kind = "s2"
+    reads = (("w", BASE),)
 
     def encode(self, op, plan, base, weights):
         op.kind = L.OP_CONV3X3S2
@@ -1046,6 +1080,12 @@ class _Fused(_Op):
     def counted_convs(self, plan):
         return [c for o in self.replaces for c in o.counted_convs(plan)]
 
+    def own_blobs(self, plan):                                # what the one-launch form reads beyond the blobs of the ops it replaces ...
+        return []
+
+    def blobs(self, plan):                                    # ... and theirs: a plan of another shape may keep the ops, with the same model's blobs
+        return self.own_blobs(plan) + [b for o in self.replaces for b in o.blobs(plan)]
+
 
 class _AnyBlob:
     """the weights of Plan._fuse's probe: every name yields a non-null dummy address (the predicates test blob pointers for null only)"""
@@ -1068,6 +1108,14 @@ class Lowres(_Fused):
     w: str
     layers: list
     kind = "lowres"
+
+    def own_blobs(self, plan):                                # the layers in the plain dense layout; kind 1: the depthwise half as it is
+        out = [_blob(self.w)] if self.w is not None else []
+        for ly in self.layers:
+            out.append((ly.w + DENSE, DENSE_CAT, (ly.w,)) if ly.kind == 3 else _blob(ly.w, DENSE))
+            if ly.kind in (1, 2):
+                out.append(_blob(ly.w_dw, DENSE if ly.kind == 2 else BASE))
+        return out
 
     def encode(self, op, plan, base, weights):
         op.kind = L.OP_ESA_LOWRES
@@ -1171,6 +1219,9 @@ class Distill(_Fused):
         assert cd.k == 1 and cb.k == 3 and cr.k == 3 and cd.act == cr.act == L.ACT_RELU and cb.act == L.ACT_NONE and cd.res is None
         assert _same_view(cb.src, cd.dst) and _same_view(cr.src, cd.src) and _same_view(cr.res, cb.dst) and cr.res_mode == L.RES_PRE_ACT
         assert cb.res is None or (_same_view(cb.res, cd.src) and cb.res_mode == L.RES_PRE_ACT)
+
+    def own_blobs(self, plan):                                # c_r and c_b as one 3x3 over cat[r, d], under c_r's name
+        return [_blob(self.replaces[2].w, FOLD, self.replaces[1].w)]
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -1308,6 +1359,12 @@ class CxBlock(_Fused):
         assert pw2.res_mode == L.RES_PRE_ACT and _same_view(pw2.res, dw.src)       # + v (no activation behind it: pre == post)
         assert _same_view(pw1.src, dw.dst) and _same_view(pw2.src, pw1.dst) and pw1.cin == dw.c and pw2.cin == pw1.cout and pw2.cout == dw.c
 
+    def blobs(self, plan):
+        """the two 1x1s as pack_cx_pw's pair, and the blobs of dw7 and pw2 -- not pw1's: no kernel takes a 1x1 as wide as the hidden tensor
+        in one launch, the per-op form runs it in slices whose images are the network's"""
+        dw, pw1, pw2 = self.replaces
+        return [_blob(pw1.w, CX1, pw2.w), (pw2.w + CX2, CX2, (pw1.w, pw2.w))] + dw.blobs(plan) + pw2.blobs(plan)
+
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
         dw, pw1, pw2 = self.replaces
@@ -1350,6 +1407,9 @@ class DwPwPair(_Fused):
         assert _same_view(pwa.src, dwa.dst) and _same_view(dwb.src, pwa.dst) and _same_view(pwb.src, dwb.dst)
         assert not _same_view(pwb.dst, dwa.src)
 
+    def own_blobs(self, plan):                                # pw_a and pw_b
+        return [_blob(self.replaces[i].w, DWPW) for i in (1, 3)]
+
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
         dwa, pwa, dwb, pwb = self.replaces
@@ -1387,6 +1447,7 @@ class Unshuffle(_Op):
     dst: Buffer
     f: int
     kind = "unshuffle"
+    reads = (("w", UNSHUFFLE),)
 
     def encode(self, op, plan, base, weights):
         op.kind = L.OP_ESA_UNSHUFFLE
@@ -1419,6 +1480,7 @@ class PaGate(_Op):
     s: object = None           # the tensor added behind the gate (a Plan.pair() where hilo has L.HILO_RES), or None
     hilo: int = 0
     kind = "pagate"
+    reads = (("w", PAG),)
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -1467,6 +1529,7 @@ class Prelu(_Op):
     dst: object
     kind = "prelu"
     FIELDS = (("inp", "cin"), ("res", "split"), ("tail_cat", "tail_cat_c"), ("out1", "tail_cout"))
+    reads = (("w", PRELU),)
 
     @property
     def c(self):
@@ -1503,7 +1566,9 @@ class Prelu(_Op):
 @dataclass
 class ResdbStep(_Fused):
     """A ResDB step as ONE esr_resdb_step op -- see Plan.resdb_step (resdb_step_kernel).  replaces: [the PReLU over cat(x, earlier distilled
-    maps), the expansion 1x1's `res` part, its distilled part, the PReLU of res, the 3x3 with the residual x]."""
+    maps), the expansion 1x1's `res` part, its distilled part, the PReLU of res, the 3x3 with the residual x]; whole: the name under which
+    the network packs the expansion 1x1 as ONE image, its `res` rows, then its distilled rows."""
+    whole: str = None
     kind = "resdb"
     predicate, field, what = "esr_resdb_step_supported", "conv", "ResDB step"
 
@@ -1516,9 +1581,8 @@ class ResdbStep(_Fused):
         assert len(pc.srcs) == 1 and _same_view(pc.srcs[0][0], cr.dst) and _same_view(c3.src, pc.dst)
         assert c3.res_mode == L.RES_PRE_ACT and _same_view(c3.res, pe.srcs[0][0]) and cr.cin == cd.cin == pe.c and pc.c == cr.cout == c3.cin
 
-    def name(self):
-        """the step's name: expansion{j}.0, under which `<name>#step` is packed"""
-        return self.replaces[0].w
+    def own_blobs(self, plan):                                # the slopes of both PReLUs, cat(a_e, a_c), under the first one's name; the whole expansion is the network's image
+        return [_blob(self.replaces[0].w, RSTEP, self.replaces[3].w), _blob(self.whole, S16)]
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -1533,10 +1597,9 @@ class ResdbStep(_Fused):
         d.inp, d.out0, d.post_out = _view(pe.srcs[0][0], base), _view(c3.dst, base), _view(cd.dst, base)
         for (v, _), dst in zip(pe.srcs[1:], ("res", "tail_cat")):
             setattr(d, dst, _view(v, base))
-        whole = cr.w[:-len("#res")]                      # the expansion 1x1 as ONE blob: its `res` rows, then its distilled rows
         d.wpacked = ctypes.c_void_p(weights[c3.w + S16].data_ptr())
-        d.post_wpacked = ctypes.c_void_p(weights[whole + S16].data_ptr())
-        d.tail_wpacked = ctypes.c_void_p(weights[self.name() + RSTEP].data_ptr())
+        d.post_wpacked = ctypes.c_void_p(weights[self.whole + S16].data_ptr())
+        d.tail_wpacked = ctypes.c_void_p(weights[pe.w + RSTEP].data_ptr())
 
     def cost(self, plan, desc):             # x and the earlier distilled maps read once, the step's distilled maps and x' written once
         pe, cr, cd, pc, c3 = self.replaces
@@ -1551,7 +1614,7 @@ class ResdbStep(_Fused):
         kern = f"resdb_step_kernel<{_tf(plan.store == 'bf16')}, {nx}, {nd // 16}>"
         rd = float(npix * es * cin) + 4.0 * macs
         wr = float(npix * es * (n + nd))
-        return _cost(self.name(), kern, cin, n, 3, 2.0 * npix * macs + npix * (cin + n), rd, wr, rd + wr, fexec)
+        return _cost(pe.w, kern, cin, n, 3, 2.0 * npix * macs + npix * (cin + n), rd, wr, rd + wr, fexec)
 
 
 @dataclass
@@ -1595,7 +1658,9 @@ class ConvPrelu(_Fused):
 @dataclass
 class MdsaGate(_Fused):
     """The end of an MDSA block as ONE esr_mdsa_gate op -- see Plan.mdsa_gate (mdsa_gate_kernel).  replaces: [the fuse 1x1 over
-    cat(f1, f2, f3), its PReLU, the replicated one-channel gate (a 1x1 of x with res_mode L.RES_GATE on the PReLU's result)]."""
+    cat(f1, f2, f3), its PReLU, the replicated one-channel gate (a 1x1 of x with res_mode L.RES_GATE on the PReLU's result)]; sa: the
+    one-channel gate's own leaf, which the replicated 1x1 is made from."""
+    sa: str = None
     kind = "mdsagate"
     predicate, field, what = "esr_mdsa_gate_supported", "conv", "MDSA gate"
 
@@ -1610,9 +1675,8 @@ class MdsaGate(_Fused):
         assert gt.res_mode == L.RES_GATE and _same_view(gt.res, pl.dst)                          # ... and the gate multiplies its result
         assert not isinstance(gt.src, (str, Planar)) and not isinstance(gt.dst, (str, Planar))
 
-    def name(self):
-        """the fuse 1x1's name, under which `<name>#mgate` is packed"""
-        return self.replaces[0].w
+    def own_blobs(self, plan):                                # conv_fuse.0, its slopes and sa.0 as one image, under conv_fuse.0's name
+        return [_blob(self.replaces[0].w, MGATE, self.replaces[1].w, self.sa)]
 
     def encode(self, op, plan, base, weights):
         cf, pl, gt = self.replaces
@@ -1629,7 +1693,7 @@ class MdsaGate(_Fused):
             d.inp = _view(cf.src, base)
         d.res, d.res_mode = _view(gt.src, base), L.RES_GATE                                      # x: the gate's operand
         d.out0 = _view(gt.dst, base)
-        d.wpacked = ctypes.c_void_p(weights[self.name() + MGATE].data_ptr())
+        d.wpacked = ctypes.c_void_p(weights[cf.w + MGATE].data_ptr())
 
     def cost(self, plan, desc):             # f1, f2, f3 and x read once, y written once; the raw 1x1 result and f never exist
         cf, pl, gt = self.replaces
@@ -1637,7 +1701,7 @@ class MdsaGate(_Fused):
         wb = 4.0 * (cf.cin * c + 3 * c + 1)
         rd, wr = float(npix * es * (cf.cin + c)) + wb, float(npix * es * c)
         flops = 2.0 * npix * (cf.cin * c + c) + 2.0 * npix * c
-        return _cost(self.name(), f"mdsa_gate_kernel<{_tf(plan.store == 'bf16')}>", cf.cin, c, 1, flops, rd, wr, rd + wr, 2.0 * 2.0 * npix * cf.cin * c)
+        return _cost(cf.w, f"mdsa_gate_kernel<{_tf(plan.store == 'bf16')}>", cf.cin, c, 1, flops, rd, wr, rd + wr, 2.0 * 2.0 * npix * cf.cin * c)
 
 
 @dataclass
@@ -1678,8 +1742,10 @@ class PaTail(_Fused):
 @dataclass
 class AsymStep(_Fused):
     """An ARFDB step as ONE esr_asym_step op -- see Plan.asym_step (asym_step_kernel).  replaces: [c_d, the folded first convolutions of the
-    two pairs (in -> [a_l | a_m]), the folded second ones (+ the residuals)]; p: the earlier steps' distilled maps (views)."""
+    two pairs (in -> [a_l | a_m]), the folded second ones (+ the residuals)]; p: the earlier steps' distilled maps (views); taps: the
+    leaves of the step's four 3-tap convolutions, [c_l1, c_m1, c_l2, c_m2]."""
     p: list = None
+    taps: list = None
     kind = "asym"
     predicate, field, what = "esr_asym_step_supported", "conv", "asymmetric-convolution step"
 
@@ -1691,9 +1757,8 @@ class AsymStep(_Fused):
         assert _same_view(ca.src, cd.src) and cd.res is None and ca.res is None and ca.cout == 2 * cd.cout and cb.cout == cd.cout
         assert cb.res is None or (_same_view(cb.res, cd.src) and cb.res_mode == L.RES_PRE_ACT and cd.cin == cd.cout)
 
-    def name(self):
-        """the step's name: c{j}_l1, under which `<name>#asym` is packed"""
-        return self.replaces[1].w.split("#")[0]
+    def own_blobs(self, plan):                                # the four as one image, under c_l1's name
+        return [_blob(self.taps[0], ASYM, *self.taps[1:])]
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
@@ -1709,7 +1774,7 @@ class AsymStep(_Fused):
         d.inp, d.out0, d.post_out, d.post_cout = _view(cd.src, base), _view(cb.dst, base), _view(cd.dst, base), cd.cout
         for v, dst in zip(self.p or (), ("res", "tail_cat")):
             setattr(d, dst, _view(v, base))
-        d.wpacked = ctypes.c_void_p(weights[self.name() + ASYM].data_ptr())
+        d.wpacked = ctypes.c_void_p(weights[self.taps[0] + ASYM].data_ptr())
         d.post_wpacked = ctypes.c_void_p(weights[cd.w + S16].data_ptr())
 
     def cost(self, plan, desc):             # the step's input (and the earlier distilled maps) read once, d and the result written once
@@ -1725,7 +1790,7 @@ class AsymStep(_Fused):
         np_ = len(self.p or ())
         rd = float(npix * es * (cd.cin_alg + np_ * c)) + 4.0 * macs
         stored = float(npix * es * (_stored_channels(cd.src, cd.cin, 16) + (2 + np_) * _stored_channels(cd.dst, c, 16))) + 4.0 * macs
-        return _cost(self.name(), kern, cd.cin, c, 3, 2.0 * npix * macs, rd, float(npix * es * 2 * c), stored, fexec)
+        return _cost(self.taps[0], kern, cd.cin, c, 3, 2.0 * npix * macs, rd, float(npix * es * 2 * c), stored, fexec)
 
 
 @dataclass
@@ -1743,6 +1808,9 @@ class Apply(_Op):
     skip_y: bool = False
     kind = "apply"
 
+    def blobs(self, plan):                                    # (the 1x1s riding in the launch are ONE blob, under the first one's name)
+        return [_blob(self.wf), _blob(self.w4)] + ([_blob(self.post[0].w, APOST, *(t.w for t in self.post[1:]))] if self.post else [])
+
     def encode(self, op, plan, base, weights):
         op.kind = L.OP_ESA_APPLY
         e = op.esa
@@ -1754,7 +1822,7 @@ class Apply(_Op):
         e.w0 = ctypes.c_void_p(weights[self.wf].data_ptr())
         e.w1 = ctypes.c_void_p(weights[self.w4].data_ptr())
         if self.post:
-            e.post_w = ctypes.c_void_p(weights[self.post[0].w + "#apost"].data_ptr())
+            e.post_w = ctypes.c_void_p(weights[self.post[0].w + APOST].data_ptr())
             e.skip_y = 1 if self.skip_y else 0
             for k, t in enumerate(self.post):
                 pp = e.post[k]
@@ -1983,14 +2051,14 @@ class Plan:
         never runs; dst: a dense tensor that is none of the sources; `wname + PRELU` names a pack_prelu blob of all the channels' slopes."""
         self.ops.append(Prelu(wname, list(srcs), dst))
 
-    def resdb_step(self, mark):
+    def resdb_step(self, mark, whole):
         """The five ops appended since `mark = len(plan.ops)` -- a ResDB step in its per-layer form, u = prelu(cat(x, ..)), r = W_e[:48] . u,
         dists = W_e[48:] . u, t = prelu(r), x' = x + W_c (*) t (resdn.py; team43_resdn.py:93-106) -- as ONE esr_resdb_step op (16-bit plans): x
         and the earlier distilled maps are read once, dists and x' are written once, u, r and t never exist.  The ops stay attached as
         `replaces`: complexity counters and algorithmic costs are theirs; the blobs are the 3x3's and the WHOLE expansion's esr_pack_conv_s16
-        images and pack_prelu(cat(a_e, a_c)) (`<expansion.0>#step`).  It stores what the five launches store, up to the summation order of
-        the fp32 sums.  x' must not be stored into x's tensor."""
-        return self._fuse(mark, ResdbStep)
+        images (`<whole>#s16`: the network's) and pack_prelu(cat(a_e, a_c)) (`<expansion.0>#step`).  It stores what the five launches store, up to
+        the summation order of the fp32 sums.  x' must not be stored into x's tensor."""
+        return self._fuse(mark, ResdbStep, whole=whole)
 
     def conv_prelu(self, mark):
         """The two ops appended since `mark = len(plan.ops)` -- a dense 64 -> 64 3x3 and the per-channel PReLU of its result, raw = conv(x),
@@ -2001,13 +2069,13 @@ class Plan:
         x's tensor."""
         return self._fuse(mark, ConvPrelu)
 
-    def mdsa_gate(self, mark):
+    def mdsa_gate(self, mark, sa):
         """The three ops appended since `mark = len(plan.ops)` -- the end of an MDSA block in its per-layer form, raw = W_f . cat(f1, f2, f3),
         t = prelu(raw, a_f), y = sigmoid(w_s . x) * t (mdgn.py; team24_mdgn.py:26-28) -- as ONE esr_mdsa_gate op (16-bit plans): f1, f2, f3 and x
         are read once, y is written once, raw and t never exist.  The ops stay attached as `replaces`: complexity counters and algorithmic
-        costs are theirs; the blob is pack_mdsa_gate's (`<conv_fuse.0>#mgate`).  Not bit-identical to the three launches, which round raw and
-        t: here one rounding, at the store.  y must not be stored into a source's tensor."""
-        return self._fuse(mark, MdsaGate)
+        costs are theirs; the blob is pack_mdsa_gate's (`<conv_fuse.0>#mgate`), of conv_fuse.0, its PReLU and the gate's leaf `sa`.  Not bit-identical
+        to the three launches, which round raw and t: here one rounding, at the store.  y must not be stored into a source's tensor."""
+        return self._fuse(mark, MdsaGate, sa=sa)
 
     def pa_tail(self, mark):
         """The two ops appended since `mark = len(plan.ops)` -- a plain 3x3 and the pixel attention that reads its result, t = conv(x),
@@ -2018,21 +2086,21 @@ class Plan:
         (include/esr_hip.h: esr_pa_tail).  y must not be stored into x's tensor."""
         return self._fuse(mark, PaTail)
 
-    def asym_step(self, mark, p=None):
+    def asym_step(self, mark, taps, p=None):
         """The three convolutions appended since `mark = len(plan.ops)` -- an ARFDB step in its per-layer form, d = act(c_d(r)), [a_l | a_m] =
         act(P (*) r), r' = act(Q (*) [d .. | a_l | a_m] (+ r)) (arfdn.py; team14_arfdn/block.py:233-254) -- as ONE esr_asym_step op (16-bit
         plans): r is read once, d and r' are written once, a_l and a_m never exist; p: the views of the earlier steps' distilled maps that
         Q adds through identity taps (at most two).  The Conv ops stay attached as `replaces`: complexity counters and algorithmic costs
-        are theirs; the 3-tap blob is pack_asym_s16's (`<c_l1>#asym`).  Not bit-identical to the three launches: another summation order,
+        are theirs; the 3-tap blob is pack_asym_s16's (`<c_l1>#asym`) of the leaves taps = [c_l1, c_m1, c_l2, c_m2].  Not bit-identical to the three launches: another summation order,
         and the 3-tap weights are rounded once where pack_conv_s16 diffuses the rounding error over a 3x3's taps.  r' must not be stored
         into r's tensor."""
-        return self._fuse(mark, AsymStep, p=list(p or ()))
+        return self._fuse(mark, AsymStep, p=list(p or ()), taps=list(taps))
 
     def esa_apply(self, wf, w4, x, c1, c3, dst, c, f, **kw):
         """y = x * sigmoid(conv4(bilinear(c3) + conv_f(c1)));  two nn.Conv2d calls of the reference.
         post (16-bit plans): [Post(w, dst, cout, act, slope, res), ...] -- one or two 1x1 convolutions evaluated in the same launch
         (esr_esa_desc.post[]): the first on y as stored, the second on the first's fp32 result; their weights are ONE blob
-        `<post[0].w>#apost` (engine.pack_apply_post, packed by the network).  skip_y: y itself is not stored (nothing but the chain
+        `<post[0].w>#apost` (engine.pack_apply_post; a chain of scaled or folded weights is packed by the network).  skip_y: y itself is not stored (nothing but the chain
         reads it)."""
         self.ops.append(Apply(wf, w4, x, c1, c3, dst, c, f, **kw))
 
@@ -2144,6 +2212,55 @@ def _mark_dirty_hook(module, incompatible):
     """HipSRModel's load_state_dict post hook.  A module-level function: the hook table is part of what copy.deepcopy / pickle carry, and
     the hook marks the module it is called on -- a copy's load re-packs the copy, not its source."""
     module._mark_dirty()
+
+
+def _wb(m, path):
+    leaf = m._leaf(path)
+    return leaf.weight, leaf.bias
+
+
+def _pack_dense_cat(m, store, path):
+    """a 3x3 over the pair's concat: the two halves' inputs at rows 0 and 16 (esr_esa_layer kind 3)"""
+    w, bias = _wb(m, path)
+    w, f = _host(w), w.shape[1] // 2
+    w32 = torch.zeros(w.shape[0], 2 * L.ESA_FP, 3, 3)
+    w32[:, :f], w32[:, L.ESA_FP:L.ESA_FP + f] = w[:, :f], w[:, f:]
+    return pack_dense(w32, bias, 2 * L.ESA_FP, L.ESA_FP)
+
+
+def _pack_dw_pad16(m, store, path):
+    w, bias = _wb(m, path)
+    w16, b16 = torch.zeros(16, 1, 3, 3), torch.zeros(16)
+    w16[:len(w)] = _host(w)
+    if bias is not None:
+        b16[:len(w)] = _host(bias)
+    return pack_dw(w16, b16)
+
+
+# kind -> packer(model, storage, *source leaf paths): how HipSRModel._repack builds a blob that an op of its plan names (_Op.blobs)
+_PACKERS = {
+    S16: lambda m, st, p: pack_conv_s16(*_wb(m, p), st, cin_map=m._cin_map(p, m._conv_specs[p][3], st)),
+    POST: lambda m, st, p: pack_post_s16(*_wb(m, p), st),
+    HEAD: lambda m, st, p: pack_head_s16(*_wb(m, p), st),
+    APOST: lambda m, st, p, p2=None: pack_apply_post(*_wb(m, p), *(_wb(m, p2) if p2 else (None, None)), st),
+    DENSE: lambda m, st, p: pack_dense(*_wb(m, p), L.ESA_FP, L.ESA_FP),
+    DENSE_CAT: _pack_dense_cat,
+    DWPAD: _pack_dw_pad16,
+    DW7: lambda m, st, p: pack_dw7(*_wb(m, p)),
+    UNSHUFFLE: lambda m, st, p: pack_unshuffle(*_wb(m, p)),
+    FOLD: lambda m, st, r, b: pack_distill_s16(*_wb(m, r), *_wb(m, b), st),
+    CX1: lambda m, st, p1, p2: pack_cx_pw(*_wb(m, p1), *_wb(m, p2), st)[0],
+    CX2: lambda m, st, p1, p2: pack_cx_pw(*_wb(m, p1), *_wb(m, p2), st)[1],
+    DWPW: lambda m, st, p: pack_dwpw_pw(*_wb(m, p), st),
+    PAG: lambda m, st, p: pack_pa_gate(*_wb(m, p), st),
+    ASYM: lambda m, st, *taps: pack_asym_s16(*(t for p in taps for t in _wb(m, p)), st),
+    PRELU: lambda m, st, p: pack_prelu(m._leaf(p).weight),
+    RSTEP: lambda m, st, e, c: pack_prelu(torch.cat([_host(m._leaf(e).weight), _host(m._leaf(c).weight)])),
+    MGATE: lambda m, st, cf, a, sa: pack_mdsa_gate(*_wb(m, cf), m._leaf(a).weight, *_wb(m, sa), st),
+}
+# the generic images: derived only from a leaf registered in _conv_specs (_add_conv without custom=True) -- a leaf outside it, or a name that
+# is no leaf at all, is the network's to pack in _extra_pack.  The dedicated packers above take any registered leaf.
+_GENERIC = (S16, POST, HEAD, APOST)
 
 
 class HipSRModel(nn.Module):
@@ -2354,69 +2471,31 @@ class HipSRModel(nn.Module):
 
     def _repack(self, device):
         store = self._store()
-        # paths whose derived blobs (`#s16`, `#post`, `#head#s16`, `#dense`) the ops of the current mode read: one plan of a small
-        # shape has every op the network emits
+        # the blobs the ops of the current mode read (_Op.blobs): one plan of a small shape has every op the network emits
         plan = Plan(1, 32, 32, store)
         self._build_plan(plan, self.in_nc)
-        s16, post, head, dense, dense_cat = set(), set(), set(), set(), set()
-        for o in plan.ops:
-            if o.kind == "lowres":                          # 3x3 / pointwise layers of the fused ESA branch: plain dense layout
-                dense.update(ly.w for ly in o.layers if ly.kind != 3)
-                dense.update(ly.w_dw for ly in o.layers if ly.kind == 2)
-                dense_cat.update(ly.w for ly in o.layers if ly.kind == 3)
-            if store == "f32":
-                continue
-            if o.kind == "bs":                              # BSConvU: pointwise + distillation 1x1 weights as hi + lo blobs
-                s16.update([o.pw] + ([o.distill.w] if o.distill is not None else []))
-            for c in (o.replaces if isinstance(o, _Fused) else [o]):      # (a fused op's blobs are those of the ops it stands for)
-                if c.kind != "conv":
-                    continue
-                if c.s16(plan) and c.head:
-                    head.add(c.w[:-len(HEAD)])
-                elif c.s16(plan):
-                    s16.add(c.w)
-                if c.post is not None:                      # the 1x1s evaluated in the conv's epilogue
-                    post.update([c.post.w] + ([c.post.post2.w] if c.post.post2 is not None else []))
+        want = {name: (o, kind, srcs) for o in plan.ops[::-1] for name, kind, srcs in o.blobs(plan)}      # (of a blob's readers, the first op)
         packed = {}
+        # every registered leaf's own image, read or not
         for path, (cin, cout, k, cin_map) in self._conv_specs.items():
             leaf = self._leaf(path)
             packed[path] = pack_conv(leaf.weight, leaf.bias, cin_map=self._cin_map(path, cin_map, "f32")).to(device)
             if k == 3 and self.winograd and store == "f32" and cin >= 32 and cout <= 64:
                 packed[path + WINO] = pack_wino(leaf.weight, leaf.bias, cin_map=self._cin_map(path, cin_map, "f32")).to(device)
-            if path in s16:
-                packed[path + S16] = pack_conv_s16(leaf.weight, leaf.bias, store, cin_map=self._cin_map(path, cin_map, store)).to(device)
-        for path in sorted(post):
-            leaf = self._leaf(path)
-            packed[path + POST] = pack_post_s16(leaf.weight, leaf.bias, store).to(device)
-        for path in sorted(head):
-            if path in self._conv_specs and not self._conv_specs[path][3]:          # (custom-packed heads: _extra_pack)
-                leaf = self._leaf(path)
-                packed[path + HEAD + S16] = pack_head_s16(leaf.weight, leaf.bias, store).to(device)
         for path, (cin_p, cout_p) in self._dense_specs.items():
-            leaf = self._leaf(path)
-            packed[path] = pack_dense(leaf.weight, leaf.bias, cin_p, cout_p).to(device)
-        for path in sorted(dense):
-            leaf = self._leaf(path)
-            packed[path + DENSE] = pack_dense(leaf.weight, leaf.bias, L.ESA_FP, L.ESA_FP).to(device)
-        for path in sorted(dense_cat):                  # a 3x3 over the pair's concat: the two halves' inputs at rows 0 and 16 (esr_esa_layer kind 3)
-            leaf = self._leaf(path)
-            w = leaf.weight.detach().to("cpu", torch.float32)
-            f = w.shape[1] // 2
-            w32 = torch.zeros(w.shape[0], 2 * L.ESA_FP, 3, 3)
-            w32[:, :f], w32[:, L.ESA_FP:L.ESA_FP + f] = w[:, :f], w[:, f:]
-            packed[path + DENSE] = pack_dense(w32, leaf.bias, 2 * L.ESA_FP, L.ESA_FP).to(device)
+            packed[path] = pack_dense(*_wb(self, path), cin_p, cout_p).to(device)
         for path in self._dw_specs:
-            leaf = self._leaf(path)
-            packed[path] = pack_dw(leaf.weight, leaf.bias).to(device)
-            c = leaf.weight.shape[0]
-            if c < 16:                                  # (ESA's low-resolution depthwise layers: Dw.encode)
-                w16 = torch.zeros(16, 1, 3, 3)
-                w16[:c] = leaf.weight.detach().to("cpu", torch.float32)
-                b16 = torch.zeros(16)
-                if leaf.bias is not None:
-                    b16[:c] = leaf.bias.detach().to("cpu", torch.float32)
-                packed[path + DWPAD] = pack_dw(w16, b16).to(device)
+            packed[path] = pack_dw(*_wb(self, path)).to(device)
+        # what the ops name beyond that
+        for name, (o, kind, srcs) in want.items():
+            spec = self._conv_specs.get(srcs[0])
+            own = kind not in _GENERIC or (spec is not None and not (kind == HEAD and spec[3]))      # (a head over a cin_map: custom-packed)
+            if kind in _PACKERS and own:
+                packed[name] = _PACKERS[kind](self, store, *srcs).to(device)
         self._extra_pack(packed, device)
+        for name, (o, kind, srcs) in reversed(want.items()):      # (in the plan's order)
+            if name not in packed:
+                raise L.EsrError(f"{type(self).__name__}: op {o.cost(plan, None)['name']!r} ({o.kind}) reads the blob {name!r}, which neither the engine nor _extra_pack built")
         if torch.device(device).type == "cuda":
             torch.cuda.synchronize(device)           # the blobs are read by forwards on ANY stream from here on
         self._packed = packed
@@ -2426,6 +2505,16 @@ class HipSRModel(nn.Module):
 
     def _extra_pack(self, packed, device):
         pass
+
+    def _pack_own(self, packed, device, name, w, bias, wino=False):
+        """A network's own weights (folded, scaled, sliced ...) under `name`, as a Conv reads a leaf's: the fp32 image, and `#s16` in a 16-bit
+        mode; wino: `#wino` where the engine would build a leaf's"""
+        store = self._store()
+        packed[name] = pack_conv(w, bias).to(device)
+        if store != "f32":
+            packed[name + S16] = pack_conv_s16(w, bias, store).to(device)
+        elif wino and self.winograd:
+            packed[name + WINO] = pack_wino(w, bias).to(device)
 
     # -- forward ------------------------------------------------------------------------------
     def _build_plan(self, plan):

@@ -100,15 +100,14 @@ class ESAN(HipSRModel):
             plan.conv('upconv.0', last, OUTPUT, nf, co, res=up0, res_mode=L.RES_PRE_ACT)
 
     def _extra_pack(self, packed, device):
-        from .engine import pack_conv, pack_conv_s16
+        from .engine import pack_conv_s16
         store = self._store()
         eye, zero = torch.eye(self.nf)[:, :, None, None], torch.zeros(self.nf)
-        packed[IDENT] = pack_conv(eye, zero).to(device)
+        self._pack_own(packed, device, IDENT, eye, zero)
         conv_f = identity_conv_f(self.f, device)
         for k in range(self.n_blocks):
             packed[f'recon_trunk.0.{k}.ESA.conv_f'] = conv_f
         if store != "f32":
-            packed[IDENT + S16] = pack_conv_s16(eye, zero, store).to(device)
             # upconv.0 over the trunk and upconv0 over the packed input [x_hi | x_lo | x_hi] as ONE 3x3: upconv0's weights as [w_hi | w_hi | w_lo]
             # (engine.pack_head_s16), the biases added
             up, up0 = self._leaf('upconv.0'), self._leaf('upconv0')

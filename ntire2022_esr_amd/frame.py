@@ -5,7 +5,7 @@ The builders allocate and append exactly what the networks used to spell out, in
 import torch
 
 from . import _lib as L
-from .engine import INPUT, OUTPUT, EsaLayer, Planar, pack_apply_post, pack_dense
+from .engine import INPUT, OUTPUT, EsaLayer, Planar, pack_dense
 
 FP = L.ESA_FP
 
@@ -47,14 +47,6 @@ def check_input(name, plan, c, in_nc, esa=True):
 def set_scale(self, scale_idx):
     """the reference models' no-op setter, for the classes whose reference has one"""
     self.scale_idx = scale_idx
-
-
-def pack_c1d_apost(model, packed, device):
-    """16-bit plans: c1_d of blocks 2..4 as the post of the previous block's ESA apply launch (Plan.esa_apply), where a kernel takes it"""
-    if model._store() != "f32" and L.lib().esr_esa_apply_post_supported(model.nf, model.dc, 0):
-        for k in range(2, 5):
-            leaf = model._leaf(f'B{k}.c1_d')
-            packed[f'B{k}.c1_d#apost'] = pack_apply_post(leaf.weight, leaf.bias, None, None, model._store()).to(device)
 
 
 def identity_conv_f(f, device):

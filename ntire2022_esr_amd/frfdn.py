@@ -30,7 +30,7 @@ segment, are this file's.
 """
 from . import _lib as L
 from .engine import HipSRModel, Post
-from .frame import FP, Concat, EsaBranch, LongSkip, check_input, pack_c1d_apost, set_scale
+from .frame import FP, Concat, EsaBranch, LongSkip, check_input, set_scale
 
 
 class FasterRFDN(HipSRModel):
@@ -124,6 +124,3 @@ class FasterRFDN(HipSRModel):
             cur = out
         plan.conv('c.0', bcat.whole, v, 4 * nf, nf, k=1, **act)
         skip.close('LR_conv', 'upsampler.0', v, r1, self.out_nc * 16)
-
-    def _extra_pack(self, packed, device):
-        pack_c1d_apost(self, packed, device)

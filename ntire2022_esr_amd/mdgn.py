@@ -40,7 +40,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import MGATE, PRELU, S16, HipSRModel, pack_conv, pack_conv_s16, pack_mdsa_gate, pack_prelu
+from .engine import HipSRModel
 from .frame import Concat, LongSkip, check_input
 
 REP = "#rep"               # sa.0 as a 64 x 64 1x1 whose rows are all w_s, biases all b_s (the gate of L.RES_GATE)
@@ -64,9 +64,6 @@ class MDGN(HipSRModel):
             self._add_conv(b + 'sa.0', nf, 1, 1, custom=True)      # packed by _extra_pack, replicated
         self._add_conv('LR_conv', nf, nf, 3)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
-
-    def _prelus(self):
-        return [f'B.{k}.{name}.1' for k in range(self.num_modules) for name in ('f1', 'f2', 'f3', 'conv_fuse')]
 
     def _build_plan(self, plan, c):
         check_input('MDGN', plan, c, self.in_nc, esa=False)
@@ -94,25 +91,17 @@ class MDGN(HipSRModel):
             out = xb if x is xa else xa
             plan.conv(b + 'sa.0' + REP, x, out, nf, nf, k=1, res=t, res_mode=L.RES_GATE)      # f * sigmoid(sa.0 . x)
             if s16 and self.fuse_mdsa_gate:
-                plan.mdsa_gate(mark)
+                plan.mdsa_gate(mark, sa=b + 'sa.0')
             x = out
         skip.close('LR_conv', 'upsampler.0', x, raw, self.out_nc * 16)
 
     def _extra_pack(self, packed, device):
-        store = self._store()
         cpu = lambda p: p.detach().to("cpu", torch.float32)
         nf = self.nf
-        for name in self._prelus():
-            packed[name + PRELU] = pack_prelu(cpu(self._leaf(name).weight)).to(device)
         for k in range(self.num_modules):
             leaf = self._leaf(f'B.{k}.sa.0')
             w, bias = cpu(leaf.weight).expand(nf, nf, 1, 1).contiguous(), cpu(leaf.bias).expand(nf).contiguous()
-            packed[f'B.{k}.sa.0' + REP] = pack_conv(w, bias).to(device)
-            if store != "f32":
-                packed[f'B.{k}.sa.0' + REP + S16] = pack_conv_s16(w, bias, store).to(device)
-            if store != "f32" and self.fuse_mdsa_gate:     # the one-launch end of the block: conv_fuse and sa.0 as one image
-                cf, a = self._leaf(f'B.{k}.conv_fuse.0'), self._leaf(f'B.{k}.conv_fuse.1')
-                packed[f'B.{k}.conv_fuse.0' + MGATE] = pack_mdsa_gate(cf.weight, cf.bias, a.weight, leaf.weight, leaf.bias, store).to(device)
+            self._pack_own(packed, device, f'B.{k}.sa.0' + REP, w, bias)
 
     def _counted_convs(self, plan, o):
         """the replicated gate is the reference's sa.0: nn.Conv2d(64, 1, 1); its nn.Sigmoid and the product have no hook in the counters"""

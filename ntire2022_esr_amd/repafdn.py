@@ -34,7 +34,7 @@ op of its own otherwise (16-bit plans only; an fp32 plan at nf = 48 has none): c
 B1.c1_d in the head convolution, the next block's c1_d in the ESA apply launch, esa.conv1 in c5's epilogue.
 """
 from . import _lib as L
-from .engine import HEAD, OUTPUT, PAG, Buffer, Conv, HipSRModel, Post, pack_apply_post, pack_pa_gate
+from .engine import HEAD, OUTPUT, Buffer, Conv, HipSRModel, Post
 from .frame import FP, Concat, EsaBranch, LongSkip, _slice_map, block_cin_map, check_input, set_scale
 
 
@@ -68,7 +68,7 @@ class RePAFDN(HipSRModel):
             self._add_conv(b + 'esa.conv4', f, nf, 1, dense=(FP, nf))
         self._add_conv('c.0', nf * 4, nf, 1, cin_map=_slice_map(4, nf, nf))
         self._add_conv('LR_conv', nf, nf, 3)
-        self._add_conv('pa.conv', nf, nf, 1, custom=True)    # packed by _extra_pack (pack_pa_gate)
+        self._add_conv('pa.conv', nf, nf, 1, custom=True)    # packed for Plan.pa_gate (pack_pa_gate)
         self._add_conv('upsampler.0', nf, out_nc * upscale * upscale, 3)
 
     def _block(self, k):
@@ -147,13 +147,3 @@ class RePAFDN(HipSRModel):
             plan.conv('upsampler.0', r2, OUTPUT, nf, self.out_nc * 16)
 
     _cin_map = block_cin_map
-
-    def _extra_pack(self, packed, device):
-        store = self._store()
-        leaf = self._leaf('pa.conv')
-        packed['pa.conv' + PAG] = pack_pa_gate(leaf.weight, leaf.bias, store).to(device)
-        if store != "f32":
-            for k in range(2, 5):                            # c1_d of blocks 2 .. 4 as the post of the previous block's ESA apply launch
-                if 16 < self._block(k)[1] <= 32 and L.lib().esr_esa_apply_post_supported(self.nf, self._block(k)[1], 0):
-                    leaf = self._leaf(f'B{k}.c1_d')
-                    packed[f'B{k}.c1_d#apost'] = pack_apply_post(leaf.weight, leaf.bias, None, None, store).to(device)

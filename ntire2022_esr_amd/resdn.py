@@ -40,7 +40,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import HEAD, INPUT, OUTPUT, PRELU, RSTEP, S16, WINO, Conv, HipSRModel, Post, pack_conv, pack_conv_s16, pack_head_s16, pack_prelu, pack_wino
+from .engine import HEAD, INPUT, OUTPUT, S16, Conv, HipSRModel, Post, pack_conv, pack_conv_s16, pack_head_s16
 from .frame import FP, EsaBranch, check_input
 
 IDENT = "ident"            # the blob of the 48 -> 48 identity 1x1 behind every block's `+ input`
@@ -121,7 +121,7 @@ class ResDN(HipSRModel):
                 mark = len(plan.ops) - 4
                 plan.conv(b + f'compression{j}.1', us[nf], nxt, nf, nf, res=x, res_mode=L.RES_PRE_ACT)
                 if self.fuse_resdb and s16:
-                    plan.resdb_step(mark)                  # (where the kernel takes the step; else the five launches stay)
+                    plan.resdb_step(mark, whole=e + '1')   # (where the kernel takes the step; else the five launches stay)
                 x = nxt
             plan.prelu(b + 'conv_tail.0', [(x, nf), d(2), d(4), d(5)], us[nf + 3 * nd])
             tail = dict(w=b + 'conv_tail.1', src=us[nf + 3 * nd], dst=t, cin=nf + 3 * nd, cout=nf, k=1)
@@ -166,32 +166,20 @@ class ResDN(HipSRModel):
         nf = self.nf
         b_sub, b_add = self._mean_shifts()
         eye, zero = torch.eye(nf)[:, :, None, None], torch.zeros(nf)
-        packed[IDENT] = pack_conv(eye, zero).to(device)
-        if s16:
-            packed[IDENT + S16] = pack_conv_s16(eye, zero, store).to(device)
+        self._pack_own(packed, device, IDENT, eye, zero)
         for k in range(1, 5):
             b = f'body_unit{k}.'
-            for name in [f'expansion{j}.0' for j in (1, 2, 3)] + [f'compression{j}.0' for j in (1, 2, 3)] + ['conv_tail.0']:
-                packed[b + name + PRELU] = pack_prelu(cpu(self._leaf(b + name).weight)).to(device)
             for j in (1, 2, 3):
                 leaf = self._leaf(b + f'expansion{j}.1')
                 w, bias = cpu(leaf.weight), cpu(leaf.bias)
                 for sfx, sl in ((RES, slice(0, nf)), (DIST, slice(nf, None))):
-                    packed[b + f'expansion{j}.1' + sfx] = pack_conv(w[sl].contiguous(), bias[sl].contiguous()).to(device)
-                    if s16:
-                        packed[b + f'expansion{j}.1' + sfx + S16] = pack_conv_s16(w[sl].contiguous(), bias[sl].contiguous(), store).to(device)
-                if s16 and self.fuse_resdb:               # the one-launch step: the whole expansion as one image, cat(a_e, a_c)
+                    self._pack_own(packed, device, b + f'expansion{j}.1' + sfx, w[sl].contiguous(), bias[sl].contiguous())
+                if s16 and self.fuse_resdb:               # the one-launch step: the whole expansion as one image
                     packed[b + f'expansion{j}.1' + S16] = pack_conv_s16(w, bias, store).to(device)
-                    packed[b + f'expansion{j}.0' + RSTEP] = pack_prelu(torch.cat([cpu(self._leaf(b + f'expansion{j}.0').weight),
-                                                                                   cpu(self._leaf(b + f'compression{j}.0').weight)])).to(device)
         # add_mean into tail.1's bias: colour c of the shuffled output is channels 16 c .. 16 c + 15
         leaf = self._leaf('tail.1')
         w, bias = cpu(leaf.weight), cpu(leaf.bias) + b_add.repeat_interleave(16)
-        packed['tail.1'] = pack_conv(w, bias).to(device)
-        if s16:
-            packed['tail.1' + S16] = pack_conv_s16(w, bias, store).to(device)
-        elif self.winograd:
-            packed['tail.1' + WINO] = pack_wino(w, bias).to(device)
+        self._pack_own(packed, device, 'tail.1', w, bias, wino=True)
         # sub_mean
         wf, bf = cpu(self._leaf('fea_conv').weight), cpu(self._leaf('fea_conv').bias)
         if s16:

@@ -10,7 +10,7 @@ low-resolution branch are the shared frame's (frame.py); specific to RFDN is whi
 """
 from . import _lib as L
 from .engine import HipSRModel, Planar, Post, Tail
-from .frame import FP, Concat, EsaBranch, LongSkip, _pad8, _slice_map, block_cin_map, check_input, identity_conv_f, pack_c1d_apost, set_scale
+from .frame import FP, Concat, EsaBranch, LongSkip, _pad8, _slice_map, block_cin_map, check_input, identity_conv_f, set_scale
 
 
 class RFDN(HipSRModel):
@@ -137,7 +137,6 @@ class RFDN(HipSRModel):
             for k in range(1, 5):
                 leaf = self._leaf(f'B{k}.c5')
                 packed[f'B{k}.c5#tail'] = pack_tail_s16(leaf.weight, leaf.bias, 3, self.dc, self.dc, self._store()).to(device)
-        pack_c1d_apost(self, packed, device)
         if not self.esa_conv_f:                  # SFDN: c3 + c1_  ==  c3 + conv_f(c1_) with conv_f = identity
             for k in range(1, 5):
                 packed[f'B{k}.esa.conv_f'] = identity_conv_f(self.f, device)

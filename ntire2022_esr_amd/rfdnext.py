@@ -37,7 +37,7 @@ The long skip (RFDN.py:64) and the two concats are the shared frame's (frame.py)
 import torch
 
 from . import _lib as L
-from .engine import CX1, CX2, S16, WINO, HipSRModel, fold_center, pack_conv, pack_conv_s16, pack_cx_pw, pack_dw7, pack_wino
+from .engine import HipSRModel, fold_center
 from .frame import Concat, LongSkip, _pad8, _slice_map, block_cin_map, check_input, set_scale
 
 
@@ -134,26 +134,14 @@ class RFDNeXt(HipSRModel):
     _cin_map = block_cin_map
 
     def _extra_pack(self, packed, device):
-        store = self._store()
         for k in range(1, 5):
             b = f'B{k}.'
             # rc_1 = c1_r(x) + c1_d(x) as one 3x3
             w, bias = fold_center(self._leaf(b + 'c1_r').weight, self._leaf(b + 'c1_r').bias, self._leaf(b + 'c1_d').weight, self._leaf(b + 'c1_d').bias)
-            packed[b + 'c1_r#fold'] = pack_conv(w, bias).to(device)
-            if store == "f32" and self.winograd:
-                packed[b + 'c1_r#fold' + WINO] = pack_wino(w, bias).to(device)
-            if store != "f32":
-                packed[b + 'c1_r#fold' + S16] = pack_conv_s16(w, bias, store).to(device)
-            dw, pw1, pw2 = (self._leaf(b + f'esa.conv.{i}') for i in (0, 1, 3))
-            packed[b + 'esa.conv.0'] = pack_dw7(dw.weight, dw.bias).to(device)
-            for j, (a, wd) in enumerate(_hidden_slices(self.cm, store)):      # the per-op first 1x1: output-channel slices
-                ws, bs = pw1.weight[a:a + wd], pw1.bias[a:a + wd]
-                packed[b + f'esa.conv.1#o{j}'] = pack_conv(ws, bs).to(device)
-                if store != "f32":
-                    packed[b + f'esa.conv.1#o{j}' + S16] = pack_conv_s16(ws, bs, store).to(device)
-            if store != "f32":
-                p1, p2 = pack_cx_pw(pw1.weight, pw1.bias, pw2.weight, pw2.bias, store)
-                packed[b + 'esa.conv.1' + CX1], packed[b + 'esa.conv.3' + CX2] = p1.to(device), p2.to(device)
+            self._pack_own(packed, device, b + 'c1_r#fold', w, bias, wino=True)
+            pw1 = self._leaf(b + 'esa.conv.1')
+            for j, (a, wd) in enumerate(_hidden_slices(self.cm, self._store())):      # the per-op first 1x1: output-channel slices
+                self._pack_own(packed, device, b + f'esa.conv.1#o{j}', pw1.weight[a:a + wd], pw1.bias[a:a + wd])
 
     def _counted_convs(self, plan, o):
         """the ConvNeXt block's first 1x1 is one nn.Conv2d of 200 outputs however many slices launch it (c5 and c.0 carry their logical

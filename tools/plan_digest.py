@@ -1,8 +1,10 @@
 """Digest of every plan the networks build (no GPU): one line per (model, storage, flags, N x H x W) with len(plan.ops), plan.total,
-plan.total_lo and a SHA-256 over the finalized Op array and the buffer table, and one line per (model, storage, flags) with a SHA-256 over
-the packed weight blobs.  Weights are the constructor's under torch.manual_seed(0); plans are finalized against the fixed base
+plan.total_lo and a SHA-256 over the finalized Op array and the buffer table, and per (model, storage, flags) one line with a SHA-256 over the
+packed weight blobs and one (`costs`) with a SHA-256 over the cost entries of the ops of all those plans (HipSRModel.op_costs: names, kernel
+strings, flops and bytes of the benchmark's roofline leg) and their complexity terms (the model summary's counters).  Weights are the constructor's under torch.manual_seed(0); plans are finalized against the fixed base
 (0x10000000, plan.total) and blob addresses 4096 * (1 + rank of the name in sorted(model._packed)); a blob name that _packed does not hold
-raises.  Two trees whose outputs are equal launch the same descriptors: run it before and after a change to the plan builders and diff.
+raises.  Two trees whose outputs are equal launch the same descriptors: run it before and after a change to the plan builders and diff
+(tests/golden/plan_digests_14_networks.txt holds the output, of all the networks by now; tests/test_plan_digest.py compares).
 usage: plan_digest.py [--models NAME,...] > digest.txt"""
 import argparse, contextlib, hashlib, io, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,6 +14,17 @@ from ntire2022_esr_amd import _lib as L
 from ntire2022_esr_amd.engine import Plan
 
 R, M = pkg.RFDN, pkg.IMDN
+
+
+def _resdn():
+    """ResDN with the 3x3 identity in both MeanShift weights, which its packing insists on; the biases keep their seeded values"""
+    m = pkg.ResDN()
+    with torch.no_grad():
+        for name in ("sub_mean", "add_mean"):
+            m._leaf(name).weight.copy_(torch.eye(3)[:, :, None, None])
+    return m
+
+
 MODELS = {          # name -> (constructor, the flags its plans read besides hilo_skip (bf16 plans) and winograd (fp32 plans))
     "IMDN": (M, ()), "IMDN_nb7": (lambda: M(nb=7, act_mode='L'), ()), "IMDN_nc32": (lambda: M(nc=32), ()),
     "RFDN": (R, ("fuse_esa_lowres", "tight_pitch", "fuse_tail")), "RFDN_nf40": (lambda: R(nf=40), ("fuse_esa_lowres", "tight_pitch", "fuse_tail")),
@@ -23,9 +36,11 @@ MODELS = {          # name -> (constructor, the flags its plans read besides hil
     "FasterRFDN": (pkg.FasterRFDN, ("fuse_esa_lowres", "fuse_cascade")), "RFDNeXt": (pkg.RFDNeXt, ("tight_pitch", "fuse_cx")),
     "DWRFDN": (pkg.DWRFDN, ("tight_pitch", "fuse_pair")), "RePAFDN": (pkg.RePAFDN, ("fuse_esa_lowres", "fuse_pa_tail")),
     "ARFDN": (pkg.ARFDN, ("fuse_esa_lowres", "tight_pitch", "fuse_asym")),
-    "ResDN": (pkg.ResDN, ("fuse_esa_lowres", "fuse_resdb")),
+    "ResDN": (_resdn, ("fuse_esa_lowres", "fuse_resdb")), "MDGN": (pkg.MDGN, ("fuse_conv_prelu", "fuse_mdsa_gate")),
 }
-SHAPES = ((1, 15, 16), (2, 45, 70), (1, 339, 510), (32, 256, 256))      # the last one crosses the 256-tile threshold of the fused tails
+# 32 x 256 x 256 crosses the 256-tile threshold of the fused tails; at 3400 x 3400 (nothing is allocated) some fused kernels refuse the shape
+# and the plan keeps the per-op form (MDGN's 16-bit plans: 32 ops instead of 20), so the blobs of a fallback form are read too
+SHAPES = ((1, 15, 16), (2, 45, 70), (1, 339, 510), (32, 256, 256), (1, 3400, 3400))
 
 
 class Blob:
@@ -63,13 +78,16 @@ def build(name, store, flip=None):
     return m
 
 
-def plan_digest(m, shape, names=None):
-    """(len(ops), total, total_lo, sha256) of the plan of `m` for shape = (N, H, W); names: the blob names (default: m._packed's)"""
+def plan_digest(m, shape, names=None, costs=None):
+    """(len(ops), total, total_lo, sha256) of the plan of `m` for shape = (N, H, W); names: the blob names (default: m._packed's); costs: a
+    hashlib object that takes the plan's cost entries and complexity terms"""
     plan = Plan(*shape, m._store())
     m._build_plan(plan, m.in_nc)
     arr, _, _ = plan.finalize((0x10000000, plan.total), Blobs(m._packed if names is None else names))
     h = hashlib.sha256(bytes(arr))
     h.update(repr([(b.pitch, b.offset, b.h, b.w, b.esize, b.arena, b.blocked) for b in plan.buffers]).encode())
+    if costs is not None:
+        costs.update(repr(m.op_costs(plan, arr)).encode() + repr([m._complexity_terms(plan, o) for o in plan.ops]).encode())
     return len(plan.ops), plan.total, plan.total_lo, h.hexdigest()
 
 
@@ -81,27 +99,44 @@ def packed_digest(m):
     return h.hexdigest()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--models", default=",".join(MODELS))
-    for name in ap.parse_args().models.split(","):
+def cells(models=None):
+    """(model name, storage, flipped flag or None) of every cell: the defaults and each flag the plans of that storage read, inverted"""
+    for name in models or MODELS:
         for store in ("f32", "bf16", "f16"):
             # (of the models' own flags only fuse_esa_lowres shapes an fp32 plan)
             flags = [None] + [f for f in MODELS[name][1] if store != "f32" or f == "fuse_esa_lowres"]
             flags += ["hilo_skip"] * (name != "ESAN" and store == "bf16") + ["winograd"] * (store == "f32")
             for flip in flags:
-                cell = f"{name} {store} {flip or 'defaults'}"
-                try:
-                    m = build(name, store, flip)
-                except L.EsrError as e:                 # (FMEN refuses fp16 storage)
-                    print(f"{cell} refused: {e}")
-                    continue
-                print(f"{cell} packed {len(m._packed)} {packed_digest(m)}")
-                for shape in SHAPES:
-                    try:
-                        print(f"{cell} {'x'.join(map(str, shape))}", *plan_digest(m, shape))
-                    except L.EsrError as e:
-                        print(f"{cell} {'x'.join(map(str, shape))} refused: {e}")
+                yield name, store, flip
+
+
+def cell_lines(name, store, flip, names=None):
+    """(the built model or None, the output lines) of one cell; names: see plan_digest"""
+    cell = f"{name} {store} {flip or 'defaults'}"
+    try:
+        m = build(name, store, flip)
+    except L.EsrError as e:                             # (FMEN refuses fp16 storage)
+        return None, [f"{cell} refused: {e}"]
+    lines, costs = [f"{cell} packed {len(m._packed)} {packed_digest(m)}"], hashlib.sha256()
+    for shape in SHAPES:
+        try:
+            lines.append(" ".join([f"{cell} {'x'.join(map(str, shape))}"] + [str(v) for v in plan_digest(m, shape, names, costs)]))
+        except L.EsrError as e:
+            lines.append(f"{cell} {'x'.join(map(str, shape))} refused: {e}")
+    return m, lines + [f"{cell} costs {costs.hexdigest()}"]
+
+
+def arrange(per_cell):
+    """The tool's output from the cells' lines: first every cell's `packed` line and first four shapes, in the places they have had since the
+    fixture was first recorded, then every cell's later additions -- the largest shape and `costs` (a cell that refused has its one line)"""
+    cut = lambda lines: max(len(lines) - 2, 1)
+    return [l for lines in per_cell for l in lines[:cut(lines)]] + [l for lines in per_cell for l in lines[cut(lines):]]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default=",".join(MODELS))
+    print("\n".join(arrange([cell_lines(*cell)[1] for cell in cells(ap.parse_args().models.split(","))])))
 
 
 if __name__ == "__main__":
