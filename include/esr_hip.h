@@ -890,7 +890,7 @@ int    esr_conv_prelu(const esr_conv_desc* d, void* hip_stream);
  * esr_mdsa_gate_supported: 1 for such a descriptor; esr_mdsa_gate returns ESR_ERR_UNSUPPORTED for every other (fp32 storage included) and
  * launches nothing.  y is another tensor than f1 .. f3 and x: the n h w pitch elements behind out0.ptr may share no byte with those behind
  * the sources' pointers -- ESR_ERR_BAD_ARG otherwise (a slice of a source's own tensor included), as for a null in / res / out0 / wpacked or
- * a view that is misaligned or does not hold its channels (esr_pa_gate's rules).
+ * a view that is misaligned or does not hold its channels (csrc/esr_internal.h: esr_bytes_overlap over the whole tensors, esr_view_ok).
  * esr_pack_mdsa_gate (16-bit storage only; esr_packed_mdsa_gate_bytes(storage) bytes, 0 for fp32): [hi image | lo image | 64 fp32 b_f |
  * 64 fp32 a_f | 64 fp32 w_s | fp32 b_s, 12 bytes of zeros]; an image = [cout tile 4][K step 6][lane 64][8] 16-bit values, lane (row, kq)
  * element e of (mt, ks) = W_f[16 mt + row][32 ks + 8 kq + e]; hi = rnd(w), lo = rnd(w - hi).  b_f and b_s may be NULL (zeros).

@@ -307,23 +307,8 @@ int launch_asym(const AsymK& k, hipStream_t st)
     return esr_check_launch("asym_step_kernel launch");
 }
 
-inline bool as_s16(int storage) { return storage == ESR_STORE_BF16 || storage == ESR_STORE_F16; }
 inline int as_nkp(int cin) { return cin > 32 ? 2 : 1; }
 inline int as_frags(int cin) { return 2 * 3 * as_nkp(cin) * AS_NT + 2 * 3 * AS_NT; }
-
-// Does a byte that the kernel WRITES through view `o` (channels [coff, coff + oc) of every pixel) belong to what it READS through view `i`
-// (channels [coff, coff + ic))?  Two views on the same pixel grid -- the same pitch, their first pixels a whole number of pixels apart
-// after taking the channel offsets out -- meet only where their channel ranges do (slices of one concat tensor); any other pair meets
-// wherever the tensors' byte ranges do.  (A null pointer meets nothing.)
-bool as_meets(const esr_view& o, int oc, const esr_view& i, int ic, size_t npx)
-{
-    if (!o.ptr || !i.ptr) return false;
-    const char* ob = static_cast<const char*>(o.ptr);
-    const char* ib = static_cast<const char*>(i.ptr);
-    if (!(ob < ib + npx * i.pitch * 2 && ib < ob + npx * o.pitch * 2)) return false;
-    if (o.pitch != i.pitch || ((ob - ib) % ((ptrdiff_t)o.pitch * 2)) != 0) return true;
-    return o.coff < i.coff + ic && i.coff < o.coff + oc;
-}
 
 }  // namespace
 
@@ -341,7 +326,7 @@ int esr_pack_asym_s16(const float* w_l1, const float* b_l1, const float* w_m1, c
 {
     const size_t need = esr_packed_asym_s16_bytes(cin, cmid);
     if (!w_l1 || !w_m1 || !w_l2 || !w_m2 || !out || !need || out_bytes < need) return ESR_ERR_BAD_ARG;
-    if (compute != ESR_COMPUTE_BF16 && compute != ESR_COMPUTE_F16) return ESR_ERR_BAD_ARG;
+    if (!esr_is_s16(compute)) return ESR_ERR_BAD_ARG;
     memset(out, 0, need);
     char* o = static_cast<char*>(out);
     const int nkp = as_nkp(cin);
@@ -377,7 +362,7 @@ int esr_unpack_asym_s16(const void* packed, size_t packed_bytes, int cin, int cm
 {
     const size_t need = esr_packed_asym_s16_bytes(cin, cmid);
     if (!packed || !need || packed_bytes < need || !w_l1 || !w_m1 || !w_l2 || !w_m2 || !bias3) return ESR_ERR_BAD_ARG;
-    if (compute != ESR_COMPUTE_BF16 && compute != ESR_COMPUTE_F16) return ESR_ERR_BAD_ARG;
+    if (!esr_is_s16(compute)) return ESR_ERR_BAD_ARG;
     const char* o = static_cast<const char*>(packed);
     const int nkp = as_nkp(cin);
     size_t frag = 0;
@@ -407,7 +392,7 @@ int esr_unpack_asym_s16(const void* packed, size_t packed_bytes, int cin, int cm
 int esr_asym_step_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (!as_s16(d->storage) || d->compute != d->storage) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     const int cmid = d->post_cout;                                                // logical channels of d, a_l, a_m and out
     if (cmid < 17 || cmid > 32 || d->cin < 17 || d->cin > 64) return 0;
@@ -418,8 +403,8 @@ int esr_asym_step_supported(const esr_conv_desc* d)
     if (d->post_act != d->act) return 0;                                          // one activation for d, a_l, a_m and out
     if (d->split || d->tail_wpacked || d->tail_cat_c || d->tail_cout || d->tail_mid_act || d->tail_seg_stride16 || d->post2_wpacked || d->post2_out.ptr ||
         d->post2_cout || d->out1.ptr || d->border_bias || d->blocked8 || d->in_seg_stride || d->in_seg_chunks || d->wino_wpacked || d->hilo || d->hilo_stride) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
-    if ((double)d->n * ((d->w + AS_T - 1) / AS_T) * ((d->h + AS_T - 1) / AS_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, AS_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -430,13 +415,13 @@ int esr_asym_step(const esr_conv_desc* d, void* hip_stream)
     const int cmid = d->post_cout, c8 = esr_round_up(cmid, 8), y8 = esr_round_up(d->cout, 8);
     if (!esr_view_fits(d->in, 8, esr_round_up(d->cin, 8)) || !esr_view_fits(d->post_out, 8, c8) || !esr_view_fits(d->out0, 8, y8)) return ESR_ERR_BAD_ARG;
     if ((d->res.ptr && !esr_view_fits(d->res, 8, c8)) || (d->tail_cat.ptr && !esr_view_fits(d->tail_cat, 8, c8))) return ESR_ERR_BAD_ARG;
-    // neither output's bytes meet `in` (the neighbouring tiles read its halo), p1 or p2, or the other output
+    // neither output's bytes meet `in` (the neighbouring tiles read its halo), p1 or p2 (an absent one: a null view meets nothing), or the other output
     const size_t npx = (size_t)d->n * d->h * d->w;
     const esr_view* ins[3] = {&d->in, &d->res, &d->tail_cat};
     const int in_c[3] = {esr_round_up(d->cin, 8), c8, c8};
     for (int i = 0; i < 3; ++i)
-        if (as_meets(d->out0, y8, *ins[i], in_c[i], npx) || as_meets(d->post_out, c8, *ins[i], in_c[i], npx)) return ESR_ERR_BAD_ARG;
-    if (as_meets(d->out0, y8, d->post_out, c8, npx)) return ESR_ERR_BAD_ARG;
+        if (esr_views_meet(d->out0, y8, *ins[i], in_c[i], npx, 2) || esr_views_meet(d->post_out, c8, *ins[i], in_c[i], npx, 2)) return ESR_ERR_BAD_ARG;
+    if (esr_views_meet(d->out0, y8, d->post_out, c8, npx, 2)) return ESR_ERR_BAD_ARG;
     AsymK k;
     memset(&k, 0, sizeof(k));
     k.x = static_cast<const char*>(d->in.ptr);
@@ -456,9 +441,8 @@ int esr_asym_step(const esr_conv_desc* d, void* hip_stream)
     k.nch1 = esr_round_up(d->cin, 16) / 16;
     k.d_cout8 = c8; k.y_cout8 = y8;
     k.slope = esr_act_slope(d->act, d->slope);
-    k.tiles_x = (d->w + AS_T - 1) / AS_T;
-    k.tiles_y = (d->h + AS_T - 1) / AS_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, AS_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const bool bf16 = d->storage == ESR_STORE_BF16;
     if (d->res_mode == ESR_RES_PRE_ACT) return bf16 ? launch_asym<true, 1, true>(k, st) : launch_asym<false, 1, true>(k, st);

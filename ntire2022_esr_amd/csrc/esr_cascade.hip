@@ -294,14 +294,13 @@ int launch_cascade(const CascK& k, hipStream_t st)
 extern "C" int esr_refine_cascade_supported(const esr_chain_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->n_layers != 4 || d->act != ESR_ACT_LRELU || d->res_mode != ESR_RES_PRE_ACT) return 0;
     if (d->cin != RC_CIN || d->cmid != RC_CM || d->cout != RC_CM) return 0;
     if (d->post_wpacked || d->post2_wpacked) return 0;
     if (d->post_cout != RC_CM || d->post2_cout != RC_CM) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
-    if ((double)d->n * ((d->w + RC_T - 1) / RC_T) * ((d->h + RC_T - 1) / RC_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, RC_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -325,9 +324,8 @@ extern "C" int esr_refine_cascade_s16(const esr_chain_desc* d, void* hip_stream)
     k.d3_pitch = d->post_out.pitch; k.d3_coff = d->post_out.coff;
     k.r4_pitch = d->post2_out.pitch; k.r4_coff = d->post2_out.coff;
     k.slope = esr_act_slope(d->act, d->slope);
-    k.tiles_x = (d->w + RC_T - 1) / RC_T;
-    k.tiles_y = (d->h + RC_T - 1) / RC_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, RC_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     return d->storage == ESR_STORE_BF16 ? launch_cascade<true>(k, st) : launch_cascade<false>(k, st);
 }

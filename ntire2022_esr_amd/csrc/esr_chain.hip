@@ -693,8 +693,7 @@ int esr_conv_chain_supported(const esr_chain_desc* d)
 {
     if (d && d->res_mode == ESR_RES_GATE) return esr_hfab_supported(d);      // FMEN's HFAB: hfab_kernel (esr_hfab.hip)
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     // RLFB: three 3x3 layers over 48 physical channels, LeakyReLU / none, the third one + the chain's input after its activation, then a
     // 1x1 of three output tiles and a 1x1 of one (no activation on the second)
     if (d->n_layers != 3 || d->res_mode != ESR_RES_POST_ACT) return 0;
@@ -703,9 +702,8 @@ int esr_conv_chain_supported(const esr_chain_desc* d)
     if (!d->post_wpacked || !d->post2_wpacked || esr_round_up(d->post_cout, 16) != 48 || d->post2_cout <= 0 || d->post2_cout > 16) return 0;
     if (d->post_act != ESR_ACT_NONE && d->post_act != ESR_ACT_LRELU && d->post_act != ESR_ACT_RELU) return 0;
     if (d->h < 4) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0 || (double)d->h * d->w * d->post_out.pitch * 2.0 >= 1073741824.0 ||
-        (double)d->h * d->w * d->post2_out.pitch * 2.0 >= 1073741824.0)
-        return 0;                                            // per-image raw buffers < 1 GiB (the out-of-range markers CH_LOOB / CH_ROOB)
+    const double px = (double)d->h * d->w;                   // esr_image_below_1g: the out-of-range markers here are CH_LOOB / CH_ROOB
+    if (!esr_image_below_1g(px, d->in.pitch, 2) || !esr_image_below_1g(px, d->post_out.pitch, 2) || !esr_image_below_1g(px, d->post2_out.pitch, 2)) return 0;
     return 1;
 }
 

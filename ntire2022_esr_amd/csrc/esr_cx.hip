@@ -354,7 +354,7 @@ size_t esr_packed_cx_pw1_bytes(int cin, int cmid)
 int esr_pack_cx_pw1_s16(const float* w, const float* bias, int cin, int cmid, int compute, void* out, size_t out_bytes)
 {
     const size_t need = esr_packed_cx_pw1_bytes(cin, cmid);
-    if (!w || !out || !need || out_bytes < need || (compute != ESR_COMPUTE_BF16 && compute != ESR_COMPUTE_F16)) return ESR_ERR_BAD_ARG;
+    if (!w || !out || !need || out_bytes < need || !esr_is_s16(compute)) return ESR_ERR_BAD_ARG;
     const int nhp = cx_nhp(cmid);
     memset(out, 0, need);
     uint16_t* img = static_cast<uint16_t*>(out);
@@ -382,7 +382,7 @@ size_t esr_packed_cx_pw2_bytes(int cmid, int cout)
 int esr_pack_cx_pw2_s16(const float* w, const float* bias, int cmid, int cout, int compute, void* out, size_t out_bytes)
 {
     const size_t need = esr_packed_cx_pw2_bytes(cmid, cout);
-    if (!w || !out || !need || out_bytes < need || (compute != ESR_COMPUTE_BF16 && compute != ESR_COMPUTE_F16)) return ESR_ERR_BAD_ARG;
+    if (!w || !out || !need || out_bytes < need || !esr_is_s16(compute)) return ESR_ERR_BAD_ARG;
     const int nhp = cx_nhp(cmid);
     memset(out, 0, need);
     uint16_t* img = static_cast<uint16_t*>(out);
@@ -402,14 +402,13 @@ int esr_pack_cx_pw2_s16(const float* w, const float* bias, int cmid, int cout, i
 int esr_cx_block_supported(const esr_chain_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->n_layers != 3 || d->act != ESR_ACT_LRELU || d->res_mode != ESR_RES_POST_ACT) return 0;
     if (d->cin != d->cout || d->cin <= 32 || d->cin > CX_CMAX || d->cmid <= 128 || d->cmid > CX_MAXHP * 32) return 0;
     if (d->post_wpacked || d->post2_wpacked) return 0;
     if ((d->post_cout & 7) || d->post_cout < d->cout || d->post_cout > esr_round_up(d->cout, 16)) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
-    if ((double)d->n * ((d->w + CX_T - 1) / CX_T) * ((d->h + CX_T - 1) / CX_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, CX_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -433,9 +432,8 @@ int esr_cx_block_s16(const esr_chain_desc* d, void* hip_stream)
     k.nhp = cx_nhp(d->cmid);
     k.cout_store = d->post_cout;
     k.slope = esr_act_slope(d->act, d->slope);
-    k.tiles_x = (d->w + CX_T - 1) / CX_T;
-    k.tiles_y = (d->h + CX_T - 1) / CX_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, CX_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     return d->storage == ESR_STORE_BF16 ? launch_cx<true>(k, st) : launch_cx<false>(k, st);
 }

@@ -253,8 +253,7 @@ int launch_distill(const DistK& k, hipStream_t st)
 extern "C" int esr_distill_step_supported(const esr_chain_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->n_layers != 2 || d->act != ESR_ACT_RELU) return 0;
     if (d->res_mode != ESR_RES_NONE && d->res_mode != ESR_RES_PRE_ACT) return 0;
     if (d->cin < 17 || d->cin > 48 || d->cmid < 17 || d->cmid > 32 || d->cout < 17 || d->cout > 32) return 0;
@@ -262,7 +261,7 @@ extern "C" int esr_distill_step_supported(const esr_chain_desc* d)
     if (d->post_wpacked || d->post2_wpacked) return 0;
     if (d->post_cout < d->cmid || d->post_cout > esr_round_up(d->cmid, 16)) return 0;
     if (d->post2_cout < d->cout || d->post2_cout > esr_round_up(d->cout, 16)) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
     return 1;
 }
 
@@ -285,11 +284,9 @@ extern "C" int esr_distill_step_s16(const esr_chain_desc* d, void* hip_stream)
     k.y_pitch = d->post2_out.pitch; k.y_coff = d->post2_out.coff;
     k.cin = d->cin;
     k.d_cout8 = d8; k.y_cout8 = y8;
-    k.tiles_x = (d->w + DS_T - 1) / DS_T;
-    k.tiles_y = (d->h + DS_T - 1) / DS_T;
-    const double nt = (double)d->n * k.tiles_x * k.tiles_y;
-    if (nt >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
-    k.ntiles = (int)nt;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, DS_T);
+    if (tg.count >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const bool bf16 = d->storage == ESR_STORE_BF16;
     if (d->res_mode == ESR_RES_PRE_ACT) return bf16 ? launch_distill<true, 2, true>(k, st) : launch_distill<false, 2, true>(k, st);

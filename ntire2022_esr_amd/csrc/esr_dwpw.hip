@@ -239,14 +239,13 @@ extern "C" {
 int esr_dwpw_pair_supported(const esr_chain_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->n_layers != 4 || d->act != ESR_ACT_LRELU || d->res_mode != ESR_RES_PRE_ACT) return 0;
     if (d->cin != d->cout || d->cmid != d->cin || d->cin <= 32 || d->cin > DP_CMAX) return 0;
     if (d->post_wpacked || d->post2_wpacked) return 0;
     if ((d->post_cout & 7) || d->post_cout < d->cout || d->post_cout > esr_round_up(d->cout, 16)) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
-    if ((double)d->n * ((d->w + DP_T - 1) / DP_T) * ((d->h + DP_T - 1) / DP_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, DP_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -270,9 +269,8 @@ int esr_dwpw_pair_s16(const esr_chain_desc* d, void* hip_stream)
     k.c = d->cin; k.cp = esr_round_up(d->cin, 8); k.cq = esr_round_up(d->cin, 4);
     k.cout_store = d->post_cout;
     k.slope = esr_act_slope(d->act, d->slope);
-    k.tiles_x = (d->w + DP_T - 1) / DP_T;
-    k.tiles_y = (d->h + DP_T - 1) / DP_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, DP_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     return d->storage == ESR_STORE_BF16 ? launch_dwpw<true>(k, st) : launch_dwpw<false>(k, st);
 }

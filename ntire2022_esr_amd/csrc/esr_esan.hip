@@ -294,19 +294,17 @@ int launch_reshead(const ResHeadK& k, hipStream_t st)
 extern "C" int esr_resblock_head_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->cin != RH_C || d->cout != RH_C || d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     if (d->act != ESR_ACT_RELU) return 0;
     if (d->res_mode != ESR_RES_NONE && d->res_mode != ESR_RES_PRE_ACT) return 0;
     if (d->split > 0 && d->split < d->cout) return 0;
     if (d->post_cout <= 0 || d->post_cout > ESR_ESA_FP || d->post_act != ESR_ACT_NONE) return 0;
     if (d->post2_wpacked || d->tail_cat.ptr || d->tail_cat_c || d->border_bias || d->in_seg_stride || d->blocked8 || d->hilo || d->wino_wpacked) return 0;
-    // per-image tensors < 1 GiB: 32-bit byte offsets, the out-of-range marker
     const double px = (double)d->h * d->w;
-    if (px * d->in.pitch * 2.0 >= 1073741824.0) return 0;
-    if (d->res_mode != ESR_RES_NONE && px * d->res.pitch * 2.0 >= 1073741824.0) return 0;
-    if ((double)d->n * ((d->w + RH_T - 1) / RH_T) * ((d->h + RH_T - 1) / RH_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g(px, d->in.pitch, 2)) return 0;
+    if (d->res_mode != ESR_RES_NONE && !esr_image_below_1g(px, d->res.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, RH_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -337,9 +335,8 @@ extern "C" int esr_resblock_head_s16(const esr_conv_desc* d, void* hip_stream)
     k.u_pitch = d->out1.pitch; k.u_coff = d->out1.coff;
     k.c1_pitch = d->post_out.pitch; k.c1_coff = d->post_out.coff;
     k.c1_cout8 = c8;
-    k.tiles_x = (d->w + RH_T - 1) / RH_T;
-    k.tiles_y = (d->h + RH_T - 1) / RH_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, RH_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const bool bf16 = d->storage == ESR_STORE_BF16;
     if (g) return bf16 ? launch_reshead<true, true>(k, st) : launch_reshead<false, true>(k, st);

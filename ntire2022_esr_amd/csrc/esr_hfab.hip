@@ -237,13 +237,12 @@ int launch_hfab(const HfabK& k, hipStream_t st)
 int esr_hfab_supported(const esr_chain_desc* d)
 {
     if (!d || d->res_mode != ESR_RES_GATE || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return 0;
-    if (d->compute != (d->storage == ESR_STORE_BF16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->n_layers != 4 || d->act != ESR_ACT_LRELU || !(d->slope >= 0.f && d->slope <= 1.f)) return 0;
     if (d->cin != d->cout || d->cin < 33 || d->cin > 64 || d->cmid < 1 || d->cmid > 16) return 0;
     if (d->post_wpacked || d->post2_wpacked) return 0;
     if (d->post_cout < d->cout || d->post_cout > esr_round_up(d->cout, 16)) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
     return 1;
 }
 
@@ -266,11 +265,9 @@ int esr_hfab_s16(const esr_chain_desc* d, void* hip_stream)
     k.cin = d->cin;
     k.cout8 = cout8;
     k.slope = d->slope;
-    k.tiles_x = (d->w + HF_T - 1) / HF_T;
-    k.tiles_y = (d->h + HF_T - 1) / HF_T;
-    const double nt = (double)d->n * k.tiles_x * k.tiles_y;
-    if (nt >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
-    k.ntiles = (int)nt;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, HF_T);
+    if (tg.count >= ESR_INDEX_LIMIT) return ESR_ERR_UNSUPPORTED;
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const bool bf16 = d->storage == ESR_STORE_BF16;
     if (esr_round_up(d->cin, 16) == 48) return bf16 ? launch_hfab<true, 3>(k, st) : launch_hfab<false, 3>(k, st);

@@ -73,6 +73,42 @@ constexpr double ESR_RAW_LIMIT = 2147483647.0;
 constexpr long long ESR_INDEX_LIMIT = 2147483647LL;
 static inline bool esr_fits_raw(double pixels, int pitch, int elem_bytes) { return pixels * pitch * elem_bytes < ESR_RAW_LIMIT; }
 
+// The fused 16-bit kernels address a tiled view with 32-bit BYTE offsets inside one image and ADD an out-of-range marker (0x80000000,
+// esr_chain also 0x40000000) to the offset of a lane or a row that lies outside the image: one image of such a view (pixels x pitch x
+// element size) stays below 1 GiB, not 2, so that no sum with a marker in it wraps to a valid offset
+constexpr double ESR_IMAGE_LIMIT = 1073741824.0;
+static inline bool esr_image_below_1g(double pixels, int pitch, int elem_bytes) { return pixels * pitch * elem_bytes < ESR_IMAGE_LIMIT; }
+
+// The T x T output tiles of a launch: a predicate holds `count` below ESR_INDEX_LIMIT, after which its launcher's ntiles is (int)count
+struct esr_tile_grid { int tiles_x, tiles_y; double count; };
+static inline esr_tile_grid esr_tiles(int n, int h, int w, int T)
+{
+    const int tx = (w + T - 1) / T, ty = (h + T - 1) / T;
+    return {tx, ty, (double)n * tx * ty};
+}
+
+// 16-bit storage (`fmt` is an ESR_STORE_* or an ESR_COMPUTE_* value: the two enums agree on the 16-bit formats, static_assert above), and
+// the rule of the fused 16-bit kernels: 16-bit storage, and the MFMA operand type is the storage type
+static inline bool esr_is_s16(int fmt) { return fmt == ESR_STORE_BF16 || fmt == ESR_STORE_F16; }
+static inline bool esr_s16_pair(int storage, int compute) { return esr_is_s16(storage) && compute == storage; }
+
+// Do the byte ranges [a, a + an) and [b, b + bn) meet?  A null pointer meets nothing.
+static inline bool esr_bytes_overlap(const char* a, size_t an, const char* b, size_t bn) { return a && b && a < b + bn && b < a + an; }
+
+// Does a byte that a launch WRITES through view `o` (channels [coff, coff + oc) of each of `npx` pixels, pad slots up to the granule included)
+// belong to what it READS through view `i` (channels [coff, coff + ic))?  A view's ptr is its tensor's base (coff lies inside the pitch), so a
+// tensor is the npx * pitch elements behind it.  Two views of one pixel grid -- the same pitch, their first pixels a whole number of pixels
+// apart -- meet only where their channel ranges do (slices of one concat tensor); any other pair meets wherever the tensors' byte ranges
+// do.  A null pointer on either side meets nothing.
+static inline bool esr_views_meet(const esr_view& o, int oc, const esr_view& i, int ic, size_t npx, int elem_bytes)
+{
+    const char* ob = static_cast<const char*>(o.ptr);
+    const char* ib = static_cast<const char*>(i.ptr);
+    if (!esr_bytes_overlap(ob, npx * o.pitch * elem_bytes, ib, npx * i.pitch * elem_bytes)) return false;
+    if (o.pitch != i.pitch || ((ob - ib) % ((ptrdiff_t)o.pitch * elem_bytes)) != 0) return true;
+    return o.coff < i.coff + ic && i.coff < o.coff + oc;
+}
+
 // "the residual is the input": a pre-activation residual over the view the conv reads, which the kernel then adds from its staged input
 // tile.  `chunk`: the channel counts agree after rounding up to it -- 16 for the 16-bit kernels (K chunks), 1 for the fp32 ones
 static inline bool esr_res_is_input(const esr_conv_desc* d, int chunk)

@@ -281,26 +281,6 @@ int launch_mdsa_gate(const MgK& k, hipStream_t st)
     return esr_check_launch("mdsa_gate_kernel launch");
 }
 
-inline bool md_s16(int storage) { return storage == ESR_STORE_BF16 || storage == ESR_STORE_F16; }
-
-// do the byte ranges [a, a + an) and [b, b + bn) meet?
-inline bool md_overlap(const char* a, size_t an, const char* b, size_t bn)
-{
-    return a && b && a < b + bn && b < a + an;
-}
-
-// Does a byte written through view `o` (channels [coff, coff + oc)) belong to what is read through view `i` (channels [coff, coff + ic))?  Two
-// views of one pixel grid -- the same pitch, their first pixels a whole number of pixels apart -- meet only where their channel ranges do;
-// any other pair wherever the tensors' byte ranges do (esr_prelu's rule)
-inline bool md_meets(const esr_view& o, int oc, const esr_view& i, int ic, size_t npx)
-{
-    const char* ob = static_cast<const char*>(o.ptr);
-    const char* ib = static_cast<const char*>(i.ptr);
-    if (!(ob < ib + npx * i.pitch * 2 && ib < ob + npx * o.pitch * 2)) return false;
-    if (o.pitch != i.pitch || ((ob - ib) % ((ptrdiff_t)o.pitch * 2)) != 0) return true;
-    return o.coff < i.coff + ic && i.coff < o.coff + oc;
-}
-
 }  // namespace
 
 extern "C" {
@@ -308,15 +288,15 @@ extern "C" {
 int esr_conv_prelu_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (!md_s16(d->storage) || d->compute != d->storage) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     if (d->cin != CP_C || d->cout != CP_C) return 0;
     if (d->act != ESR_ACT_NONE || d->res_mode != ESR_RES_NONE) return 0;
     if (d->split || d->res.ptr || d->out1.ptr || d->tail_cat.ptr || d->tail_cat_c || d->tail_cout || d->tail_mid_act || d->tail_seg_stride16 || d->post_wpacked ||
         d->post_out.ptr || d->post_cout || d->post_act || d->post2_wpacked || d->post2_out.ptr || d->post2_cout || d->border_bias || d->blocked8 ||
         d->in_seg_stride || d->in_seg_chunks || d->wino_wpacked || d->hilo || d->hilo_stride) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
-    if ((double)d->n * ((d->w + CP_T - 1) / CP_T) * ((d->h + CP_T - 1) / CP_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, CP_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -326,7 +306,7 @@ int esr_conv_prelu(const esr_conv_desc* d, void* hip_stream)
     if (!esr_conv_prelu_supported(d)) return ESR_ERR_UNSUPPORTED;
     if (!esr_view_ok(d->in, 8, CP_C) || !esr_view_ok(d->out0, 8, CP_C)) return ESR_ERR_BAD_ARG;
     // no byte of the output belongs to the input: the neighbouring tiles read it as halo
-    if (md_meets(d->out0, CP_C, d->in, CP_C, (size_t)d->n * d->h * d->w)) return ESR_ERR_BAD_ARG;
+    if (esr_views_meet(d->out0, CP_C, d->in, CP_C, (size_t)d->n * d->h * d->w, 2)) return ESR_ERR_BAD_ARG;
     CpK k;
     memset(&k, 0, sizeof(k));
     k.x = static_cast<const char*>(d->in.ptr);
@@ -336,16 +316,15 @@ int esr_conv_prelu(const esr_conv_desc* d, void* hip_stream)
     k.N = d->n; k.H = d->h; k.W = d->w;
     k.in_pitch = d->in.pitch; k.in_coff = d->in.coff;
     k.y_pitch = d->out0.pitch; k.y_coff = d->out0.coff;
-    k.tiles_x = (d->w + CP_T - 1) / CP_T;
-    k.tiles_y = (d->h + CP_T - 1) / CP_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, CP_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     return d->storage == ESR_STORE_BF16 ? launch_conv_prelu<true>(k, st) : launch_conv_prelu<false>(k, st);
 }
 
 size_t esr_packed_mdsa_gate_bytes(int storage)
 {
-    return md_s16(storage) ? (size_t)MG_BLOB : 0;
+    return esr_is_s16(storage) ? (size_t)MG_BLOB : 0;
 }
 
 int esr_pack_mdsa_gate(const float* w_f, const float* b_f, const float* a_f, const float* w_s, const float* b_s, int storage, void* out, size_t out_bytes)
@@ -398,7 +377,7 @@ int esr_unpack_mdsa_gate(const void* packed, size_t packed_bytes, int storage, f
 int esr_mdsa_gate_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (!md_s16(d->storage) || d->compute != d->storage) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->ksize != 1 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     if (d->cin != MG_K || d->cout != MG_C) return 0;
     if (d->act != ESR_ACT_NONE || d->res_mode != ESR_RES_GATE) return 0;
@@ -422,12 +401,12 @@ int esr_mdsa_gate(const esr_conv_desc* d, void* hip_stream)
     k.x = static_cast<const char*>(d->res.ptr);
     k.y = static_cast<char*>(d->out0.ptr);
     k.f_step = planar ? d->in_seg_stride : (long long)MG_C * 2;
-    // y shares no byte with f1 .. f3 or x: the op is not specified in place (esr_pa_gate's rule: whole tensors)
+    // y shares no byte with f1 .. f3 or x: the op is not specified in place (esr_bytes_overlap over the whole tensors)
     const size_t npx = (size_t)d->n * d->h * d->w;
     const size_t f_n = npx * d->in.pitch * 2, x_n = npx * d->res.pitch * 2, y_n = npx * d->out0.pitch * 2;
     for (int i = 0; i < (planar ? 3 : 1); ++i)
-        if (md_overlap(k.y, y_n, k.f + i * k.f_step, f_n)) return ESR_ERR_BAD_ARG;
-    if (md_overlap(k.y, y_n, k.x, x_n)) return ESR_ERR_BAD_ARG;
+        if (esr_bytes_overlap(k.y, y_n, k.f + i * k.f_step, f_n)) return ESR_ERR_BAD_ARG;
+    if (esr_bytes_overlap(k.y, y_n, k.x, x_n)) return ESR_ERR_BAD_ARG;
     k.w = static_cast<const char*>(d->wpacked);
     k.npix = (long long)npx;
     k.ngroups = (int)((k.npix + 15) / 16);

@@ -388,14 +388,6 @@ int launch_pa_tail(const PtK& k, hipStream_t st)
     return esr_check_launch("pa_tail_kernel launch");
 }
 
-// do the byte ranges [a, a + an) and [b, b + bn) meet?  (a null pointer meets nothing)
-inline bool pa_overlap(const char* a, size_t an, const char* b, size_t bn)
-{
-    return a && b && a < b + bn && b < a + an;
-}
-
-inline bool pa_s16(int storage) { return storage == ESR_STORE_BF16 || storage == ESR_STORE_F16; }
-
 }  // namespace
 
 extern "C" {
@@ -403,7 +395,7 @@ extern "C" {
 size_t esr_packed_pa_gate_bytes(int c, int storage)
 {
     if (c <= 0 || c > PA_CMAX || storage < ESR_STORE_F32 || storage > ESR_STORE_F16) return 0;
-    return (size_t)(pa_s16(storage) ? 2 * PA_IMG16 : PA_IMG32) + PA_CMAX * 4;
+    return (size_t)(esr_is_s16(storage) ? 2 * PA_IMG16 : PA_IMG32) + PA_CMAX * 4;
 }
 
 int esr_pack_pa_gate(const float* w_oi, const float* bias, int c, int storage, void* out, size_t out_bytes)
@@ -416,7 +408,7 @@ int esr_pack_pa_gate(const float* w_oi, const float* bias, int c, int storage, v
     for (int mt = 0; mt < 4; ++mt)
         for (int lane = 0; lane < 64; ++lane) {
             const int row = mt * 16 + (lane & 15), kq = lane >> 4;
-            if (pa_s16(storage)) {
+            if (esr_is_s16(storage)) {
                 for (int ks = 0; ks < 2; ++ks)
                     for (int e = 0; e < 8; ++e) {
                         const float v = wt(row, (2 * ks + e / 4) * 16 + kq * 4 + e % 4);
@@ -434,7 +426,7 @@ int esr_pack_pa_gate(const float* w_oi, const float* bias, int c, int storage, v
                     }
             }
         }
-    float* b = reinterpret_cast<float*>(o + (pa_s16(storage) ? 2 * PA_IMG16 : PA_IMG32));
+    float* b = reinterpret_cast<float*>(o + (esr_is_s16(storage) ? 2 * PA_IMG16 : PA_IMG32));
     for (int i = 0; i < c; ++i) b[i] = bias ? bias[i] : 0.f;
     return ESR_OK;
 }
@@ -442,16 +434,16 @@ int esr_pack_pa_gate(const float* w_oi, const float* bias, int c, int storage, v
 int esr_pa_gate_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (d->storage != ESR_STORE_F32 && !pa_s16(d->storage)) return 0;
+    if (d->storage != ESR_STORE_F32 && !esr_is_s16(d->storage)) return 0;
     if (d->compute != d->storage) return 0;
-    const int gran = pa_s16(d->storage) ? 8 : 4;
+    const int gran = esr_is_s16(d->storage) ? 8 : 4;
     if (d->ksize != 1 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     if (d->cin <= 32 || d->cin > PA_CMAX) return 0;
     if ((d->cout & (gran - 1)) || d->cout < d->cin || d->cout > esr_round_up(d->cin, 16)) return 0;
     if (d->act != ESR_ACT_NONE || (d->res_mode != ESR_RES_NONE && d->res_mode != ESR_RES_POST_ACT)) return 0;
     if (d->split || d->tail_wpacked || d->tail_cat.ptr || d->tail_cat_c || d->post_wpacked || d->post2_wpacked || d->border_bias || d->blocked8 || d->in_seg_stride || d->wino_wpacked) return 0;
     if (d->hilo & ~(ESR_HILO_RES | ESR_HILO_OUT)) return 0;
-    if (d->hilo && (!pa_s16(d->storage) || d->hilo_stride <= 0 || (d->hilo_stride & 15))) return 0;
+    if (d->hilo && (!esr_is_s16(d->storage) || d->hilo_stride <= 0 || (d->hilo_stride & 15))) return 0;
     if ((d->hilo & ESR_HILO_RES) && d->res_mode == ESR_RES_NONE) return 0;
     if ((double)d->n * d->h * d->w >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
@@ -461,7 +453,7 @@ int esr_pa_gate(const esr_conv_desc* d, void* hip_stream)
 {
     if (!d || !d->in.ptr || !d->out0.ptr || !d->wpacked) return ESR_ERR_BAD_ARG;
     if (!esr_pa_gate_supported(d)) return ESR_ERR_UNSUPPORTED;
-    const bool s16 = pa_s16(d->storage);
+    const bool s16 = esr_is_s16(d->storage);
     const int gran = s16 ? 8 : 4, cp = esr_round_up(d->cin, gran);
     const bool has_s = d->res_mode != ESR_RES_NONE;
     if (has_s && !d->res.ptr) return ESR_ERR_BAD_ARG;
@@ -480,7 +472,7 @@ int esr_pa_gate(const esr_conv_desc* d, void* hip_stream)
     const char* outs[2] = {k.y, k.y_lo};
     for (const char* o : outs)
         for (int i = 0; i < 3; ++i)
-            if (pa_overlap(o, out_n, ins[i], in_n[i])) return ESR_ERR_BAD_ARG;
+            if (esr_bytes_overlap(o, out_n, ins[i], in_n[i])) return ESR_ERR_BAD_ARG;
     k.w = static_cast<const char*>(d->wpacked);
     k.npix = (long long)d->n * d->h * d->w;
     k.ngroups = (int)((k.npix + 15) / 16);
@@ -497,7 +489,7 @@ int esr_pa_gate(const esr_conv_desc* d, void* hip_stream)
 int esr_pa_tail_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if (!pa_s16(d->storage) || d->compute != d->storage) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     if (d->cin <= 32 || d->cin > PA_CMAX) return 0;
     if ((d->cout & 7) || d->cout < d->cin || d->cout > esr_round_up(d->cin, 16)) return 0;
@@ -506,8 +498,8 @@ int esr_pa_tail_supported(const esr_conv_desc* d)
     if (d->hilo & ~(ESR_HILO_RES | ESR_HILO_OUT)) return 0;
     if (d->hilo && (d->hilo_stride <= 0 || (d->hilo_stride & 15))) return 0;
     if ((d->hilo & ESR_HILO_RES) && d->res_mode == ESR_RES_NONE) return 0;
-    if ((double)d->h * d->w * d->in.pitch * 2.0 >= 1073741824.0) return 0;        // per-image input < 1 GiB: 32-bit offsets, the out-of-range marker
-    if ((double)d->n * ((d->w + PT_T - 1) / PT_T) * ((d->h + PT_T - 1) / PT_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (!esr_image_below_1g((double)d->h * d->w, d->in.pitch, 2)) return 0;
+    if (esr_tiles(d->n, d->h, d->w, PT_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -533,7 +525,7 @@ int esr_pa_tail(const esr_conv_desc* d, void* hip_stream)
     const char* outs[2] = {k.y, k.y_lo};
     for (const char* o : outs)
         for (int i = 0; i < 3; ++i)
-            if (pa_overlap(o, out_n, ins[i], in_n[i])) return ESR_ERR_BAD_ARG;
+            if (esr_bytes_overlap(o, out_n, ins[i], in_n[i])) return ESR_ERR_BAD_ARG;
     k.w3 = static_cast<const char*>(d->wpacked);
     k.wg = static_cast<const char*>(d->tail_wpacked);
     k.N = d->n; k.H = d->h; k.W = d->w;
@@ -541,9 +533,8 @@ int esr_pa_tail(const esr_conv_desc* d, void* hip_stream)
     k.s_pitch = d->res.pitch; k.s_coff = d->res.coff;
     k.y_pitch = d->out0.pitch; k.y_coff = d->out0.coff;
     k.c = d->cin; k.cout_store = d->cout;
-    k.tiles_x = (d->w + PT_T - 1) / PT_T;
-    k.tiles_y = (d->h + PT_T - 1) / PT_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, PT_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const bool bf16 = d->storage == ESR_STORE_BF16;
     if (d->cin > 48) return bf16 ? launch_pa_tail<true, 4>(k, st) : launch_pa_tail<false, 4>(k, st);

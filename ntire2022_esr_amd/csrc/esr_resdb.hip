@@ -163,20 +163,6 @@ int pr_sources(const esr_conv_desc* d, const esr_view* v[PR_MAXSRC], int c[PR_MA
     return n;
 }
 
-// Does a byte written through view `o` (channels [coff, coff + oc)) belong to what is read through view `i` (channels [coff, coff + ic))?  Two
-// views of one pixel grid -- the same pitch, their first pixels a whole number of pixels apart -- meet only where their channel ranges do;
-// any other pair wherever the tensors' byte ranges do.  A view's ptr is its tensor's base (coff lies inside the pitch), so a tensor is the
-// npx * pitch elements behind it.  `oc` counts what the launch WRITES (pad slots up to the granule included), `ic` what it reads.
-bool pr_meets(const esr_view& o, int oc, const esr_view& i, int ic, size_t npx, int es)
-{
-    const char* ob = static_cast<const char*>(o.ptr);
-    const char* ib = static_cast<const char*>(i.ptr);
-    if (!(ob < ib + npx * i.pitch * es && ib < ob + npx * o.pitch * es)) return false;
-    if (o.pitch != i.pitch || ((ob - ib) % ((ptrdiff_t)o.pitch * es)) != 0) return true;
-    return o.coff < i.coff + ic && i.coff < o.coff + oc;
-}
-
-
 // ---- esr_resdb_step: one ResDB step (team43_resdn.py:93-106) as ONE launch on 16-bit storage ---------------------------------------------------
 //
 //     u = (prelu(in, a_e))~          in = cat(x, e0, e1): 48 + 16 NX channels             e = W_e . u + b_e (fp32)
@@ -455,7 +441,7 @@ int esr_prelu(const esr_conv_desc* d, void* hip_stream)
     bool vec = true;
     for (int i = 0; i < n; ++i) {
         if (!v[i]->ptr || !esr_view_fits(*v[i], g, c[i])) return ESR_ERR_BAD_ARG;           // (only the c[i] channels are read: never a pad slot)
-        if (pr_meets(d->out0, cstore, *v[i], c[i], npx, es)) return ESR_ERR_BAD_ARG;
+        if (esr_views_meet(d->out0, cstore, *v[i], c[i], npx, es)) return ESR_ERR_BAD_ARG;
         vec = vec && c[i] % g == 0;
     }
     PreluK k;
@@ -493,14 +479,14 @@ static int rs_count16(int channels, int lo, int hi)
 int esr_resdb_step_supported(const esr_conv_desc* d)
 {
     if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
-    if ((d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) || d->compute != d->storage) return 0;
+    if (!esr_s16_pair(d->storage, d->compute)) return 0;
     if (d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return 0;
     if (d->cin != 48 || d->cout != 48) return 0;                                                  // n = 48
     if (rs_count16(d->post_cout, 1, 3) < 0 || rs_count16(d->tail_cat_c, 0, 2) < 0) return 0;        // d = 16: 1..3 distilled outputs, 0..2 extra inputs
     if (d->act != ESR_ACT_NONE || d->post_act != ESR_ACT_NONE || d->res_mode != ESR_RES_NONE) return 0;
     if (d->split || d->tail_cout || d->tail_mid_act || d->tail_seg_stride16 || d->post2_wpacked || d->post2_out.ptr || d->post2_cout || d->out1.ptr ||
         d->border_bias || d->blocked8 || d->in_seg_stride || d->in_seg_chunks || d->wino_wpacked || d->hilo || d->hilo_stride) return 0;
-    if ((double)d->n * ((d->w + RS_T - 1) / RS_T) * ((d->h + RS_T - 1) / RS_T) >= (double)ESR_INDEX_LIMIT) return 0;
+    if (esr_tiles(d->n, d->h, d->w, RS_T).count >= (double)ESR_INDEX_LIMIT) return 0;
     return 1;
 }
 
@@ -517,8 +503,8 @@ int esr_resdb_step(const esr_conv_desc* d, void* hip_stream)
     const esr_view* ins[3] = {&d->in, &d->res, &d->tail_cat};
     const int in_c[3] = {48, 16, 16};
     for (int i = 0; i <= nx; ++i)
-        if (pr_meets(d->out0, 48, *ins[i], in_c[i], npx, 2) || pr_meets(d->post_out, 16 * nd, *ins[i], in_c[i], npx, 2)) return ESR_ERR_BAD_ARG;
-    if (pr_meets(d->out0, 48, d->post_out, 16 * nd, npx, 2)) return ESR_ERR_BAD_ARG;
+        if (esr_views_meet(d->out0, 48, *ins[i], in_c[i], npx, 2) || esr_views_meet(d->post_out, 16 * nd, *ins[i], in_c[i], npx, 2)) return ESR_ERR_BAD_ARG;
+    if (esr_views_meet(d->out0, 48, d->post_out, 16 * nd, npx, 2)) return ESR_ERR_BAD_ARG;
     ResdbK k;
     memset(&k, 0, sizeof(k));
     k.x = static_cast<const char*>(d->in.ptr);
@@ -535,9 +521,8 @@ int esr_resdb_step(const esr_conv_desc* d, void* hip_stream)
     k.e1_pitch = d->tail_cat.pitch; k.e1_coff = d->tail_cat.coff;
     k.d_pitch = d->post_out.pitch; k.d_coff = d->post_out.coff;
     k.y_pitch = d->out0.pitch; k.y_coff = d->out0.coff;
-    k.tiles_x = (d->w + RS_T - 1) / RS_T;
-    k.tiles_y = (d->h + RS_T - 1) / RS_T;
-    k.ntiles = d->n * k.tiles_x * k.tiles_y;
+    const esr_tile_grid tg = esr_tiles(d->n, d->h, d->w, RS_T);
+    k.tiles_x = tg.tiles_x; k.tiles_y = tg.tiles_y; k.ntiles = (int)tg.count;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     return d->storage == ESR_STORE_BF16 ? launch_resdb_nx<true>(k, nx, nd, st) : launch_resdb_nx<false>(k, nx, nd, st);
 }

@@ -986,7 +986,7 @@ static S16Path s16_select(const esr_conv_desc* d, bool any_range)
 // residual, no activation on the 1x1; from 256 tiles of 16 x 16
 static bool rfdb_tail_takes(const esr_conv_desc* d)
 {
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return false;
+    if (!esr_is_s16(d->storage)) return false;
     if (!d->tail_wpacked || !d->wpacked || d->ksize != 3 || d->in_layout != ESR_NHWC || d->out_layout != ESR_NHWC) return false;
     const int nch = esr_round_up(d->cin, 16) / 16;
     if ((nch != 3 && nch != 4) || d->cout < 17 || d->cout > 32 || d->tail_cat_c != 96) return false;
@@ -1187,7 +1187,7 @@ int esr_conv_tail_supported(const esr_conv_desc* d) { return d && rfdb_tail_take
 
 int esr_conv_post_supported(const esr_conv_desc* d)
 {
-    if (!d || !d->post_wpacked || (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16)) return 0;
+    if (!d || !d->post_wpacked || !esr_is_s16(d->storage)) return 0;
     int a, b, c, r;
     size_t l;
     return s16_post_plan(d, esr_round_up(d->cout, 16) / 16, esr_round_up(d->cin, 16) / 16, &a, &b, &c, &r, &l) == ESR_OK;
@@ -1256,7 +1256,7 @@ extern "C" int esr_pack_input_s16(const esr_conv_desc* d, void* hip_stream)
 {
     if (!d || !d->in.ptr || !d->out0.ptr || d->n <= 0 || d->h <= 0 || d->w <= 0) return ESR_ERR_BAD_ARG;
     if (d->cin <= 0 || d->cin > 4) return ESR_ERR_UNSUPPORTED;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return ESR_ERR_BAD_ARG;
+    if (!esr_is_s16(d->storage)) return ESR_ERR_BAD_ARG;
     if (!esr_view_fits(d->out0, 8, 16)) return ESR_ERR_BAD_ARG;
     const long long hw = (long long)d->h * d->w, npix = hw * d->n;
     const long long want = (npix + 255) / 256;
@@ -1287,7 +1287,7 @@ int esr_s16_block_waves(const esr_conv_desc* d)
 int esr_conv2d_s16(const esr_conv_desc* d, void* hip_stream)
 {
     const bool bf16 = d->storage == ESR_STORE_BF16;
-    if (d->storage != ESR_STORE_BF16 && d->storage != ESR_STORE_F16) return ESR_ERR_BAD_ARG;
+    if (!esr_is_s16(d->storage)) return ESR_ERR_BAD_ARG;
     if (d->compute != (bf16 ? ESR_COMPUTE_BF16 : ESR_COMPUTE_F16)) return ESR_ERR_BAD_ARG;   // operand type = storage type
     if (d->in_layout != ESR_NHWC) return ESR_ERR_UNSUPPORTED;                                  // the NCHW head runs on conv_f32_kernel
     if (d->blocked8) return ESR_ERR_UNSUPPORTED;                                               // an fp32 feature
