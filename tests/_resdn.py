@@ -181,10 +181,10 @@ def _sparse(rows, cols, per_row, g):
     return w
 
 
-def step_case(kind, store, hw, nx, nd, seed=0, b_e=None):
+def step_case(kind, store, hw, nx, nd, seed=0, b_e=None, n=2):
     """inputs of one step: kind "grid" -- x and extras in {-1, 0, 1}, three +-1 weights per expansion row and two per compression filter,
     integer biases in -1 .. 1, slopes drawn from {-2, -1/2, 1/2, 2}; "random" -- randn data, randn weights scaled by 1 / sqrt(fan-in), slopes
-    over the checkpoint's range.  Batch 2."""
+    over the checkpoint's range.  Batch n."""
     dt = DT[store]
     h, w = hw
     cin = NF + ND * nx
@@ -192,12 +192,12 @@ def step_case(kind, store, hw, nx, nd, seed=0, b_e=None):
     if kind == "grid":
         draw = lambda *s: torch.randint(-1, 2, s, generator=g).float()
         pick = lambda c: torch.tensor([-2.0, -0.5, 0.5, 2.0])[torch.randint(0, 4, (c,), generator=g)]
-        x, extras = draw(2, h, w, NF), [draw(2, h, w, ND) for _ in range(nx)]
+        x, extras = draw(n, h, w, NF), [draw(n, h, w, ND) for _ in range(nx)]
         a_e, a_c = pick(cin), pick(NF)
         w_e, w_c = _sparse(NF + ND * nd, cin, 3, g), _sparse(NF, NF * 9, 2, g).reshape(NF, NF, 3, 3)
         be, bc = draw(NF + ND * nd), draw(NF)
     else:
-        x, extras = torch.randn(2, h, w, NF, generator=g), [torch.randn(2, h, w, ND, generator=g) for _ in range(nx)]
+        x, extras = torch.randn(n, h, w, NF, generator=g), [torch.randn(n, h, w, ND, generator=g) for _ in range(nx)]
         a_e, a_c = random_slopes(cin, seed + 1), random_slopes(NF, seed + 2)
         w_e = torch.randn(NF + ND * nd, cin, generator=g) / cin ** 0.5
         w_c = torch.randn(NF, NF, 3, 3, generator=g) / (9 * NF) ** 0.5

@@ -61,7 +61,9 @@ CHAIN_CASES = [pytest.param(*nhw, *RLFN_WIDTHS, id="-".join(str(v) for v in nhw)
 @pytest.mark.parametrize("compute", ["bf16", "f16"])
 @pytest.mark.parametrize("n,h,w,nf,mf,f", CHAIN_CASES)
 def test_chain_equals_separate_launches(compute, n, h, w, nf, mf, f, strip_groups):
-    """ragged strips (w not a multiple of the strip width), one-strip and one-segment images, several jobs per block: v and c1 bit for bit"""
+    """ragged strips (w not a multiple of the strip width), one-strip and one-segment images, several strips and segments per image: v and c1
+    bit for bit.  Every case here is a few dozen jobs at most, so every block has ONE job (chain_geometry_g keeps per_block == 1); a block's
+    hand-over from job to job runs in tests/test_gpu_walk.py, on batches of more than 1024 jobs"""
     from ntire2022_esr_amd import ops
     dt = DT[compute]
     ws, bs, w5, b5, w1, b1 = _weights(n * 1000 + h + w, nf, mf, f)

@@ -67,14 +67,15 @@ def _dw7_ref(x, w0, b0, pad_value=None):
 _cases = {}
 
 
-def _case(store, nhw, c=50, m=200, bias=None):
+def _case(store, nhw, c=50, m=200, bias=None, seed=0):
     """v rounded to the storage type, the weights, the 1x1 weights as the fused kernel's blobs hold them (rounded once) -- computed once per
     case and left unchanged.  bias: a large dw7 bias (the border case), the first 1x1 small: at |t| ~ 3 the hidden values would reach 8, where
-    ONE 16-bit step of a hidden value, which no launch stores, times a weight of the second 1x1 is larger than the bound of the result"""
-    key = (store, nhw, c, m, bias)
+    ONE 16-bit step of a hidden value, which no launch stores, times a weight of the second 1x1 is larger than the bound of the result.
+    seed: other data of the same kind (tests/_walk_cases.py)"""
+    key = (store, nhw, c, m, bias, seed)
     if key not in _cases:
         n, h, w = nhw
-        g = torch.Generator().manual_seed(10000 * c + 100 * h + w + (store == "f16") + (7 if bias else 0))
+        g = torch.Generator().manual_seed(10000 * c + 100 * h + w + (store == "f16") + (7 if bias else 0) + 1000003 * seed)
         dt = DT[store]
         x = torch.randn(n, h, w, c, generator=g).to(dt)
         rnd = lambda *s: torch.randn(*s, generator=g)

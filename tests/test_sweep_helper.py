@@ -221,8 +221,14 @@ def test_within_rejects_an_fp16_tanh_sigmoid(store):
 def test_every_kernel_is_swept_or_exempt():
     """the __global__ kernels of csrc/ (parsed as tests/test_kernel_names.py parses them) against test_gpu_value_sweep.SWEPT and .EXEMPT: a
     kernel added without a sweep case fails here, on the CPU"""
+    import glob
+    import importlib
+    import os
     import test_gpu_value_sweep as V
     from test_kernel_names import _sources
+    # the newer sweeps live in files of their own and enter themselves into V.SWEPT when imported: a run of this file alone imports them here
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_sweep_*.py"))):
+        importlib.import_module(os.path.basename(path)[:-3])
     tmpl = re.compile(r"__global__\s+(?:__launch_bounds__\s*\((?:[^()]|\([^()]*\))*\)\s*)?void\s+(\w+)\s*\(")
     kernels = {m.group(1) for _, text in _sources(strip=True) for m in tmpl.finditer(text)}
     assert len(kernels) >= 35, sorted(kernels)
