@@ -19,22 +19,10 @@ RES_NONE, RES_PRE_ACT, RES_POST_ACT, RES_GATE = 0, 1, 2, 3                  # RE
 NHWC, NCHW_IN, NCHW_SHUFFLE4 = 0, 1, 2
 BLOCKED_IN, BLOCKED_OUT1, BLOCKED_OUT0, BLOCKED_RES = 1, 2, 4, 8          # esr_conv_desc.blocked8 bits (ABI v6 / v9)
 HILO_IN, HILO_RES, HILO_OUT = 1, 2, 4                                     # esr_conv_desc.hilo bits (ABI v10)
-OP_CONV, OP_CONV3X3S2, OP_MAXPOOL7S3, OP_ESA_APPLY, OP_DWCONV, OP_BSCONV, OP_PACK_INPUT, OP_ESA_LOWRES, OP_CONV_CHAIN = 0, 1, 2, 3, 4, 5, 6, 7, 8
-OP_MAXPOOL7S7 = 9                                                         # EFDN's ESA pooling (esr_maxpool7s7_f32)
-OP_DISTILL_STEP = 10                                                      # BMDN's distillation step (esr_distill_step_s16 on Op.chain)
-OP_RESBLOCK_HEAD = 11                                                     # ESAN's residual-block head (esr_resblock_head_s16 on Op.conv)
-OP_REFINE_CASCADE = 12                                                    # FasterRFDN's refinement cascade (esr_refine_cascade_s16 on Op.chain)
-OP_DWCONV7 = 13                                                           # depthwise 7x7 (esr_dwconv7x7 on Op.conv)
-OP_CX_BLOCK = 14                                                          # RFDNeXt's ConvNeXt block (esr_cx_block_s16 on Op.chain)
-OP_DWPW_PAIR = 15                                                         # team 35's depthwise-pointwise residual pair (esr_dwpw_pair_s16 on Op.chain)
-OP_ESA_UNSHUFFLE = 16                                                     # team 35's ESA low-resolution branch (esr_esa_unshuffle_f32 on Op.esa)
-OP_PA_GATE = 17                                                           # RePAFDN's pixel attention + long skip (esr_pa_gate on Op.conv)
-OP_PA_TAIL = 18                                                           # ... with the 3x3 in front of it in the same launch (esr_pa_tail on Op.conv)
-OP_ASYM_STEP = 19                                                         # ARFDN's asymmetric-convolution step (esr_asym_step on Op.conv)
-OP_PRELU = 20                                                             # ResDN's per-channel PReLU in front of a convolution (esr_prelu on Op.conv)
-OP_RESDB_STEP = 21                                                        # a ResDB step of ResDN in one launch (esr_resdb_step on Op.conv)
-OP_CONV_PRELU = 22                                                        # MDGN's 64 -> 64 3x3 with the PReLU in its epilogue (esr_conv_prelu on Op.conv)
-OP_MDSA_GATE = 23                                                         # the end of an MDSA block of MDGN in one launch (esr_mdsa_gate on Op.conv)
+# esr_op kinds (ESR_OP_* of include/esr_hip.h); LAUNCHERS below says what each one runs
+(OP_CONV, OP_CONV3X3S2, OP_MAXPOOL7S3, OP_ESA_APPLY, OP_DWCONV, OP_BSCONV, OP_PACK_INPUT, OP_ESA_LOWRES, OP_CONV_CHAIN, OP_MAXPOOL7S7, OP_DISTILL_STEP,
+ OP_RESBLOCK_HEAD, OP_REFINE_CASCADE, OP_DWCONV7, OP_CX_BLOCK, OP_DWPW_PAIR, OP_ESA_UNSHUFFLE, OP_PA_GATE, OP_PA_TAIL, OP_ASYM_STEP, OP_PRELU, OP_RESDB_STEP,
+ OP_CONV_PRELU, OP_MDSA_GATE) = range(24)
 CHAIN_MAX_LAYERS = 4
 ESA_MAX_LAYERS = 3
 ESA_FP = 16
@@ -169,6 +157,35 @@ EXPORTS = [
     "esr_event_pair_ms", "esr_bw_probe",
 ]
 
+# op kind -> (the entry point esr_run_ops dispatches to, the Op field it reads, its esr_*_supported predicate or None): THE place that names a
+# launcher.  lib() types them from it, ops._launch and the engine's op classes look them up (tests/test_launcher_table.py holds it to the C switch)
+LAUNCHERS = {
+    OP_CONV: ("esr_conv2d_f32", "conv", None),
+    OP_CONV3X3S2: ("esr_conv3x3s2_f32", "esa", None),
+    OP_MAXPOOL7S3: ("esr_maxpool7s3_f32", "esa", None),
+    OP_ESA_APPLY: ("esr_esa_apply_f32", "esa", None),
+    OP_DWCONV: ("esr_dwconv3x3_f32", "conv", None),
+    OP_BSCONV: ("esr_bsconv_f32", "bs", None),
+    OP_PACK_INPUT: ("esr_pack_input_s16", "conv", None),
+    OP_ESA_LOWRES: ("esr_esa_lowres_f32", "lo", None),
+    OP_CONV_CHAIN: ("esr_conv_chain_s16", "chain", "esr_conv_chain_supported"),                    # RLFN's RLFB; with RES_GATE FMEN's HFAB
+    OP_MAXPOOL7S7: ("esr_maxpool7s7_f32", "esa", None),                                            # EFDN's ESA pooling
+    OP_DISTILL_STEP: ("esr_distill_step_s16", "chain", "esr_distill_step_supported"),              # BMDN's distillation step
+    OP_RESBLOCK_HEAD: ("esr_resblock_head_s16", "conv", "esr_resblock_head_supported"),            # ESAN's residual-block head
+    OP_REFINE_CASCADE: ("esr_refine_cascade_s16", "chain", "esr_refine_cascade_supported"),        # FasterRFDN's refinement cascade
+    OP_DWCONV7: ("esr_dwconv7x7", "conv", "esr_dwconv7x7_supported"),
+    OP_CX_BLOCK: ("esr_cx_block_s16", "chain", "esr_cx_block_supported"),                          # RFDNeXt's ConvNeXt block
+    OP_DWPW_PAIR: ("esr_dwpw_pair_s16", "chain", "esr_dwpw_pair_supported"),                       # team 35's depthwise-pointwise residual pair
+    OP_ESA_UNSHUFFLE: ("esr_esa_unshuffle_f32", "esa", None),                                      # team 35's ESA low-resolution branch
+    OP_PA_GATE: ("esr_pa_gate", "conv", "esr_pa_gate_supported"),                                  # RePAFDN's pixel attention + long skip
+    OP_PA_TAIL: ("esr_pa_tail", "conv", "esr_pa_tail_supported"),                                  # ... with the 3x3 in front of it in the same launch
+    OP_ASYM_STEP: ("esr_asym_step", "conv", "esr_asym_step_supported"),                            # ARFDN's asymmetric-convolution step
+    OP_PRELU: ("esr_prelu", "conv", "esr_prelu_supported"),                                        # ResDN's per-channel PReLU in front of a convolution
+    OP_RESDB_STEP: ("esr_resdb_step", "conv", "esr_resdb_step_supported"),                         # a ResDB step of ResDN
+    OP_CONV_PRELU: ("esr_conv_prelu", "conv", "esr_conv_prelu_supported"),                         # MDGN's 64 -> 64 3x3 with the PReLU in its epilogue
+    OP_MDSA_GATE: ("esr_mdsa_gate", "conv", "esr_mdsa_gate_supported"),                            # the end of an MDSA block of MDGN
+}
+
 _lib = None
 
 
@@ -221,8 +238,6 @@ def lib():
     L.esr_unpack_wino_f32.restype = ci
     L.esr_wino_supported.argtypes = [ctypes.POINTER(ConvDesc)]
     L.esr_wino_supported.restype = ci
-    L.esr_conv2d_f32.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_conv2d_f32.restype = ci
     L.esr_conv_block_waves.argtypes = [ctypes.POINTER(ConvDesc)]
     L.esr_conv_block_waves.restype = ci
     L.esr_run_ops.argtypes = [ctypes.POINTER(Op), ci, vp]
@@ -231,19 +246,15 @@ def lib():
     L.esr_packed_dense_bytes.restype = sz
     L.esr_pack_dense_f32.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz]
     L.esr_pack_dense_f32.restype = ci
-    for fn in (L.esr_conv3x3s2_f32, L.esr_maxpool7s3_f32, L.esr_maxpool7s7_f32, L.esr_esa_apply_f32):
-        fn.argtypes = [ctypes.POINTER(EsaDesc), vp]
-        fn.restype = ci
-    L.esr_esa_lowres_f32.argtypes = [ctypes.POINTER(EsaLowresDesc), vp]
-    L.esr_esa_lowres_f32.restype = ci
+    descs = dict(Op._fields_)
+    for run, field, pred in LAUNCHERS.values():               # int run(const desc*, stream); int pred(const desc*)
+        for fn, more in ((run, [vp]), (pred, [])):
+            if fn is not None:
+                getattr(L, fn).argtypes, getattr(L, fn).restype = [ctypes.POINTER(descs[field])] + more, ci
     L.esr_packed_dw_bytes.argtypes = [ci]
     L.esr_packed_dw_bytes.restype = sz
     L.esr_pack_dw_f32.argtypes = [vp, vp, ci, vp, sz]
     L.esr_pack_dw_f32.restype = ci
-    L.esr_dwconv3x3_f32.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_dwconv3x3_f32.restype = ci
-    L.esr_bsconv_f32.argtypes = [ctypes.POINTER(BsDesc), vp]
-    L.esr_bsconv_f32.restype = ci
     L.esr_channel_attention_f32.argtypes = [ctypes.POINTER(CaDesc), vp]
     L.esr_channel_attention_f32.restype = ci
     L.esr_tensor2uint_u8.argtypes = [vp, vp, ci, ci, ci, ctypes.c_float, vp]
@@ -273,30 +284,10 @@ def lib():
     L.esr_packed_apply_post_bytes.restype = sz
     L.esr_pack_apply_post.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, sz]
     L.esr_pack_apply_post.restype = ci
-    L.esr_conv_chain_supported.argtypes = [ctypes.POINTER(ChainDesc)]
-    L.esr_conv_chain_supported.restype = ci
-    L.esr_conv_chain_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
-    L.esr_conv_chain_s16.restype = ci
-    L.esr_distill_step_supported.argtypes = [ctypes.POINTER(ChainDesc)]
-    L.esr_distill_step_supported.restype = ci
-    L.esr_distill_step_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
-    L.esr_distill_step_s16.restype = ci
-    L.esr_resblock_head_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_resblock_head_supported.restype = ci
-    L.esr_resblock_head_s16.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_resblock_head_s16.restype = ci
-    L.esr_refine_cascade_supported.argtypes = [ctypes.POINTER(ChainDesc)]
-    L.esr_refine_cascade_supported.restype = ci
-    L.esr_refine_cascade_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
-    L.esr_refine_cascade_s16.restype = ci
     L.esr_packed_dw7_bytes.argtypes = [ci]
     L.esr_packed_dw7_bytes.restype = sz
     L.esr_pack_dw7_f32.argtypes = [vp, vp, ci, vp, sz]
     L.esr_pack_dw7_f32.restype = ci
-    L.esr_dwconv7x7_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_dwconv7x7_supported.restype = ci
-    L.esr_dwconv7x7.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_dwconv7x7.restype = ci
     L.esr_packed_cx_pw1_bytes.argtypes = [ci, ci]
     L.esr_packed_cx_pw1_bytes.restype = sz
     L.esr_pack_cx_pw1_s16.argtypes = [vp, vp, ci, ci, ci, vp, sz]
@@ -305,66 +296,28 @@ def lib():
     L.esr_packed_cx_pw2_bytes.restype = sz
     L.esr_pack_cx_pw2_s16.argtypes = [vp, vp, ci, ci, ci, vp, sz]
     L.esr_pack_cx_pw2_s16.restype = ci
-    L.esr_cx_block_supported.argtypes = [ctypes.POINTER(ChainDesc)]
-    L.esr_cx_block_supported.restype = ci
-    L.esr_cx_block_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
-    L.esr_cx_block_s16.restype = ci
-    L.esr_dwpw_pair_supported.argtypes = [ctypes.POINTER(ChainDesc)]
-    L.esr_dwpw_pair_supported.restype = ci
-    L.esr_dwpw_pair_s16.argtypes = [ctypes.POINTER(ChainDesc), vp]
-    L.esr_dwpw_pair_s16.restype = ci
-    L.esr_esa_unshuffle_f32.argtypes = [ctypes.POINTER(EsaDesc), vp]
-    L.esr_esa_unshuffle_f32.restype = ci
     L.esr_packed_pa_gate_bytes.argtypes = [ci, ci]
     L.esr_packed_pa_gate_bytes.restype = sz
     L.esr_pack_pa_gate.argtypes = [vp, vp, ci, ci, vp, sz]
     L.esr_pack_pa_gate.restype = ci
-    L.esr_pa_gate_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_pa_gate_supported.restype = ci
-    L.esr_pa_gate.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_pa_gate.restype = ci
-    L.esr_pa_tail_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_pa_tail_supported.restype = ci
-    L.esr_pa_tail.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_pa_tail.restype = ci
     L.esr_packed_asym_s16_bytes.argtypes = [ci, ci]
     L.esr_packed_asym_s16_bytes.restype = sz
     L.esr_pack_asym_s16.argtypes = [vp] * 8 + [ci, ci, ci, vp, sz]
     L.esr_pack_asym_s16.restype = ci
     L.esr_unpack_asym_s16.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp, vp, vp]
     L.esr_unpack_asym_s16.restype = ci
-    L.esr_asym_step_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_asym_step_supported.restype = ci
-    L.esr_asym_step.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_asym_step.restype = ci
     L.esr_packed_prelu_bytes.argtypes = [ci]
     L.esr_packed_prelu_bytes.restype = sz
     L.esr_pack_prelu.argtypes = [vp, ci, vp, sz]
     L.esr_pack_prelu.restype = ci
     L.esr_unpack_prelu.argtypes = [vp, sz, ci, vp]
     L.esr_unpack_prelu.restype = ci
-    L.esr_prelu_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_prelu_supported.restype = ci
-    L.esr_prelu.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_prelu.restype = ci
-    L.esr_resdb_step_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_resdb_step_supported.restype = ci
-    L.esr_resdb_step.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_resdb_step.restype = ci
-    L.esr_conv_prelu_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_conv_prelu_supported.restype = ci
-    L.esr_conv_prelu.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_conv_prelu.restype = ci
     L.esr_packed_mdsa_gate_bytes.argtypes = [ci]
     L.esr_packed_mdsa_gate_bytes.restype = sz
     L.esr_pack_mdsa_gate.argtypes = [vp, vp, vp, vp, vp, ci, vp, sz]
     L.esr_pack_mdsa_gate.restype = ci
     L.esr_unpack_mdsa_gate.argtypes = [vp, sz, ci, vp, vp, vp, vp, vp]
     L.esr_unpack_mdsa_gate.restype = ci
-    L.esr_mdsa_gate_supported.argtypes = [ctypes.POINTER(ConvDesc)]
-    L.esr_mdsa_gate_supported.restype = ci
-    L.esr_mdsa_gate.argtypes = [ctypes.POINTER(ConvDesc), vp]
-    L.esr_mdsa_gate.restype = ci
     L.esr_graph_create.argtypes = [ctypes.POINTER(Op), ci, vp, vp, ctypes.POINTER(vp)]
     L.esr_graph_create.restype = ci
     L.esr_graph_launch.argtypes = [vp, vp, vp, vp]

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import descs
 
 
 def _ptr(t):
@@ -519,6 +520,9 @@ def _addr(buf, base):
 
 
 def _view(v, base):
+    """the esr_view of an op operand (Buffer | (Buffer, coff, channels)); None, an absent operand, stays None"""
+    if v is None:
+        return None
     if isinstance(v, Buffer):
         v = (v, 0, v.pitch)
     buf, coff, _ = v
@@ -594,10 +598,15 @@ class EsaLayer:
 
 
 class _Op:
-    """What every op kind provides: encode(op, plan, base, weights) fills its esr_op (Plan.finalize), cost(plan, desc) is its
-    HipSRModel.op_costs entry (desc: the finalized esr_op or None), counted_convs(plan) the nn.Conv2d calls of the reference it
-    stands for (HipSRModel._counted_convs), blobs(plan) the weight blobs its encode reads as `weights[name]`: [(name, kind, source leaf
-    paths), ...] -- what HipSRModel._repack builds for the op (_PACKERS[kind]) or expects from the network's _extra_pack."""
+    """What every op kind provides: OP, its esr_op kind (a row of L.LAUNCHERS), encode(op, plan, base, weights) fills its esr_op
+    (Plan.finalize), cost(plan, desc) is its HipSRModel.op_costs entry (desc: the finalized esr_op or None), counted_convs(plan) the nn.Conv2d
+    calls of the reference it stands for (HipSRModel._counted_convs), blobs(plan) the weight blobs its encode reads as `weights[name]`:
+    [(name, kind, source leaf paths), ...] -- what HipSRModel._repack builds for the op (_PACKERS[kind]) or expects from the network's _extra_pack."""
+
+    def desc(self, op):
+        """marks `op` as this kind -> the descriptor in it that the kind's launcher reads"""
+        op.kind = self.OP
+        return getattr(op, L.LAUNCHERS[self.OP][1])
 
     def counted_convs(self, plan):
         return []
@@ -618,12 +627,11 @@ class Pack(_Op):
     """16-bit plans: the NCHW fp32 input packed to 16-bit hi / lo slots (esr_pack_input_s16) for the head convolution"""
     dst: Buffer
     cin: int
-    kind = "pack"
+    kind, OP = "pack", L.OP_PACK_INPUT
     src = INPUT
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_PACK_INPUT
-        d = op.conv
+        d = self.desc(op)
         d.n, d.h, d.w, d.cin, d.storage = plan.n, plan.h, plan.w, self.cin, L.STORE[plan.store]
         d.out0 = _view(self.dst, base)
 
@@ -657,7 +665,7 @@ class Conv(_Op):
     bs_of: str = None          # this dense 3x3 is that BSConvU (merged weights): its algorithmic flops and counter terms are the BSConvU's
     head: int = None           # set by Plan.conv on a 16-bit plan's head: the logical input channels
     hilo: int = 0              # L.HILO_IN | HILO_RES | HILO_OUT: src / res / dst are Plan.pair() hi + lo pairs (esr_conv_desc.hilo)
-    kind = "conv"
+    kind, OP = "conv", L.OP_CONV
 
     def __post_init__(self):
         if self.cin_alg is None:
@@ -677,8 +685,7 @@ class Conv(_Op):
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
         lowres = self.hw is not None
-        op.kind = L.OP_CONV
-        d = op.conv
+        d = self.desc(op)
         d.n, d.h, d.w = plan.n, plan.h, plan.w
         if lowres:
             d.h, d.w = self.hw
@@ -875,7 +882,7 @@ class Dw(_Op):
     hw: tuple = None
     res: object = None         # a view added before / behind the activation (res_mode), as Conv's
     res_mode: int = L.RES_NONE
-    kind = "dw"
+    kind, OP = "dw", L.OP_DWCONV
 
     def blobs(self, plan):
         # a low-resolution map that is a whole dense buffer is stored whole, pad channels (zeros: zero weights, zero bias) included:
@@ -885,23 +892,11 @@ class Dw(_Op):
         return [_blob(self.w, DWPAD if pad else BASE)]
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_DWCONV
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        if self.hw is not None:
-            d.h, d.w = self.hw
-        d.cin = d.cout = self.c
-        d.ksize = 3
-        d.act, d.slope = self.act, self.slope
-        d.in_layout = d.out_layout = L.NHWC
-        d.inp, d.out0 = _view(self.src, base), _view(self.dst, base)
-        if self.res is not None:
-            d.res, d.res_mode = _view(self.res, base), self.res_mode
-        d.storage = 0 if self.hw is not None else L.STORE[plan.store]
         (w, kind, _), = self.blobs(plan)
-        if kind == DWPAD:
-            d.cin = d.cout = 16
-        d.wpacked = ctypes.c_void_p(weights[w].data_ptr())
+        lowres = self.hw is not None                          # a low-resolution map is fp32 in every plan; the DWPAD image has 16 channels
+        descs.dwconv3x3(self.desc(op), (plan.n, *self.hw) if lowres else plan.nhw, 0 if lowres else plan.st,
+                        x=_view(self.src, base), w=weights[w].data_ptr(), c=16 if kind == DWPAD else self.c, act=self.act, slope=self.slope,
+                        y=_view(self.dst, base), res=_view(self.res, base), res_mode=self.res_mode if self.res is not None else L.RES_NONE)
 
     def cost(self, plan, desc):
         npix, e_act = (plan.npix, plan.esize) if self.hw is None else (plan.n * self.hw[0] * self.hw[1], 4)
@@ -923,19 +918,11 @@ class Dw7(_Op):
     src: object
     dst: object
     c: int
-    kind = "dw7"
+    kind, OP = "dw7", L.OP_DWCONV7
     reads = (("w", DW7),)
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_DWCONV7
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        d.cin = d.cout = self.c
-        d.ksize = 7
-        d.in_layout = d.out_layout = L.NHWC
-        d.inp, d.out0 = _view(self.src, base), _view(self.dst, base)
-        d.storage = L.STORE[plan.store]
-        d.wpacked = ctypes.c_void_p(weights[self.w].data_ptr())
+        descs.dwconv7x7(self.desc(op), plan.nhw, plan.st, x=_view(self.src, base), w=weights[self.w].data_ptr(), c=self.c, y=_view(self.dst, base))
 
     def cost(self, plan, desc):
         npix, es = plan.npix, plan.esize
@@ -962,7 +949,7 @@ class Bs(_Op):
     res: object = None
     res_mode: int = L.RES_NONE
     distill: Post = None
-    kind = "bs"
+    kind, OP = "bs", L.OP_BSCONV
 
     def blobs(self, plan):                                    # 16-bit storage: hi + lo 1x1 blobs (esr_pack_conv_s16)
         sfx = S16 if plan.esize == 2 else BASE
@@ -970,8 +957,7 @@ class Bs(_Op):
 
     def encode(self, op, plan, base, weights):
         st = L.STORE[plan.store]
-        op.kind = L.OP_BSCONV
-        d = op.bs
+        d = self.desc(op)
         d.storage = st
         d.n, d.h, d.w, d.cin, d.c = plan.n, plan.h, plan.w, self.cin, self.cout
         d.act, d.slope, d.res_mode = self.act, self.slope, self.res_mode
@@ -1003,12 +989,11 @@ class S2(_Op):
     src: Buffer
     dst: Buffer
     f: int
-    kind = "s2"
+    kind, OP = "s2", L.OP_CONV3X3S2
     reads = (("w", BASE),)
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_CONV3X3S2
-        e = op.esa
+        e = self.desc(op)
         e.n, e.h, e.w, e.h_lo, e.w_lo = plan.n, self.src.h, self.src.w, self.dst.h, self.dst.w
         e.x, e.y = _view(self.src, base), _view(self.dst, base)
         e.storage = L.STORE[plan.store]                       # reads the full-resolution conv1 map
@@ -1029,11 +1014,10 @@ class Pool(_Op):
     """ESA's 7x7 / stride-3 max pooling (esr_maxpool7s3_f32)"""
     src: Buffer
     dst: Buffer
-    kind = "pool"
+    kind, OP = "pool", L.OP_MAXPOOL7S3
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_MAXPOOL7S3
-        e = op.esa
+        e = self.desc(op)
         e.n, e.h, e.w, e.h_lo, e.w_lo = plan.n, self.src.h, self.src.w, self.dst.h, self.dst.w
         e.x, e.y = _view(self.src, base), _view(self.dst, base)
 
@@ -1047,11 +1031,10 @@ class Pool7(_Op):
     """EFDN's ESA pooling, max_pool2d(7, stride 7, padding 1) of the full-resolution conv1 map (esr_maxpool7s7_f32)"""
     src: Buffer
     dst: Buffer
-    kind = "pool7"
+    kind, OP = "pool7", L.OP_MAXPOOL7S7
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_MAXPOOL7S7
-        e = op.esa
+        e = self.desc(op)
         e.n, e.h, e.w, e.h_lo, e.w_lo = plan.n, self.src.h, self.src.w, self.dst.h, self.dst.w
         e.x, e.y = _view(self.src, base), _view(self.dst, base)
         e.storage = L.STORE[plan.store]                       # reads the full-resolution conv1 map
@@ -1064,18 +1047,18 @@ class Pool7(_Op):
 @dataclass
 class _Fused(_Op):
     """ONE op in place of a run of ops, which stay attached as `replaces`: weights, complexity counters and algorithmic costs are theirs.
-    Where the kernel takes only some shapes the class names the C ABI's `predicate` (esr_*_supported), the esr_op `field` it reads and the
-    kernel in words (`what`), and states the structure it stands for in check(): Plan._fuse asks the predicate about the descriptor
+    Where the kernel takes only some shapes its row of L.LAUNCHERS names the C ABI's predicate (esr_*_supported); the class names the
+    kernel in words (`what`) and states the structure it stands for in check(): Plan._fuse asks the predicate about the descriptor
     `encode` fills before it fuses, Plan.finalize once more."""
     replaces: list
-    predicate = None
 
     def check(self):
         pass
 
     def supported(self, op):
         """does the kernel take the descriptor that `encode` filled into `op`?"""
-        return self.predicate is None or bool(getattr(L.lib(), self.predicate)(ctypes.byref(getattr(op, self.field))))
+        _, field, predicate = L.LAUNCHERS[self.OP]
+        return predicate is None or bool(getattr(L.lib(), predicate)(ctypes.byref(getattr(op, field))))
 
     def counted_convs(self, plan):
         return [c for o in self.replaces for c in o.counted_convs(plan)]
@@ -1107,7 +1090,7 @@ class Lowres(_Fused):
     f: int
     w: str
     layers: list
-    kind = "lowres"
+    kind, OP = "lowres", L.OP_ESA_LOWRES
 
     def own_blobs(self, plan):                                # the layers in the plain dense layout; kind 1: the depthwise half as it is
         out = [_blob(self.w)] if self.w is not None else []
@@ -1118,8 +1101,7 @@ class Lowres(_Fused):
         return out
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_ESA_LOWRES
-        d = op.lo
+        d = self.desc(op)
         d.n, d.h, d.w, d.f, d.storage, d.n_layers = plan.n, plan.h, plan.w, self.f, L.STORE[plan.store], len(self.layers)
         d.x = _view(self.src, base)
         d.w_s2 = ctypes.c_void_p(weights[self.w].data_ptr()) if self.w is not None else None
@@ -1153,8 +1135,7 @@ class Chain(_Fused):
     """A block's 3x3 convolutions as ONE esr_conv_chain_s16 op -- see Plan.chain (gate=False: rlfb_chain_kernel) and Plan.hfab
     (gate=True: hfab_kernel)."""
     gate: bool = False
-    kind = "chain"
-    predicate, field = "esr_conv_chain_supported", "chain"
+    kind, OP = "chain", L.OP_CONV_CHAIN
     what = property(lambda self: "HFAB" if self.gate else "chain")
 
     def check(self):
@@ -1169,26 +1150,16 @@ class Chain(_Fused):
             assert last.dst is None and last.res is sub[0].src and last.post is not None and last.post.post2 is not None
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
-        op.kind = L.OP_CONV_CHAIN
-        d = op.chain
-        sub = self.replaces
-        first, last = sub[0], sub[-1]
-        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, len(sub)
-        d.cin, d.cmid, d.cout = first.cin, first.cout, last.cout
-        d.act, d.slope, d.res_mode = first.act, first.slope, last.res_mode
-        d.storage = d.compute = st
-        d.inp = _view(first.src, base)
-        for l, so in enumerate(sub):
-            d.wpacked[l] = weights[so.w + S16].data_ptr()
-        if self.gate:                                         # HFAB: the gated result goes to post_out
-            d.post_out, d.post_cout = _view(last.dst, base), _stored_width(last.dst, last.cout)
-            return
-        t, t2 = last.post, last.post.post2
-        d.post_wpacked, d.post_out = ctypes.c_void_p(weights[t.w + POST].data_ptr()), _view(t.dst, base)
-        d.post_cout, d.post_act = _stored_width(t.dst, t.cout), t.act
-        d.post2_wpacked, d.post2_out = ctypes.c_void_p(weights[t2.w + POST].data_ptr()), _view(t2.dst, base)
-        d.post2_cout = t2.cout
+        first, last = self.replaces[0], self.replaces[-1]
+        t = last.post
+        common = dict(x=_view(first.src, base), w=[weights[so.w + S16].data_ptr() for so in self.replaces], cin=first.cin, cmid=first.cout,
+                      cout=last.cout, act=first.act, slope=first.slope)
+        if self.gate:
+            descs.hfab(self.desc(op), plan.nhw, plan.st, **common, y=_view(last.dst, base), y_width=_stored_width(last.dst, last.cout))
+        else:
+            descs.chain(self.desc(op), plan.nhw, plan.st, **common, res_mode=last.res_mode, post_w=weights[t.w + POST].data_ptr(), v=_view(t.dst, base),
+                        v_width=_stored_width(t.dst, t.cout), post_act=t.act, post2_w=weights[t.post2.w + POST].data_ptr(),
+                        c1=_view(t.post2.dst, base), c1_width=t.post2.cout)
 
     def cost(self, plan, desc):
         sub, npix, es = self.replaces, plan.npix, plan.esize
@@ -1209,8 +1180,7 @@ class Chain(_Fused):
 @dataclass
 class Distill(_Fused):
     """A BMDB distillation step as ONE esr_distill_step_s16 op -- see Plan.distill_step (distill_step_kernel).  replaces: [c_d, c_b, c_r]."""
-    kind = "distill"
-    predicate, field, what = "esr_distill_step_supported", "chain", "distillation step"
+    kind, OP, what = "distill", L.OP_DISTILL_STEP, "distillation step"
 
     def check(self):
         sub = self.replaces
@@ -1224,19 +1194,10 @@ class Distill(_Fused):
         return [_blob(self.replaces[2].w, FOLD, self.replaces[1].w)]
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         cd, cb, cr = self.replaces
-        op.kind = L.OP_DISTILL_STEP
-        d = op.chain
-        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 2
-        d.cin, d.cmid, d.cout = cd.cin, cd.cout, cr.cout
-        d.act, d.slope, d.res_mode = L.ACT_RELU, 0.0, (L.RES_PRE_ACT if cb.res is not None else L.RES_NONE)
-        d.storage = d.compute = st
-        d.inp = _view(cd.src, base)
-        d.wpacked[0] = weights[cd.w + S16].data_ptr()
-        d.wpacked[1] = weights[cr.w + FOLD].data_ptr()
-        d.post_out, d.post_cout = _view(cd.dst, base), _stored_width(cd.dst, cd.cout)
-        d.post2_out, d.post2_cout = _view(cr.dst, base), _stored_width(cr.dst, cr.cout)
+        descs.distill_step(self.desc(op), plan.nhw, plan.st, x=_view(cd.src, base), w_d=weights[cd.w + S16].data_ptr(),
+                           w_fold=weights[cr.w + FOLD].data_ptr(), cin=cd.cin, cmid=cd.cout, cout=cr.cout, res=cb.res is not None,
+                           dd=_view(cd.dst, base), d_width=_stored_width(cd.dst, cd.cout), y=_view(cr.dst, base), y_width=_stored_width(cr.dst, cr.cout))
 
     def cost(self, plan, desc):             # the step's input read once, d and the result written once
         cd, cb, cr = self.replaces
@@ -1252,8 +1213,7 @@ class Distill(_Fused):
 class ResHead(_Fused):
     """The head of ESAN's residual block as ONE esr_resblock_head_s16 op -- see Plan.resblock_head (resblock_head_kernel).  replaces: [add,]
     conv1, conv2, ESA.conv1; the first block of the trunk has no add."""
-    kind = "reshead"
-    predicate, field, what = "esr_resblock_head_supported", "conv", "residual-block head"
+    kind, OP, what = "reshead", L.OP_RESBLOCK_HEAD, "residual-block head"
 
     def check(self):
         sub = self.replaces
@@ -1267,27 +1227,13 @@ class ResHead(_Fused):
             assert not _same_view(add.dst, add.res) and not _same_view(add.dst, add.src)
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         add = self.replaces[0] if len(self.replaces) == 4 else None
         c1, c2, ce = self.replaces[-3:]
-        op.kind = L.OP_RESBLOCK_HEAD
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        d.cin, d.cout, d.ksize = c1.cin, c2.cout, 3
-        d.in_layout = d.out_layout = L.NHWC
-        d.act, d.slope = L.ACT_RELU, 0.0
-        d.storage = d.compute = st
-        if add is not None:                                   # x = xin + g: the add's residual is the block input, its source the ESA result
-            d.res_mode = L.RES_PRE_ACT
-            d.inp, d.res, d.out0 = _view(add.res, base), _view(add.src, base), _view(add.dst, base)
-        else:
-            d.res_mode = L.RES_NONE
-            d.inp = _view(c1.src, base)
-        d.out1 = _view(c2.dst, base)
-        d.wpacked = ctypes.c_void_p(weights[c1.w + S16].data_ptr())
-        d.tail_wpacked = ctypes.c_void_p(weights[c2.w + S16].data_ptr())
-        d.post_wpacked = ctypes.c_void_p(weights[ce.w + S16].data_ptr())
-        d.post_out, d.post_cout = _view(ce.dst, base), _stored_width(ce.dst, ce.cout)
+        # x = xin + g: the add's residual is the block input, its source the ESA result
+        xin, g, xs = (add.res, add.src, add.dst) if add is not None else (c1.src, None, None)
+        descs.resblock_head(self.desc(op), plan.nhw, plan.st, x=_view(xin, base), g=_view(g, base), xs=_view(xs, base),
+                            w1=weights[c1.w + S16].data_ptr(), w2=weights[c2.w + S16].data_ptr(), wc=weights[ce.w + S16].data_ptr(),
+                            cin=c1.cin, cout=c2.cout, u=_view(c2.dst, base), c1=_view(ce.dst, base), c1_width=_stored_width(ce.dst, ce.cout))
 
     def cost(self, plan, desc):             # xin (and g) read once; x, u and c1 written once
         add = len(self.replaces) == 4
@@ -1307,8 +1253,7 @@ class ResHead(_Fused):
 class Cascade(_Fused):
     """FRFDB's narrowing refinement path as ONE esr_refine_cascade_s16 op -- see Plan.refine_cascade (refine_cascade_kernel).
     replaces: [c2_r, c3_d, c3_r, c4]."""
-    kind = "cascade"
-    predicate, field, what = "esr_refine_cascade_supported", "chain", "refinement cascade"
+    kind, OP, what = "cascade", L.OP_REFINE_CASCADE, "refinement cascade"
 
     def check(self):
         sub = self.replaces
@@ -1320,19 +1265,10 @@ class Cascade(_Fused):
         assert _same_view(c3d.src, c2r.dst) and _same_view(c3r.src, c3d.dst) and _same_view(c4.src, c3r.dst)
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         c2r, c3d, c3r, c4 = self.replaces
-        op.kind = L.OP_REFINE_CASCADE
-        d = op.chain
-        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 4
-        d.cin, d.cmid, d.cout = c2r.cin, c3d.cout, c4.cout
-        d.act, d.slope, d.res_mode = L.ACT_LRELU, c2r.slope, L.RES_PRE_ACT
-        d.storage = d.compute = st
-        d.inp = _view(c2r.src, base)
-        for l, so in enumerate(self.replaces):
-            d.wpacked[l] = weights[so.w + S16].data_ptr()
-        d.post_out, d.post_cout = _view(c3d.dst, base), _stored_width(c3d.dst, c3d.cout)
-        d.post2_out, d.post2_cout = _view(c4.dst, base), _stored_width(c4.dst, c4.cout)
+        descs.refine_cascade(self.desc(op), plan.nhw, plan.st, d2=_view(c2r.src, base), w=[weights[so.w + S16].data_ptr() for so in self.replaces],
+                             cin=c2r.cin, cmid=c3d.cout, cout=c4.cout, slope=c2r.slope, d3=_view(c3d.dst, base),
+                             d3_width=_stored_width(c3d.dst, c3d.cout), r4=_view(c4.dst, base), r4_width=_stored_width(c4.dst, c4.cout))
 
     def cost(self, plan, desc):             # d2 read once; d3 and r4 written once
         c2r, c3d, c3r, c4 = self.replaces
@@ -1347,8 +1283,7 @@ class Cascade(_Fused):
 @dataclass
 class CxBlock(_Fused):
     """RFDNeXt's ConvNeXt block as ONE esr_cx_block_s16 op -- see Plan.cx_block (cx_block_kernel).  replaces: [dw7, pw1, pw2]."""
-    kind = "cx"
-    predicate, field, what = "esr_cx_block_supported", "chain", "ConvNeXt block"
+    kind, OP, what = "cx", L.OP_CX_BLOCK, "ConvNeXt block"
 
     def check(self):
         sub = self.replaces
@@ -1366,19 +1301,10 @@ class CxBlock(_Fused):
         return [_blob(pw1.w, CX1, pw2.w), (pw2.w + CX2, CX2, (pw1.w, pw2.w))] + dw.blobs(plan) + pw2.blobs(plan)
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         dw, pw1, pw2 = self.replaces
-        op.kind = L.OP_CX_BLOCK
-        d = op.chain
-        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 3
-        d.cin, d.cmid, d.cout = dw.c, pw1.cout, pw2.cout
-        d.act, d.slope, d.res_mode = L.ACT_LRELU, pw1.slope, L.RES_POST_ACT
-        d.storage = d.compute = st
-        d.inp = _view(dw.src, base)
-        d.wpacked[0] = weights[dw.w].data_ptr()
-        d.wpacked[1] = weights[pw1.w + CX1].data_ptr()
-        d.wpacked[2] = weights[pw2.w + CX2].data_ptr()
-        d.post_out, d.post_cout = _view(pw2.dst, base), _stored_width(pw2.dst, pw2.cout)
+        descs.cx_block(self.desc(op), plan.nhw, plan.st, v=_view(dw.src, base), w0=weights[dw.w].data_ptr(), w1=weights[pw1.w + CX1].data_ptr(),
+                       w2=weights[pw2.w + CX2].data_ptr(), c=dw.c, m=pw1.cout, cout=pw2.cout, slope=pw1.slope, out=_view(pw2.dst, base),
+                       out_width=_stored_width(pw2.dst, pw2.cout))
 
     def cost(self, plan, desc):             # v read once, the result written once
         dw, pw1, pw2 = self.replaces
@@ -1393,8 +1319,7 @@ class CxBlock(_Fused):
 @dataclass
 class DwPwPair(_Fused):
     """Team 35's refinement path as ONE esr_dwpw_pair_s16 op -- see Plan.dwpw_pair (dwpw_pair_kernel).  replaces: [dw_a, pw_a, dw_b, pw_b]."""
-    kind = "dwpw"
-    predicate, field, what = "esr_dwpw_pair_supported", "chain", "depthwise-pointwise pair"
+    kind, OP, what = "dwpw", L.OP_DWPW_PAIR, "depthwise-pointwise pair"
 
     def check(self):
         sub = self.replaces
@@ -1411,20 +1336,10 @@ class DwPwPair(_Fused):
         return [_blob(self.replaces[i].w, DWPW) for i in (1, 3)]
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         dwa, pwa, dwb, pwb = self.replaces
-        op.kind = L.OP_DWPW_PAIR
-        d = op.chain
-        d.n, d.h, d.w, d.n_layers = plan.n, plan.h, plan.w, 4
-        d.cin = d.cmid = d.cout = dwa.c
-        d.act, d.slope, d.res_mode = L.ACT_LRELU, pwb.slope, L.RES_PRE_ACT
-        d.storage = d.compute = st
-        d.inp = _view(dwa.src, base)
-        d.wpacked[0] = weights[dwa.w].data_ptr()
-        d.wpacked[1] = weights[pwa.w + DWPW].data_ptr()
-        d.wpacked[2] = weights[dwb.w].data_ptr()
-        d.wpacked[3] = weights[pwb.w + DWPW].data_ptr()
-        d.post_out, d.post_cout = _view(pwb.dst, base), _stored_width(pwb.dst, pwb.cout)
+        w = [weights[name].data_ptr() for name in (dwa.w, pwa.w + DWPW, dwb.w, pwb.w + DWPW)]
+        descs.dwpw_pair(self.desc(op), plan.nhw, plan.st, x=_view(dwa.src, base), w=w, c=dwa.c, slope=pwb.slope, out=_view(pwb.dst, base),
+                        out_width=_stored_width(pwb.dst, pwb.cout))
 
     def cost(self, plan, desc):             # x read once, the result written once
         dwa, pwa, dwb, pwb = self.replaces
@@ -1446,16 +1361,12 @@ class Unshuffle(_Op):
     src: Buffer
     dst: Buffer
     f: int
-    kind = "unshuffle"
+    kind, OP = "unshuffle", L.OP_ESA_UNSHUFFLE
     reads = (("w", UNSHUFFLE),)
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_ESA_UNSHUFFLE
-        e = op.esa
-        e.n, e.h, e.w, e.f, e.storage = plan.n, self.src.h, self.src.w, self.f, L.STORE[plan.store]
-        e.h_lo, e.w_lo = self.dst.h, self.dst.w
-        e.x, e.y = _view(self.src, base), _view(self.dst, base)
-        e.w0 = ctypes.c_void_p(weights[self.w].data_ptr())
+        descs.esa_unshuffle(self.desc(op), (plan.n, self.src.h, self.src.w), plan.st, c1=_view(self.src, base), w=weights[self.w].data_ptr(), f=self.f,
+                            y=_view(self.dst, base), lo=(self.dst.h, self.dst.w))
 
     def cost(self, plan, desc):             # the conv1 map read (about 49 / 36 times: the windows overlap), the small map written
         f, npl = self.f, plan.n * self.dst.h * self.dst.w
@@ -1479,31 +1390,20 @@ class PaGate(_Op):
     c: int
     s: object = None           # the tensor added behind the gate (a Plan.pair() where hilo has L.HILO_RES), or None
     hilo: int = 0
-    kind = "pagate"
+    kind, OP = "pagate", L.OP_PA_GATE
     reads = (("w", PAG),)
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
-        op.kind = L.OP_PA_GATE
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        s, dst = self.s, self.dst
+        s, dst, stride = self.s, self.dst, 0
         if self.hilo:
             pairs = [v for bit, v in ((L.HILO_RES, s), (L.HILO_OUT, dst)) if self.hilo & bit]
             assert not self.hilo & L.HILO_IN and all(isinstance(v, Planar) and len(v.segs) == 2 for v in pairs), "hilo: Plan.pair() buffers"
             strides = {v.stride for v in pairs}
             assert len(strides) == 1, "hilo: pairs of one shape"
-            d.hilo_stride = strides.pop()
+            stride = strides.pop()
             s, dst = (v.seg(0) if self.hilo & bit else v for bit, v in ((L.HILO_RES, s), (L.HILO_OUT, dst)))
-        d.cin, d.ksize = self.c, 1
-        d.cout = _stored_width(dst, self.c) if st else (self.c + 3) // 4 * 4
-        d.in_layout = d.out_layout = L.NHWC
-        d.inp, d.out0 = _view(self.src, base), _view(dst, base)
-        if s is not None:
-            d.res, d.res_mode = _view(s, base), L.RES_POST_ACT
-        d.hilo = self.hilo
-        d.storage = d.compute = st
-        d.wpacked = ctypes.c_void_p(weights[self.w + PAG].data_ptr())
+        descs.pa_gate(self.desc(op), plan.nhw, plan.st, t=_view(self.src, base), w=weights[self.w + PAG].data_ptr(), c=self.c, y=_view(dst, base),
+                      y_width=_stored_width(dst, self.c) if plan.st else (self.c + 3) // 4 * 4, s=_view(s, base), hilo=self.hilo, hilo_stride=stride)
 
     def cost(self, plan, desc):             # t (and s) read once, y written once
         npix, es, c = plan.npix, plan.esize, self.c
@@ -1527,8 +1427,7 @@ class Prelu(_Op):
     w: str
     srcs: list                 # [(view, channels), ...] in the concat's order
     dst: object
-    kind = "prelu"
-    FIELDS = (("inp", "cin"), ("res", "split"), ("tail_cat", "tail_cat_c"), ("out1", "tail_cout"))
+    kind, OP = "prelu", L.OP_PRELU
     reads = (("w", PRELU),)
 
     @property
@@ -1536,18 +1435,9 @@ class Prelu(_Op):
         return sum(c for _, c in self.srcs)
 
     def encode(self, op, plan, base, weights):
-        assert 1 <= len(self.srcs) <= len(self.FIELDS)
-        op.kind = L.OP_PRELU
-        d = op.conv
-        d.n, d.h, d.w, d.ksize = plan.n, plan.h, plan.w, 1
-        d.in_layout = d.out_layout = L.NHWC
-        d.storage = d.compute = L.STORE[plan.store]
-        for (v, c), (view, count) in zip(self.srcs, self.FIELDS):
-            setattr(d, view, _view(v, base))
-            setattr(d, count, c)
-        d.cout = self.c
-        d.out0 = _view(self.dst, base)
-        d.wpacked = ctypes.c_void_p(weights[self.w + PRELU].data_ptr())
+        assert 1 <= len(self.srcs) <= len(descs.PRELU_SRCS)
+        d = self.desc(op)
+        descs.prelu(d, plan.nhw, plan.st, srcs=[(_view(v, base), c) for v, c in self.srcs], a=weights[self.w + PRELU].data_ptr(), y=_view(self.dst, base))
         if not L.lib().esr_prelu_supported(ctypes.byref(d)):
             raise L.EsrError(f"{self.w}: esr_prelu does not take this descriptor")
 
@@ -1569,8 +1459,7 @@ class ResdbStep(_Fused):
     maps), the expansion 1x1's `res` part, its distilled part, the PReLU of res, the 3x3 with the residual x]; whole: the name under which
     the network packs the expansion 1x1 as ONE image, its `res` rows, then its distilled rows."""
     whole: str = None
-    kind = "resdb"
-    predicate, field, what = "esr_resdb_step_supported", "conv", "ResDB step"
+    kind, OP, what = "resdb", L.OP_RESDB_STEP, "ResDB step"
 
     def check(self):
         sub = self.replaces
@@ -1585,21 +1474,11 @@ class ResdbStep(_Fused):
         return [_blob(self.replaces[0].w, RSTEP, self.replaces[3].w), _blob(self.whole, S16)]
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         pe, cr, cd, pc, c3 = self.replaces
-        op.kind = L.OP_RESDB_STEP
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        d.cin, d.cout, d.ksize = pe.srcs[0][1], c3.cout, 3
-        d.post_cout, d.tail_cat_c = cd.cout, sum(c for _, c in pe.srcs[1:])
-        d.in_layout = d.out_layout = L.NHWC
-        d.storage = d.compute = st
-        d.inp, d.out0, d.post_out = _view(pe.srcs[0][0], base), _view(c3.dst, base), _view(cd.dst, base)
-        for (v, _), dst in zip(pe.srcs[1:], ("res", "tail_cat")):
-            setattr(d, dst, _view(v, base))
-        d.wpacked = ctypes.c_void_p(weights[c3.w + S16].data_ptr())
-        d.post_wpacked = ctypes.c_void_p(weights[self.whole + S16].data_ptr())
-        d.tail_wpacked = ctypes.c_void_p(weights[pe.w + RSTEP].data_ptr())
+        (x, cin), extras = pe.srcs[0], pe.srcs[1:]
+        descs.resdb_step(self.desc(op), plan.nhw, plan.st, x=_view(x, base), extras=[_view(v, base) for v, _ in extras],
+                         a=weights[pe.w + RSTEP].data_ptr(), w_e=weights[self.whole + S16].data_ptr(), w_c=weights[c3.w + S16].data_ptr(), cin=cin,
+                         cout=c3.cout, extra_channels=sum(c for _, c in extras), dists=_view(cd.dst, base), dists_channels=cd.cout, y=_view(c3.dst, base))
 
     def cost(self, plan, desc):             # x and the earlier distilled maps read once, the step's distilled maps and x' written once
         pe, cr, cd, pc, c3 = self.replaces
@@ -1621,8 +1500,7 @@ class ResdbStep(_Fused):
 class ConvPrelu(_Fused):
     """A dense 64 -> 64 3x3 and the per-channel PReLU behind it as ONE esr_conv_prelu op -- see Plan.conv_prelu (conv_prelu_kernel).
     replaces: [conv, prelu]."""
-    kind = "convprelu"
-    predicate, field, what = "esr_conv_prelu_supported", "conv", "conv + PReLU"
+    kind, OP, what = "convprelu", L.OP_CONV_PRELU, "conv + PReLU"
 
     def check(self):
         sub = self.replaces
@@ -1635,15 +1513,8 @@ class ConvPrelu(_Fused):
 
     def encode(self, op, plan, base, weights):
         cv, pl = self.replaces
-        op.kind = L.OP_CONV_PRELU
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        d.cin, d.cout, d.ksize = cv.cin, cv.cout, 3
-        d.in_layout = d.out_layout = L.NHWC
-        d.storage = d.compute = L.STORE[plan.store]
-        d.inp, d.out0 = _view(cv.src, base), _view(pl.dst, base)
-        d.wpacked = ctypes.c_void_p(weights[cv.w + S16].data_ptr())
-        d.tail_wpacked = ctypes.c_void_p(weights[pl.w + PRELU].data_ptr())
+        descs.conv_prelu(self.desc(op), plan.nhw, plan.st, x=_view(cv.src, base), w=weights[cv.w + S16].data_ptr(), a=weights[pl.w + PRELU].data_ptr(),
+                         cin=cv.cin, cout=cv.cout, y=_view(pl.dst, base))
 
     def cost(self, plan, desc):             # the input read once, the activated result written once; the raw result never exists
         cv, pl = self.replaces
@@ -1661,8 +1532,7 @@ class MdsaGate(_Fused):
     cat(f1, f2, f3), its PReLU, the replicated one-channel gate (a 1x1 of x with res_mode L.RES_GATE on the PReLU's result)]; sa: the
     one-channel gate's own leaf, which the replicated 1x1 is made from."""
     sa: str = None
-    kind = "mdsagate"
-    predicate, field, what = "esr_mdsa_gate_supported", "conv", "MDSA gate"
+    kind, OP, what = "mdsagate", L.OP_MDSA_GATE, "MDSA gate"
 
     def check(self):
         sub = self.replaces
@@ -1680,20 +1550,9 @@ class MdsaGate(_Fused):
 
     def encode(self, op, plan, base, weights):
         cf, pl, gt = self.replaces
-        op.kind = L.OP_MDSA_GATE
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        d.cin, d.cout, d.ksize = cf.cin, cf.cout, 1
-        d.in_layout = d.out_layout = L.NHWC
-        d.storage = d.compute = L.STORE[plan.store]
-        if isinstance(cf.src, Planar):
-            d.inp = _view(cf.src.seg(0), base)
-            d.in_seg_stride, d.in_seg_chunks = cf.src.stride, (cf.src.pitch + 15) // 16
-        else:
-            d.inp = _view(cf.src, base)
-        d.res, d.res_mode = _view(gt.src, base), L.RES_GATE                                      # x: the gate's operand
-        d.out0 = _view(gt.dst, base)
-        d.wpacked = ctypes.c_void_p(weights[cf.w + MGATE].data_ptr())
+        f, seg = (cf.src.seg(0), (cf.src.stride, (cf.src.pitch + 15) // 16)) if isinstance(cf.src, Planar) else (cf.src, None)
+        descs.mdsa_gate(self.desc(op), plan.nhw, plan.st, f=_view(f, base), x=_view(gt.src, base), w=weights[cf.w + MGATE].data_ptr(), cin=cf.cin,
+                        cout=cf.cout, y=_view(gt.dst, base), seg=seg)
 
     def cost(self, plan, desc):             # f1, f2, f3 and x read once, y written once; the raw 1x1 result and f never exist
         cf, pl, gt = self.replaces
@@ -1707,8 +1566,7 @@ class MdsaGate(_Fused):
 @dataclass
 class PaTail(_Fused):
     """A 3x3 and the pixel attention behind it as ONE esr_pa_tail op -- see Plan.pa_tail (pa_tail_kernel).  replaces: [conv, pagate]."""
-    kind = "patail"
-    predicate, field, what = "esr_pa_tail_supported", "conv", "pixel-attention tail"
+    kind, OP, what = "patail", L.OP_PA_TAIL, "pixel-attention tail"
 
     def check(self):
         sub = self.replaces
@@ -1722,12 +1580,7 @@ class PaTail(_Fused):
     def encode(self, op, plan, base, weights):
         cv, gate = self.replaces
         gate.encode(op, plan, base, weights)                                        # t's view is replaced by the 3x3's input
-        op.kind = L.OP_PA_TAIL
-        d = op.conv
-        d.ksize = 3
-        d.inp = _view(cv.src, base)
-        d.wpacked = ctypes.c_void_p(weights[cv.w + S16].data_ptr())
-        d.tail_wpacked = ctypes.c_void_p(weights[gate.w + PAG].data_ptr())
+        descs.pa_tail(self.desc(op), x=_view(cv.src, base), w3=weights[cv.w + S16].data_ptr(), w=weights[gate.w + PAG].data_ptr())
 
     def cost(self, plan, desc):             # x (and s) read once, y written once; t never exists
         cv, gate = self.replaces
@@ -1746,8 +1599,7 @@ class AsymStep(_Fused):
     leaves of the step's four 3-tap convolutions, [c_l1, c_m1, c_l2, c_m2]."""
     p: list = None
     taps: list = None
-    kind = "asym"
-    predicate, field, what = "esr_asym_step_supported", "conv", "asymmetric-convolution step"
+    kind, OP, what = "asym", L.OP_ASYM_STEP, "asymmetric-convolution step"
 
     def check(self):
         sub = self.replaces
@@ -1761,21 +1613,10 @@ class AsymStep(_Fused):
         return [_blob(self.taps[0], ASYM, *self.taps[1:])]
 
     def encode(self, op, plan, base, weights):
-        st = L.STORE[plan.store]
         cd, ca, cb = self.replaces
-        op.kind = L.OP_ASYM_STEP
-        d = op.conv
-        d.n, d.h, d.w = plan.n, plan.h, plan.w
-        d.cin, d.cout, d.ksize = cd.cin, _stored_width(cb.dst, cb.cout), 3
-        d.act, d.slope, d.post_act = cd.act, cd.slope, cd.act
-        d.res_mode = L.RES_PRE_ACT if cb.res is not None else L.RES_NONE
-        d.in_layout = d.out_layout = L.NHWC
-        d.storage = d.compute = st
-        d.inp, d.out0, d.post_out, d.post_cout = _view(cd.src, base), _view(cb.dst, base), _view(cd.dst, base), cd.cout
-        for v, dst in zip(self.p or (), ("res", "tail_cat")):
-            setattr(d, dst, _view(v, base))
-        d.wpacked = ctypes.c_void_p(weights[self.taps[0] + ASYM].data_ptr())
-        d.post_wpacked = ctypes.c_void_p(weights[cd.w + S16].data_ptr())
+        descs.asym_step(self.desc(op), plan.nhw, plan.st, x=_view(cd.src, base), w_d=weights[cd.w + S16].data_ptr(),
+                        w_taps=weights[self.taps[0] + ASYM].data_ptr(), cin=cd.cin, c=cd.cout, act=cd.act, slope=cd.slope, res=cb.res is not None,
+                        dd=_view(cd.dst, base), y=_view(cb.dst, base), y_width=_stored_width(cb.dst, cb.cout), p=[_view(v, base) for v in self.p or ()])
 
     def cost(self, plan, desc):             # the step's input (and the earlier distilled maps) read once, d and the result written once
         cd, ca, cb = self.replaces
@@ -1806,14 +1647,13 @@ class Apply(_Op):
     f: int
     post: list = None
     skip_y: bool = False
-    kind = "apply"
+    kind, OP = "apply", L.OP_ESA_APPLY
 
     def blobs(self, plan):                                    # (the 1x1s riding in the launch are ONE blob, under the first one's name)
         return [_blob(self.wf), _blob(self.w4)] + ([_blob(self.post[0].w, APOST, *(t.w for t in self.post[1:]))] if self.post else [])
 
     def encode(self, op, plan, base, weights):
-        op.kind = L.OP_ESA_APPLY
-        e = op.esa
+        e = self.desc(op)
         e.n, e.h, e.w, e.c, e.f, e.storage = plan.n, plan.h, plan.w, self.c, self.f, L.STORE[plan.store]
         e.h_lo, e.w_lo = self.c3.h, self.c3.w
         e.x, e.y = _view(self.x, base), _view(self.dst, base)
@@ -1863,6 +1703,7 @@ class Plan:
         self.n, self.h, self.w = n, h, w
         self.npix = n * h * w
         self.store = store
+        self.nhw, self.st = (n, h, w), L.STORE[store]          # as the fills of descs.py take them
         self.esize = 4 if store == "f32" else 2
         self.total = 0         # bytes of the full-resolution arena
         self.total_lo = 0      # bytes of the low-resolution (always fp32) arena.  The two never overlap across plans: a 16-bit plan
@@ -1963,7 +1804,7 @@ class Plan:
         o.check()
         probe = L.Op()
         o.encode(probe, self, (0, 0), _AnyBlob())
-        getattr(probe, o.field).n = 1
+        getattr(probe, L.LAUNCHERS[o.OP][1]).n = 1
         if not o.supported(probe):
             return False
         self.ops[mark:] = [o]

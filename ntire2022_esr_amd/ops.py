@@ -7,13 +7,14 @@ import ctypes
 import torch
 
 from . import _lib as L
+from . import descs
 from .engine import (pack_asym_s16, pack_conv, pack_conv_s16, pack_cx_pw, pack_distill_s16, pack_dw, pack_dw7, pack_dwpw_pw, pack_mdsa_gate, pack_pa_gate,
                      pack_post_s16, pack_prelu, pack_unshuffle, pack_wino)
 
 
 def _view(t, coff=0):
-    """NHWC tensor [N,H,W,pitch] -> esr_view at channel offset coff."""
-    return L.View(ctypes.c_void_p(t.data_ptr()), t.shape[-1], coff)
+    """NHWC tensor [N,H,W,pitch] -> esr_view at channel offset coff; None, an absent operand, stays None"""
+    return None if t is None else L.View(ctypes.c_void_p(t.data_ptr()), t.shape[-1], coff)
 
 
 _STORE_OF = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
@@ -50,6 +51,14 @@ def _s16_store(x, what):
     return st
 
 
+def _any_store(x, what):
+    """the shared opening of the ops that take every storage: x on the GPU -> (its storage type by name, the channels of a 16-byte granule)"""
+    if not x.is_cuda:
+        raise L.EsrError(f"{what}: tensors must live on the GPU; there is no CPU fallback")
+    st = _STORE_OF[x.dtype]
+    return st, 4 if st == "f32" else 8
+
+
 _TRACE = None       # kernel_trace(): the list that collects device symbols
 
 
@@ -69,11 +78,19 @@ def kernel_trace():
         _TRACE = prev
 
 
-def _launch(fn, what, d, stream, kind=None, field=None):
-    """one C ABI call fn(&d, stream) -- also for a descriptor a caller filled in by hand (the tests do, for entry points without a wrapper
-    here); under kernel_trace() as a one-op list through the profiler, which records the device symbol"""
+def _launch(kind, d, stream, what=None, *named):
+    """one C ABI call of the launcher of op `kind` (L.LAUNCHERS) on the descriptor d -- also one a caller filled in by hand (the tests do, for
+    entry points without a wrapper here); under kernel_trace() as a one-op list through the profiler, which records the device symbol.
+    what: the name in the error's text (default: the entry point's).
+    The call form from before the table, _launch(fn, what, d, stream, kind, field), is still taken, so that callers written against it keep
+    working; the entry point and field it names must be the row's."""
     lib = L.lib()
-    if _TRACE is None or kind is None:
+    if isinstance(kind, str):
+        (named_fn, what, d, stream), (kind, named_field) = (kind, d, stream, what), named
+        assert (named_fn, named_field) == L.LAUNCHERS[kind][:2], (named_fn, named_field, kind)
+    fn, field, _ = L.LAUNCHERS[kind]
+    what = what or fn
+    if _TRACE is None:
         L.check(getattr(lib, fn)(ctypes.byref(d), ctypes.c_void_p(stream)), what)
         return
     op = L.Op()
@@ -90,6 +107,15 @@ def _launch(fn, what, d, stream, kind=None, field=None):
         # the profiler's events are recorded on THIS stream (0: the default stream)
         (torch.cuda.ExternalStream(stream) if stream else torch.cuda.default_stream()).synchronize()
         lib.esr_prof_destroy(prof)
+
+
+def _run(kind, d, x, refusal):
+    """the shared end of a wrapper: the predicate of the kind's row, where it has one, refuses with EsrError(refusal); else one launch on the
+    current stream of x's device"""
+    predicate = L.LAUNCHERS[kind][2]
+    if predicate is not None and not getattr(L.lib(), predicate)(ctypes.byref(d)):
+        raise L.EsrError(refusal)
+    _launch(kind, d, torch.cuda.current_stream(x.device).cuda_stream)
 
 
 def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.RES_NONE,
@@ -250,7 +276,7 @@ def conv2d(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode=L.
     stream = torch.cuda.current_stream(x.device).cuda_stream
     if (post_out is not None and post_weight is None) or (post2_out is not None and post2_weight is None):
         raise L.EsrError("conv2d: post_out / post2_out without the post weights")
-    _launch("esr_conv2d_f32", "esr_conv2d_f32", d, stream, L.OP_CONV, "conv")
+    _launch(L.OP_CONV, d, stream)
     if yp is None:
         return y
     return (y, yp) if yp2 is None else (y, yp, yp2)
@@ -268,51 +294,27 @@ def conv_chain(x, weights, biases, post_weight=None, post_bias=None, post2_weigh
     a tensor that fails the check used to reach the kernel unchecked and now raises EsrError.
     v_out / c1_out (RLFB form): caller-provided NHWC [N, H, W, pitch] tensors of x's dtype and device for v (pitch a multiple of 16 holding
     the first 1x1's channels) and c1 (a multiple of 8 holding the second's); default: freshly allocated zeros.  EsrError otherwise."""
-    if res_mode == L.RES_GATE:
-        return _hfab(x, weights, biases, act=act, slope=slope, cin=cin, out=out)
-    d, st, keep = _chain_desc(x, weights, biases, act, slope, res_mode, cin)
-    n, h, w, _ = x.shape
-    pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
-    p1 = pack_post_s16(pw, post_bias, st).to(x.device)
-    p2 = pack_post_s16(post2_weight, post2_bias, st).to(x.device)
-    v = _zeros_or(v_out, "conv_chain: v_out", x, (n, h, w), (pw.shape[0] + 15) // 16 * 16, 16)
-    c1 = _zeros_or(c1_out, "conv_chain: c1_out", x, (n, h, w), (post2_weight.shape[0] + 7) // 8 * 8, 8)
-    d.post_wpacked, d.post_out, d.post_cout, d.post_act = ctypes.c_void_p(p1.data_ptr()), _view(v), pw.shape[0], post_act
-    d.post2_wpacked, d.post2_out, d.post2_cout = ctypes.c_void_p(p2.data_ptr()), _view(c1), post2_weight.shape[0]
-    _launch_chain(d, x)
-    return v, c1
-
-
-def _chain_desc(x, weights, biases, act, slope, res_mode, cin):
-    """what both forms of conv_chain fill: shape, activation, input view and the packed 3x3s -> (descriptor, storage name, the blobs to keep)"""
     st = _s16_store(x, "conv_chain")
-    d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = x.shape[0], x.shape[1], x.shape[2], len(weights)
-    d.cin = weights[0].shape[1] if cin is None else cin
-    d.cmid, d.cout = weights[0].shape[0], weights[-1].shape[0]
-    d.act, d.slope, d.res_mode = act, slope, res_mode
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x)
-    keep = [pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device) for wt, b in zip(weights, biases)]
-    for i, blob in enumerate(keep):
-        d.wpacked[i] = blob.data_ptr()
-    return d, st, keep
-
-
-def _launch_chain(d, x):
-    if not L.lib().esr_conv_chain_supported(ctypes.byref(d)):
-        raise L.EsrError("conv_chain: no kernel for this shape (esr_conv_chain_supported)")
-    _launch("esr_conv_chain_s16", "esr_conv_chain_s16", d, torch.cuda.current_stream(x.device).cuda_stream, L.OP_CONV_CHAIN, "chain")
-
-
-def _hfab(x, weights, biases, *, act, slope, cin, out):
-    d, st, keep = _chain_desc(x, weights, biases, act, slope, L.RES_GATE, cin)
     n, h, w, pitch = x.shape
-    y = _zeros_or(out, "conv_chain: out", x, (n, h, w), pitch, 8)
-    d.post_out = _view(y)
-    d.post_cout = min((d.cout + 15) // 16 * 16, y.shape[-1])      # the pad channels of the last chunk too, as the per-layer store (zeros)
-    _launch_chain(d, x)
-    return y
+    keep = [pack_conv_s16(wt, b, st, cin_phys=(wt.shape[1] + 15) // 16 * 16).to(x.device) for wt, b in zip(weights, biases)]
+    common = dict(x=_view(x), w=[k.data_ptr() for k in keep], cin=weights[0].shape[1] if cin is None else cin, cmid=weights[0].shape[0],
+                  cout=weights[-1].shape[0], act=act, slope=slope)
+    d = L.ChainDesc()
+    if res_mode == L.RES_GATE:
+        y = _zeros_or(out, "conv_chain: out", x, (n, h, w), pitch, 8)
+        # (the pad channels of the last chunk too, as the per-layer store: zeros)
+        descs.hfab(d, (n, h, w), L.STORE[st], **common, y=_view(y), y_width=min((common["cout"] + 15) // 16 * 16, y.shape[-1]))
+        outs = y
+    else:
+        pw = post_weight if post_weight.dim() == 4 else post_weight[:, :, None, None]
+        keep += [pack_post_s16(pw, post_bias, st).to(x.device), pack_post_s16(post2_weight, post2_bias, st).to(x.device)]
+        v = _zeros_or(v_out, "conv_chain: v_out", x, (n, h, w), (pw.shape[0] + 15) // 16 * 16, 16)
+        c1 = _zeros_or(c1_out, "conv_chain: c1_out", x, (n, h, w), (post2_weight.shape[0] + 7) // 8 * 8, 8)
+        descs.chain(d, (n, h, w), L.STORE[st], **common, res_mode=res_mode, post_w=keep[-2].data_ptr(), v=_view(v), v_width=pw.shape[0],
+                    post_act=post_act, post2_w=keep[-1].data_ptr(), c1=_view(c1), c1_width=post2_weight.shape[0])
+        outs = v, c1
+    _run(L.OP_CONV_CHAIN, d, x, "conv_chain: no kernel for this shape (esr_conv_chain_supported)")
+    return outs
 
 
 def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_coff=0, d_out=None, d_coff=0, d_channels=None,
@@ -324,28 +326,18 @@ def distill_step(x, w_d, b_d, w_r, b_r, w_b, b_b, *, res=False, cin=None, in_cof
     out_coff; default: freshly allocated zeros of pitch round_up(channels, 8).  d_channels / out_channels: esr_chain_desc.post_cout /
     post2_cout, the stored widths (default: the logical ones; up to round_up(.., 16): the pad channels are written as zeros)."""
     st = _s16_store(x, "distill_step")
-    lib = L.lib()
     n, h, w, _ = x.shape
     w1 = w_d if w_d.dim() == 4 else w_d[:, :, None, None]
-    d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = n, h, w, 2
-    d.cin = w1.shape[1] if cin is None else cin
-    d.cmid, d.cout = w1.shape[0], w_r.shape[0]
-    d.act, d.res_mode = L.ACT_RELU, (L.RES_PRE_ACT if res else L.RES_NONE)
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x, in_coff)
     keep = [pack_conv_s16(w1, b_d, st, cin_phys=(w1.shape[1] + 15) // 16 * 16).to(x.device), pack_distill_s16(w_r, b_r, w_b, b_b, st).to(x.device)]
-    d.wpacked[0], d.wpacked[1] = keep[0].data_ptr(), keep[1].data_ptr()
-    d.post_cout = d.cmid if d_channels is None else d_channels
-    d.post2_cout = d.cout if out_channels is None else out_channels
-    dc8, oc8 = (d.post_cout + 7) // 8 * 8, (d.post2_cout + 7) // 8 * 8
-    dd = _zeros_or(d_out, "distill_step: d_out", x, (n, h, w), dc8, 8)
-    y = _zeros_or(out, "distill_step: out", x, (n, h, w), oc8, 8)
-    d.post_out, d.post2_out = _view(dd, d_coff), _view(y, out_coff)
-    if not lib.esr_distill_step_supported(ctypes.byref(d)):
-        raise L.EsrError("distill_step: no kernel for this shape (esr_distill_step_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_distill_step_s16", "esr_distill_step_s16", d, stream, L.OP_DISTILL_STEP, "chain")
+    dc = w1.shape[0] if d_channels is None else d_channels
+    oc = w_r.shape[0] if out_channels is None else out_channels
+    dd = _zeros_or(d_out, "distill_step: d_out", x, (n, h, w), (dc + 7) // 8 * 8, 8)
+    y = _zeros_or(out, "distill_step: out", x, (n, h, w), (oc + 7) // 8 * 8, 8)
+    d = L.ChainDesc()
+    descs.distill_step(d, (n, h, w), L.STORE[st], x=_view(x, in_coff), w_d=keep[0].data_ptr(), w_fold=keep[1].data_ptr(),
+                       cin=w1.shape[1] if cin is None else cin, cmid=w1.shape[0], cout=w_r.shape[0], res=res, dd=_view(dd, d_coff), d_width=dc,
+                       y=_view(y, out_coff), y_width=oc)
+    _run(L.OP_DISTILL_STEP, d, x, "distill_step: no kernel for this shape (esr_distill_step_supported)")
     return dd, y
 
 
@@ -360,33 +352,19 @@ def asym_step(x, w_d, b_d, w_l1, b_l1, w_l2, b_l2, w_m1, b_m1, w_m2, b_m2, *, re
     allocated zeros of pitch round_up(channels, 8).  out_channels: esr_conv_desc.cout, y's stored width (default c; up to
     round_up(c, 16): the pad channels are written as zeros)."""
     st = _s16_store(x, "asym_step")
-    lib = L.lib()
     n, h, w, _ = x.shape
     w1 = w_d if w_d.dim() == 4 else w_d[:, :, None, None]
     c = w1.shape[0]
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.ksize = n, h, w, 3
-    d.cin = w1.shape[1] if cin is None else cin
-    d.post_cout, d.cout = c, (c if out_channels is None else out_channels)
-    d.act, d.post_act, d.slope = act, act, slope
-    d.res_mode = L.RES_PRE_ACT if res else L.RES_NONE
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x, in_coff)
-    if p1 is not None:
-        d.res = _view(p1, p1_coff)
-    if p2 is not None:
-        d.tail_cat = _view(p2, p2_coff)
+    oc = c if out_channels is None else out_channels
     keep = [pack_asym_s16(w_l1, b_l1, w_m1, b_m1, w_l2, b_l2, w_m2, b_m2, st).to(x.device),
             pack_conv_s16(w1, b_d, st, cin_phys=(w1.shape[1] + 15) // 16 * 16).to(x.device)]
-    d.wpacked, d.post_wpacked = keep[0].data_ptr(), keep[1].data_ptr()
     dd = _zeros_or(d_out, "asym_step: d_out", x, (n, h, w), (c + 7) // 8 * 8, 8)
-    y = _zeros_or(out, "asym_step: out", x, (n, h, w), (d.cout + 7) // 8 * 8, 8)
-    d.post_out, d.out0 = _view(dd, d_coff), _view(y, out_coff)
-    if not lib.esr_asym_step_supported(ctypes.byref(d)):
-        raise L.EsrError("asym_step: no kernel for this shape (esr_asym_step_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_asym_step", "esr_asym_step", d, stream, L.OP_ASYM_STEP, "conv")
+    y = _zeros_or(out, "asym_step: out", x, (n, h, w), (oc + 7) // 8 * 8, 8)
+    d = L.ConvDesc()
+    descs.asym_step(d, (n, h, w), L.STORE[st], x=_view(x, in_coff), w_d=keep[1].data_ptr(), w_taps=keep[0].data_ptr(),
+                    cin=w1.shape[1] if cin is None else cin, c=c, act=act, slope=slope, res=res, dd=_view(dd, d_coff), y=_view(y, out_coff), y_width=oc,
+                    p=(_view(p1, p1_coff), _view(p2, p2_coff)))
+    _run(L.OP_ASYM_STEP, d, x, "asym_step: no kernel for this shape (esr_asym_step_supported)")
     return dd, y
 
 
@@ -398,30 +376,17 @@ def prelu(srcs, slopes, *, out=None, out_coff=0):
     default: freshly allocated zeros of pitch round_up(channels, granule).  Returns y."""
     srcs = [(s, 0, s.shape[-1]) if isinstance(s, torch.Tensor) else tuple(s) for s in srcs]
     x = srcs[0][0]
-    if not x.is_cuda:
-        raise L.EsrError("prelu: tensors must live on the GPU; there is no CPU fallback")
+    st, gran = _any_store(x, "prelu")
     if not 1 <= len(srcs) <= 4 or any(t.dtype != x.dtype or t.device != x.device or not t.is_contiguous() or tuple(t.shape[:3]) != tuple(x.shape[:3])
                                       for t, _, _ in srcs):
         raise L.EsrError("prelu: one to four contiguous NHWC tensors of one dtype, device and N x H x W")
-    st = _STORE_OF[x.dtype]
-    gran = 4 if st == "f32" else 8
     n, h, w, _ = x.shape
     ctot = sum(c for _, _, c in srcs)
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.ksize, d.cout = n, h, w, 1, ctot
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = d.compute = L.STORE[st]
-    for (t, coff, c), (view, count) in zip(srcs, (("inp", "cin"), ("res", "split"), ("tail_cat", "tail_cat_c"), ("out1", "tail_cout"))):
-        setattr(d, view, _view(t, coff))
-        setattr(d, count, c)
     keep = pack_prelu(slopes).to(x.device)
-    d.wpacked = keep.data_ptr()
     y = _zeros_or(out, "prelu: out", x, (n, h, w), (ctot + gran - 1) // gran * gran, gran)
-    d.out0 = _view(y, out_coff)
-    if not L.lib().esr_prelu_supported(ctypes.byref(d)):
-        raise L.EsrError("prelu: esr_prelu does not take this descriptor (esr_prelu_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_prelu", "esr_prelu", d, stream, L.OP_PRELU, "conv")
+    d = L.ConvDesc()
+    descs.prelu(d, (n, h, w), L.STORE[st], srcs=[(_view(t, coff), c) for t, coff, c in srcs], a=keep.data_ptr(), y=_view(y, out_coff))
+    _run(L.OP_PRELU, d, x, "prelu: esr_prelu does not take this descriptor (esr_prelu_supported)")
     return y
 
 
@@ -432,28 +397,21 @@ def resdb_step(x, a_e, w_e, b_e, a_c, w_c, b_c, *, extras=(), x_coff=0, d_out=No
     (tensor, first channel) pairs of 16 channels each.  Returns (dists, y).  d_out / out: caller-provided NHWC tensors that receive dists / y
     from channel d_coff / out_coff; default: freshly allocated zeros."""
     st = _s16_store(x, "resdb_step")
-    lib = L.lib()
+    refusal = "resdb_step: no kernel for this shape (esr_resdb_step_supported: n = 48, d = 16, 1..3 distilled outputs, 0..2 extra inputs)"
     n, h, w, _ = x.shape
     nd, nx = w_e.shape[0] - 48, len(extras)
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.ksize, d.cin, d.cout = n, h, w, 3, 48, 48
-    d.post_cout, d.tail_cat_c = nd, 16 * nx
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x, x_coff)
-    for (t, coff), name in zip(extras, ("res", "tail_cat")):
-        setattr(d, name, _view(t, coff))
     w1 = w_e if w_e.dim() == 4 else w_e[:, :, None, None]
+    if nd < 1 or w1.shape[1] != 48 + 16 * nx or a_e.numel() != 48 + 16 * nx or a_c.numel() != 48:
+        raise L.EsrError(refusal)
     keep = [pack_conv_s16(w_c, b_c, st).to(x.device), pack_conv_s16(w1, b_e, st).to(x.device),
             pack_prelu(torch.cat([a_e.float().reshape(-1), a_c.float().reshape(-1)])).to(x.device)]
-    d.wpacked, d.post_wpacked, d.tail_wpacked = keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr()
-    if not lib.esr_resdb_step_supported(ctypes.byref(d)) or w1.shape[1] != 48 + 16 * nx or a_e.numel() != 48 + 16 * nx or a_c.numel() != 48:
-        raise L.EsrError("resdb_step: no kernel for this shape (esr_resdb_step_supported: n = 48, d = 16, 1..3 distilled outputs, 0..2 extra inputs)")
     dd = _zeros_or(d_out, "resdb_step: d_out", x, (n, h, w), nd, 8)
     y = _zeros_or(out, "resdb_step: out", x, (n, h, w), 48, 8)
-    d.post_out, d.out0 = _view(dd, d_coff), _view(y, out_coff)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_resdb_step", "esr_resdb_step", d, stream, L.OP_RESDB_STEP, "conv")
+    d = L.ConvDesc()
+    descs.resdb_step(d, (n, h, w), L.STORE[st], x=_view(x, x_coff), extras=[_view(t, coff) for t, coff in extras], a=keep[2].data_ptr(),
+                     w_e=keep[1].data_ptr(), w_c=keep[0].data_ptr(), cin=48, cout=48, extra_channels=16 * nx, dists=_view(dd, d_coff), dists_channels=nd,
+                     y=_view(y, out_coff))
+    _run(L.OP_RESDB_STEP, d, x, refusal)
     return dd, y
 
 
@@ -464,20 +422,15 @@ def conv_prelu(x, w, b, a, *, x_coff=0, out=None, out_coff=0):
     and size.  out: a caller-provided NHWC tensor that receives y from channel out_coff and shares no byte with x's channels; default:
     freshly allocated zeros.  Returns y."""
     st = _s16_store(x, "conv_prelu")
+    refusal = "conv_prelu: no kernel for this shape (esr_conv_prelu_supported: 64 -> 64, 3x3, 16-bit storage)"
     n, h, wd, _ = x.shape
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.ksize, d.cin, d.cout = n, h, wd, 3, w.shape[1], w.shape[0]
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x, x_coff)
-    if not L.lib().esr_conv_prelu_supported(ctypes.byref(d)) or tuple(w.shape) != (64, 64, 3, 3) or a.numel() != 64:
-        raise L.EsrError("conv_prelu: no kernel for this shape (esr_conv_prelu_supported: 64 -> 64, 3x3, 16-bit storage)")
+    if tuple(w.shape) != (64, 64, 3, 3) or a.numel() != 64:
+        raise L.EsrError(refusal)
     keep = [pack_conv_s16(w, b, st).to(x.device), pack_prelu(a).to(x.device)]
-    d.wpacked, d.tail_wpacked = keep[0].data_ptr(), keep[1].data_ptr()
     y = _zeros_or(out, "conv_prelu: out", x, (n, h, wd), 64, 8)
-    d.out0 = _view(y, out_coff)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_conv_prelu", "esr_conv_prelu", d, stream, L.OP_CONV_PRELU, "conv")
+    d = L.ConvDesc()
+    descs.conv_prelu(d, (n, h, wd), L.STORE[st], x=_view(x, x_coff), w=keep[0].data_ptr(), a=keep[1].data_ptr(), cin=64, cout=64, y=_view(y, out_coff))
+    _run(L.OP_CONV_PRELU, d, x, refusal)
     return y
 
 
@@ -493,22 +446,12 @@ def mdsa_gate(f, x, w_f, b_f, a_f, w_s, b_s, *, f_coff=0, x_coff=0, out=None, ou
     planar = f.dim() == 5
     if not f.is_cuda or f.dtype != x.dtype or not f.is_contiguous() or not x.is_contiguous() or tuple(f.shape[-4:-1]) != (n, h, w) or (planar and f.shape[0] != 3):
         raise L.EsrError("mdsa_gate: f [N, H, W, P] or [3, N, H, W, P] and x [N, H, W, Q], contiguous, one dtype and device")
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.ksize, d.cin, d.cout = n, h, w, 1, 192, 64
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = d.compute = L.STORE[st]
-    d.res_mode = L.RES_GATE
-    d.inp, d.res = _view(f, f_coff), _view(x, x_coff)
-    if planar:
-        d.in_seg_stride, d.in_seg_chunks = f.stride(0) * f.element_size(), 4
     keep = pack_mdsa_gate(w_f, b_f, a_f, w_s, b_s, st).to(x.device)
-    d.wpacked = keep.data_ptr()
-    if not L.lib().esr_mdsa_gate_supported(ctypes.byref(d)):
-        raise L.EsrError("mdsa_gate: esr_mdsa_gate does not take this descriptor (esr_mdsa_gate_supported)")
     y = _zeros_or(out, "mdsa_gate: out", x, (n, h, w), 64, 8)
-    d.out0 = _view(y, out_coff)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_mdsa_gate", "esr_mdsa_gate", d, stream, L.OP_MDSA_GATE, "conv")
+    d = L.ConvDesc()
+    descs.mdsa_gate(d, (n, h, w), L.STORE[st], f=_view(f, f_coff), x=_view(x, x_coff), w=keep.data_ptr(), cin=192, cout=64, y=_view(y, out_coff),
+                    seg=(f.stride(0) * f.element_size(), 4) if planar else None)
+    _run(L.OP_MDSA_GATE, d, x, "mdsa_gate: esr_mdsa_gate does not take this descriptor (esr_mdsa_gate_supported)")
     return y
 
 
@@ -521,32 +464,17 @@ def resblock_head(x, w1, b1, w2, b2, wc, bc, *, g=None, in_coff=0, g_coff=0, x_o
     x_coff / u_coff / c1_coff; default: freshly allocated zeros (c1: pitch 16, the ESA map).  c1_channels: esr_conv_desc.post_cout, the
     stored width (default: the logical one; round_up(.., 8) channels are written, the pad ones as zeros)."""
     st = _s16_store(x, "resblock_head")
-    lib = L.lib()
     n, h, w, _ = x.shape
     wc4 = wc if wc.dim() == 4 else wc[:, :, None, None]
-    c, f = w1.shape[1], wc4.shape[0]
-    d = L.ConvDesc()
-    d.n, d.h, d.w = n, h, w
-    d.cin, d.cout, d.ksize = c, w2.shape[0], 3
-    d.in_layout = d.out_layout = L.NHWC
-    d.act, d.res_mode = L.ACT_RELU, (L.RES_NONE if g is None else L.RES_PRE_ACT)
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x, in_coff)
+    c, f = w1.shape[1], (wc4.shape[0] if c1_channels is None else c1_channels)
     keep = [pack_conv_s16(w1, b1, st).to(x.device), pack_conv_s16(w2, b2, st).to(x.device), pack_conv_s16(wc4, bc, st).to(x.device)]
-    d.wpacked, d.tail_wpacked, d.post_wpacked = (ctypes.c_void_p(k.data_ptr()) for k in keep)
-    xs = None
-    if g is not None:
-        d.res = _view(g, g_coff)
-        xs = _zeros_or(x_out, "resblock_head: x_out", x, (n, h, w), c, 8)
-        d.out0 = _view(xs, x_coff)
+    xs = None if g is None else _zeros_or(x_out, "resblock_head: x_out", x, (n, h, w), c, 8)
     u = _zeros_or(u_out, "resblock_head: u_out", x, (n, h, w), c, 8)
-    d.post_cout = f if c1_channels is None else c1_channels
-    c1 = _zeros_or(c1_out, "resblock_head: c1_out", x, (n, h, w), (d.post_cout + 7) // 8 * 8, 8, pitch=L.ESA_FP)
-    d.out1, d.post_out = _view(u, u_coff), _view(c1, c1_coff)
-    if not lib.esr_resblock_head_supported(ctypes.byref(d)):
-        raise L.EsrError("resblock_head: no kernel for this shape (esr_resblock_head_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_resblock_head_s16", "esr_resblock_head_s16", d, stream, L.OP_RESBLOCK_HEAD, "conv")
+    c1 = _zeros_or(c1_out, "resblock_head: c1_out", x, (n, h, w), (f + 7) // 8 * 8, 8, pitch=L.ESA_FP)
+    d = L.ConvDesc()
+    descs.resblock_head(d, (n, h, w), L.STORE[st], x=_view(x, in_coff), g=_view(g, g_coff), xs=_view(xs, x_coff), w1=keep[0].data_ptr(),
+                        w2=keep[1].data_ptr(), wc=keep[2].data_ptr(), cin=c, cout=w2.shape[0], u=_view(u, u_coff), c1=_view(c1, c1_coff), c1_width=f)
+    _run(L.OP_RESBLOCK_HEAD, d, x, "resblock_head: no kernel for this shape (esr_resblock_head_supported)")
     return xs, u, c1
 
 
@@ -562,26 +490,16 @@ def refine_cascade(d2, w2r, b2r, w3d, b3d, w3r, b3r, w4, b4, *, slope=0.05, in_c
     st = _s16_store(d2, "refine_cascade")
     if store is not None and store != st:
         raise L.EsrError(f"refine_cascade: store {store!r}, d2 is stored as {st}")
-    lib = L.lib()
     n, h, w, _ = d2.shape
     w1 = w3d if w3d.dim() == 4 else w3d[:, :, None, None]
-    d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = n, h, w, 4
-    d.cin, d.cmid, d.cout = w2r.shape[1], w1.shape[0], w4.shape[0]
-    d.act, d.slope, d.res_mode = L.ACT_LRELU, slope, L.RES_PRE_ACT
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(d2, in_coff)
+    cmid, cout = w1.shape[0], w4.shape[0]
     keep = [pack_conv_s16(wt, b, st).to(d2.device) for wt, b in ((w2r, b2r), (w1, b3d), (w3r, b3r), (w4, b4))]
-    for i, k in enumerate(keep):
-        d.wpacked[i] = k.data_ptr()
-    d.post_cout, d.post2_cout = d.cmid, d.cout
-    d3 = _zeros_or(d3_out, "refine_cascade: d3_out", d2, (n, h, w), (d.post_cout + 7) // 8 * 8, 8)
-    r4 = _zeros_or(r4_out, "refine_cascade: r4_out", d2, (n, h, w), (d.post2_cout + 7) // 8 * 8, 8)
-    d.post_out, d.post2_out = _view(d3, d3_coff), _view(r4, r4_coff)
-    if not lib.esr_refine_cascade_supported(ctypes.byref(d)):
-        raise L.EsrError("refine_cascade: no kernel for this shape (esr_refine_cascade_supported)")
-    stream = torch.cuda.current_stream(d2.device).cuda_stream
-    _launch("esr_refine_cascade_s16", "esr_refine_cascade_s16", d, stream, L.OP_REFINE_CASCADE, "chain")
+    d3 = _zeros_or(d3_out, "refine_cascade: d3_out", d2, (n, h, w), (cmid + 7) // 8 * 8, 8)
+    r4 = _zeros_or(r4_out, "refine_cascade: r4_out", d2, (n, h, w), (cout + 7) // 8 * 8, 8)
+    d = L.ChainDesc()
+    descs.refine_cascade(d, (n, h, w), L.STORE[st], d2=_view(d2, in_coff), w=[k.data_ptr() for k in keep], cin=w2r.shape[1], cmid=cmid, cout=cout,
+                         slope=slope, d3=_view(d3, d3_coff), d3_width=cmid, r4=_view(r4, r4_coff), r4_width=cout)
+    _run(L.OP_REFINE_CASCADE, d, d2, "refine_cascade: no kernel for this shape (esr_refine_cascade_supported)")
     return d3, r4
 
 
@@ -590,26 +508,14 @@ def dwconv7x7(x, weight, bias, *, in_coff=0, out=None, out_coff=0, packed=None):
     from in_coff) in fp32, bf16 or fp16 storage: fp32 sums in (ky, kx) ascending order, the bias last, one rounding.  weight [C, 1, 7, 7].
     out: a caller-provided NHWC tensor of x's dtype and device (another tensor than x) that receives the result from channel out_coff;
     default: freshly allocated zeros of pitch round_up(C, granule).  The pad channels up to the granule (4 fp32 / 8 16-bit) are stored as zeros."""
-    if not x.is_cuda:
-        raise L.EsrError("dwconv7x7: tensors must live on the GPU; there is no CPU fallback")
-    lib = L.lib()
-    st = _STORE_OF[x.dtype]
-    gran = 4 if st == "f32" else 8
+    st, gran = _any_store(x, "dwconv7x7")
     n, h, w, _ = x.shape
     c = weight.shape[0]
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, h, w, c, c, 7
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = L.STORE[st]
-    d.inp = _view(x, in_coff)
     keep = pack_dw7(weight, bias).to(x.device) if packed is None else packed
-    d.wpacked = keep.data_ptr()
     y = _zeros_or(out, "dwconv7x7: out", x, (n, h, w), (c + gran - 1) // gran * gran, gran)
-    d.out0 = _view(y, out_coff)
-    if not lib.esr_dwconv7x7_supported(ctypes.byref(d)):
-        raise L.EsrError("dwconv7x7: no kernel for this shape (esr_dwconv7x7_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_dwconv7x7", "esr_dwconv7x7", d, stream, L.OP_DWCONV7, "conv")
+    d = L.ConvDesc()
+    descs.dwconv7x7(d, (n, h, w), L.STORE[st], x=_view(x, in_coff), w=keep.data_ptr(), c=c, y=_view(y, out_coff))
+    _run(L.OP_DWCONV7, d, x, "dwconv7x7: no kernel for this shape (esr_dwconv7x7_supported)")
     return y
 
 
@@ -623,25 +529,15 @@ def cx_block(v, w0, b0, w1, b1, w2, b2, *, slope=0.05, in_coff=0, out=None, out_
     st = _s16_store(v, "cx_block")
     if store is not None and store != st:
         raise L.EsrError(f"cx_block: store {store!r}, v is stored as {st}")
-    lib = L.lib()
     n, h, w, _ = v.shape
-    c, m = w0.shape[0], w1.shape[0]
-    d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = n, h, w, 3
-    d.cin, d.cmid, d.cout = c, m, w2.shape[0]
-    d.act, d.slope, d.res_mode = L.ACT_LRELU, slope, L.RES_POST_ACT
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(v, in_coff)
+    cout = w2.shape[0]
     keep = [pack_dw7(w0, b0).to(v.device)] + [p.to(v.device) for p in pack_cx_pw(w1, b1, w2, b2, st)]
-    for i, k in enumerate(keep):
-        d.wpacked[i] = k.data_ptr()
-    d.post_cout = (d.cout + 7) // 8 * 8 if out_channels is None else out_channels
-    y = _zeros_or(out, "cx_block: out", v, (n, h, w), d.post_cout, 8)
-    d.post_out = _view(y, out_coff)
-    if not lib.esr_cx_block_supported(ctypes.byref(d)):
-        raise L.EsrError("cx_block: no kernel for this shape (esr_cx_block_supported)")
-    stream = torch.cuda.current_stream(v.device).cuda_stream
-    _launch("esr_cx_block_s16", "esr_cx_block_s16", d, stream, L.OP_CX_BLOCK, "chain")
+    width = (cout + 7) // 8 * 8 if out_channels is None else out_channels
+    y = _zeros_or(out, "cx_block: out", v, (n, h, w), width, 8)
+    d = L.ChainDesc()
+    descs.cx_block(d, (n, h, w), L.STORE[st], v=_view(v, in_coff), w0=keep[0].data_ptr(), w1=keep[1].data_ptr(), w2=keep[2].data_ptr(), c=w0.shape[0],
+                   m=w1.shape[0], cout=cout, slope=slope, out=_view(y, out_coff), out_width=width)
+    _run(L.OP_CX_BLOCK, d, v, "cx_block: no kernel for this shape (esr_cx_block_supported)")
     return y
 
 
@@ -650,25 +546,15 @@ def dwconv3x3(x, weight, bias, *, act=L.ACT_NONE, slope=0.05, res=None, res_mode
     from in_coff) in fp32, bf16 or fp16 storage, + res before / behind the activation (res_mode).  weight [C, 1, 3, 3].
     out: a caller-provided NHWC tensor of x's dtype and device (another tensor than x) that receives round_up(C, 4) channels from out_coff;
     default: freshly allocated zeros of pitch round_up(C, granule)."""
-    if not x.is_cuda:
-        raise L.EsrError("dwconv3x3: tensors must live on the GPU; there is no CPU fallback")
-    st = _STORE_OF[x.dtype]
-    gran = 4 if st == "f32" else 8
+    st, gran = _any_store(x, "dwconv3x3")
     n, h, w, _ = x.shape
     c = weight.shape[0]
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.cin, d.cout, d.ksize = n, h, w, c, c, 3
-    d.in_layout = d.out_layout = L.NHWC
-    d.act, d.slope, d.res_mode = act, slope, res_mode
-    d.storage = L.STORE[st]
-    d.inp = _view(x, in_coff)
-    if res is not None:
-        d.res = _view(res, res_coff)
     keep = pack_dw(weight, bias).to(x.device)
-    d.wpacked = keep.data_ptr()
     y = _zeros_or(out, "dwconv3x3: out", x, (n, h, w), (c + gran - 1) // gran * gran, gran)
-    d.out0 = _view(y, out_coff)
-    _launch("esr_dwconv3x3_f32", "esr_dwconv3x3_f32", d, torch.cuda.current_stream(x.device).cuda_stream, L.OP_DWCONV, "conv")
+    d = L.ConvDesc()
+    descs.dwconv3x3(d, (n, h, w), L.STORE[st], x=_view(x, in_coff), w=keep.data_ptr(), c=c, act=act, slope=slope, y=_view(y, out_coff),
+                    res=_view(res, res_coff), res_mode=res_mode)
+    _run(L.OP_DWCONV, d, x, None)
     return y
 
 
@@ -683,66 +569,46 @@ def dwpw_pair(x, wda, bda, wa, ba, wdb, bdb, wb, bb, *, slope=0.05, in_coff=0, o
     st = _s16_store(x, "dwpw_pair")
     if store is not None and store != st:
         raise L.EsrError(f"dwpw_pair: store {store!r}, x is stored as {st}")
-    lib = L.lib()
+    refusal = "dwpw_pair: no kernel for this shape (esr_dwpw_pair_supported)"
     n, h, w, _ = x.shape
     c = wda.shape[0]
-    d = L.ChainDesc()
-    d.n, d.h, d.w, d.n_layers = n, h, w, 4
-    d.cin = d.cmid = d.cout = c
-    d.act, d.slope, d.res_mode = L.ACT_LRELU, slope, L.RES_PRE_ACT
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(x, in_coff)
-    if not lib.esr_packed_cx_pw1_bytes(c, c):
-        raise L.EsrError("dwpw_pair: no kernel for this shape (esr_dwpw_pair_supported)")
+    if not L.lib().esr_packed_cx_pw1_bytes(c, c):
+        raise L.EsrError(refusal)
     keep = [pack_dw(wda, bda).to(x.device), pack_dwpw_pw(wa, ba, st).to(x.device), pack_dw(wdb, bdb).to(x.device), pack_dwpw_pw(wb, bb, st).to(x.device)]
-    for i, k in enumerate(keep):
-        d.wpacked[i] = k.data_ptr()
-    d.post_cout = (c + 7) // 8 * 8 if out_channels is None else out_channels
-    y = _zeros_or(out, "dwpw_pair: out", x, (n, h, w), d.post_cout, 8)
-    d.post_out = _view(y, out_coff)
-    if not lib.esr_dwpw_pair_supported(ctypes.byref(d)):
-        raise L.EsrError("dwpw_pair: no kernel for this shape (esr_dwpw_pair_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_dwpw_pair_s16", "esr_dwpw_pair_s16", d, stream, L.OP_DWPW_PAIR, "chain")
+    width = (c + 7) // 8 * 8 if out_channels is None else out_channels
+    y = _zeros_or(out, "dwpw_pair: out", x, (n, h, w), width, 8)
+    d = L.ChainDesc()
+    descs.dwpw_pair(d, (n, h, w), L.STORE[st], x=_view(x, in_coff), w=[k.data_ptr() for k in keep], c=c, slope=slope, out=_view(y, out_coff), out_width=width)
+    _run(L.OP_DWPW_PAIR, d, x, refusal)
     return y
 
 
 def _pa(what, t, weight, bias, s, pair_out, in_coff, s_coff, out, out_coff, out_channels):
     """the descriptor esr_pa_gate and esr_pa_tail share -> (desc, y, the blob to keep alive)"""
-    if not t.is_cuda:
-        raise L.EsrError(f"{what}: tensors must live on the GPU; there is no CPU fallback")
-    lib = L.lib()
-    st = _STORE_OF[t.dtype]
-    gran = 4 if st == "f32" else 8
+    st, gran = _any_store(t, what)
     n, h, w, _ = t.shape
     c = weight.shape[0]
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.cin, d.ksize = n, h, w, c, 1
-    d.cout = (c + gran - 1) // gran * gran if out_channels is None else out_channels
-    d.in_layout = d.out_layout = L.NHWC
-    d.storage = d.compute = L.STORE[st]
-    d.inp = _view(t, in_coff)
-    strides = set()
+    width = (c + gran - 1) // gran * gran if out_channels is None else out_channels
+    hilo, strides = 0, set()
     if s is not None:
         pair = s.dim() == 5
         if s.device != t.device or s.dtype != t.dtype or not s.is_contiguous() or tuple(s.shape[:-1]) != ((2,) if pair else ()) + (n, h, w):
             raise L.EsrError(f"{what}: s must be a contiguous [{'2, ' if pair else ''}{n}, {h}, {w}, pitch] tensor of t's dtype on t's device")
-        d.res, d.res_mode = _view(s, s_coff), L.RES_POST_ACT
         if pair:
-            d.hilo |= L.HILO_RES
+            hilo |= L.HILO_RES
             strides.add(s[1].data_ptr() - s[0].data_ptr())
-    if not lib.esr_packed_pa_gate_bytes(c, d.storage) or tuple(weight.shape[:2]) != (c, c):
+    if not L.lib().esr_packed_pa_gate_bytes(c, L.STORE[st]) or tuple(weight.shape[:2]) != (c, c):
         raise L.EsrError(f"{what}: no kernel for this shape (a square 1x1 of 33 .. 64 channels)")
     keep = pack_pa_gate(weight, bias, st).to(t.device)
-    y = _zeros_or(out, f"{what}: out", t, ((2,) if pair_out else ()) + (n, h, w), d.cout, gran)
-    d.out0 = _view(y, out_coff)
+    y = _zeros_or(out, f"{what}: out", t, ((2,) if pair_out else ()) + (n, h, w), width, gran)
     if pair_out:
-        d.hilo |= L.HILO_OUT
+        hilo |= L.HILO_OUT
         strides.add(y[1].data_ptr() - y[0].data_ptr())
     if len(strides) > 1:
         raise L.EsrError(f"{what}: a pair s and a pair result must have one pitch")
-    if strides:
-        d.hilo_stride = strides.pop()
+    d = L.ConvDesc()
+    descs.pa_gate(d, (n, h, w), L.STORE[st], t=_view(t, in_coff), w=keep.data_ptr(), c=c, y=_view(y, out_coff), y_width=width, s=_view(s, s_coff),
+                  hilo=hilo, hilo_stride=strides.pop() if strides else 0)
     return d, y, keep
 
 
@@ -757,11 +623,7 @@ def pa_gate(t, weight, bias, *, s=None, pair_out=False, in_coff=0, s_coff=0, out
     allocated zeros of pitch round_up(C, granule).  out_channels: the channels stored (default round_up(C, granule), granule 4 fp32 / 8
     16-bit; those >= C are zeros)."""
     d, y, keep = _pa("pa_gate", t, weight, bias, s, pair_out, in_coff, s_coff, out, out_coff, out_channels)
-    d.wpacked = keep.data_ptr()
-    if not L.lib().esr_pa_gate_supported(ctypes.byref(d)):
-        raise L.EsrError("pa_gate: no kernel for this shape (esr_pa_gate_supported)")
-    stream = torch.cuda.current_stream(t.device).cuda_stream
-    _launch("esr_pa_gate", "esr_pa_gate", d, stream, L.OP_PA_GATE, "conv")
+    _run(L.OP_PA_GATE, d, t, "pa_gate: no kernel for this shape (esr_pa_gate_supported)")
     return y
 
 
@@ -776,12 +638,8 @@ def pa_tail(x, w3, b3, weight, bias, *, s=None, pair_out=False, in_coff=0, s_cof
     if tuple(w3.shape) != (c, c, 3, 3):
         raise L.EsrError(f"pa_tail: w3 must be [{c}, {c}, 3, 3]")
     keep3 = pack_conv_s16(w3, b3, _STORE_OF[x.dtype], cin_phys=(c + 15) // 16 * 16).to(x.device)
-    d.ksize = 3
-    d.wpacked, d.tail_wpacked = keep3.data_ptr(), keep.data_ptr()
-    if not L.lib().esr_pa_tail_supported(ctypes.byref(d)):
-        raise L.EsrError("pa_tail: no kernel for this shape (esr_pa_tail_supported)")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_pa_tail", "esr_pa_tail", d, stream, L.OP_PA_TAIL, "conv")
+    descs.pa_tail(d, x=_view(x, in_coff), w3=keep3.data_ptr(), w=keep.data_ptr())
+    _run(L.OP_PA_TAIL, d, x, "pa_tail: no kernel for this shape (esr_pa_tail_supported)")
     return y
 
 
@@ -790,22 +648,17 @@ def esa_unshuffle(c1, weight, bias, *, out=None):
     c1: the conv1 map [N, H, W, 16] in fp32, bf16 or fp16 storage (f channels, the rest ignored), H, W >= 14; weight [f, 4 f, 1, 1] and bias
     of con_ = nn.Conv2d(4 f, f, 1, padding 1).  Returns the fp32 map [N, h3 + 2, w3 + 2, 16], h3 = (H // 2 - 7) // 3 + 1: the ring is
     relu(bias), the pad channels f .. 15 are zeros.  out: a caller-provided contiguous fp32 tensor of that shape on c1's device."""
-    if not c1.is_cuda:
-        raise L.EsrError("esa_unshuffle: tensors must live on the GPU; there is no CPU fallback")
+    st, _ = _any_store(c1, "esa_unshuffle")
     n, h, w, _ = c1.shape
-    f = weight.shape[0]
     if h < 14 or w < 14:
         raise L.EsrError("esa_unshuffle: H, W >= 14 (one 7x7 pooling window of the half-resolution map)")
-    d = L.EsaDesc()
-    d.n, d.h, d.w, d.f, d.storage = n, h, w, f, L.STORE[_STORE_OF[c1.dtype]]
-    d.h_lo, d.w_lo = (h // 2 - 7) // 3 + 3, (w // 2 - 7) // 3 + 3
-    d.x = _view(c1)
+    lo = (h // 2 - 7) // 3 + 3, (w // 2 - 7) // 3 + 3
     keep = pack_unshuffle(weight, bias).to(c1.device)
-    d.w0 = keep.data_ptr()
     like = torch.empty(0, dtype=torch.float32, device=c1.device)
-    y = _zeros_or(out, "esa_unshuffle: out", like, (n, d.h_lo, d.w_lo), L.ESA_FP, 4)
-    d.y = _view(y)
-    _launch("esr_esa_unshuffle_f32", "esr_esa_unshuffle_f32", d, torch.cuda.current_stream(c1.device).cuda_stream, L.OP_ESA_UNSHUFFLE, "esa")
+    y = _zeros_or(out, "esa_unshuffle: out", like, (n,) + lo, L.ESA_FP, 4)
+    d = L.EsaDesc()
+    descs.esa_unshuffle(d, (n, h, w), L.STORE[st], c1=_view(c1), w=keep.data_ptr(), f=weight.shape[0], y=_view(y), lo=lo)
+    _run(L.OP_ESA_UNSHUFFLE, d, c1, None)
     return y
 
 
@@ -955,7 +808,7 @@ def bsconv(x, pw_weight, pw_bias, dw_weight, dw_bias, *, act=L.ACT_NONE, slope=0
         yd = _zeros_or(d_out, "bsconv: d_out", x, (n, h, w), (dco + 3) // 4 * 4, 4)
         d.d_packed, d.d_cout, d.d_act, d.d_out = ctypes.c_void_p(keep[2].data_ptr()), dco, d_act, _view(yd)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_bsconv_f32", "esr_bsconv_f32", d, stream, L.OP_BSCONV, "bs")
+    _launch(L.OP_BSCONV, d, stream)
     return y if yd is None else (y, yd)
 
 
@@ -1045,7 +898,7 @@ def esa_apply(x, c1, c3, wf, bf, w4, b4, *, out=None, post=None, skip_y=False, p
             if t.get("res") is not None:
                 pp.res_mode, pp.res = L.RES_PRE_ACT, _view(t["res"])
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    _launch("esr_esa_apply_f32", "esr_esa_apply_f32", d, stream, L.OP_ESA_APPLY, "esa")
+    _launch(L.OP_ESA_APPLY, d, stream)
     return (y, outs) if post else y
 
 

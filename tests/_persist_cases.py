@@ -479,7 +479,7 @@ def block_tail(compute, n, hw, C, dc, f, esdb, period=None):
 
     def launch():
         with ops.kernel_trace() as names:
-            ops._launch("esr_conv2d_f32", "tail", d, st.value, L.OP_CONV, "conv")
+            ops._launch(L.OP_CONV, d, st.value, "tail")
         torch.cuda.synchronize()
         return names
 

@@ -387,7 +387,7 @@ def test_pack_input(store, n, h, w):
     channels [8, 24) of a pitch-32 buffer"""
     from ntire2022_esr_amd import _lib as L
     x = torch.rand(n, 3, h, w, generator=_gen(n, h, w, 3)) * 255
-    _property(_desc_case("esr_pack_input_s16", L.OP_PACK_INPUT, "conv", lambda t: _pack_desc(L, t, n, h, w, store), {"x": x},
+    _property(_desc_case(L.OP_PACK_INPUT, lambda t: _pack_desc(L, t, n, h, w, store), {"x": x},
                          {"slots": ((n, h, w, 32), DT[store], (-1, 8, 16))}, rf"pack_input_kernel<{'true' if store == 'bf16' else 'false'}>"))
 
 
@@ -410,8 +410,7 @@ def _head(store, n, h, w, cout, kernel, hilo=False, post=0):
             outs["p"] = ((n, h, w, _up(post, 8) + 8), dt, (-1, 0, _up(post, 8)))
 
         def launch(t):
-            ops._launch("esr_pack_input_s16", "esr_pack_input_s16", _pack_desc(L, t, n, h, w, store), torch.cuda.current_stream().cuda_stream,
-                        L.OP_PACK_INPUT, "conv")
+            ops._launch(L.OP_PACK_INPUT, _pack_desc(L, t, n, h, w, store), torch.cuda.current_stream().cuda_stream)
             kw = dict(cin=9, in_coff=8, out=t["y"], out_coff=0 if hilo else 8, hilo=L.HILO_OUT if hilo else 0)
             if post:
                 kw.update(post_weight=pw[0], post_bias=pw[1], post_act=1, post_out=t["p"])
@@ -536,7 +535,7 @@ def _tails(store, n, h, w, esdb, widths):
             if esdb:
                 d.border_bias = keep[3].data_ptr()
             assert L.lib().esr_conv_tail_supported(ctypes.byref(d)) == 1
-            ops._launch("esr_conv2d_f32", "esr_conv2d_f32", d, torch.cuda.current_stream().cuda_stream, L.OP_CONV, "conv")
+            ops._launch(L.OP_CONV, d, torch.cuda.current_stream().cuda_stream)
         return Case({"r3": r3, "ds": ds}, outs, launch, r"rfdb_tail_kernel<")
     _property(make)
 
@@ -654,12 +653,12 @@ def test_bsconv(store, n, h, w):
     _property(make)
 
 
-def _desc_case(fn, kind, field, build, ins, outs, kernel):
+def _desc_case(kind, build, ins, outs, kernel):
     from ntire2022_esr_amd import ops
 
     def make(variant):
         def launch(t):
-            ops._launch(fn, fn, build(t), torch.cuda.current_stream().cuda_stream, kind, field)
+            ops._launch(kind, build(t), torch.cuda.current_stream().cuda_stream)
         return Case(ins(variant) if callable(ins) else ins, outs, launch, kernel)
     return make
 
@@ -683,7 +682,7 @@ def test_dwconv(n, h, w):
         d.res = L.View(ctypes.c_void_p(t["r"].data_ptr()), 48, 0)
         d.wpacked = pk.data_ptr()
         return d
-    _property(_desc_case("esr_dwconv3x3_f32", L.OP_DWCONV, "conv", build, lambda v: {"x": _widen(x, 64, 8, v, 1), "r": r},
+    _property(_desc_case(L.OP_DWCONV, build, lambda v: {"x": _widen(x, 64, 8, v, 1), "r": r},
                          {"y": ((n, h, w, 64), torch.float32, (-1, 4, 48))}, r"dwconv3x3_kernel<0>"))
 
 
@@ -712,9 +711,9 @@ def test_esa_conv3x3s2_and_pools(store, n, h, w):
             d.w0 = pk.data_ptr()
             return d
         return build
-    _property(_desc_case("esr_conv3x3s2_f32", L.OP_CONV3X3S2, "esa", desc(h, w, h2, w2, L.STORE[store]), {"x": x},
+    _property(_desc_case(L.OP_CONV3X3S2, desc(h, w, h2, w2, L.STORE[store]), {"x": x},
                          {"y": ((n, h2, w2, 16), torch.float32, "all")}, r"conv3x3s2_kernel<"))
-    _property(_desc_case("esr_maxpool7s7_f32", L.OP_MAXPOOL7S7, "esa", desc(h, w, h7, w7, L.STORE[store]), {"x": x},
+    _property(_desc_case(L.OP_MAXPOOL7S7, desc(h, w, h7, w7, L.STORE[store]), {"x": x},
                          {"y": ((n, h7, w7, 16), torch.float32, "all")}, r"esa_pool7_kernel<"))
 
 
@@ -731,7 +730,7 @@ def test_esa_maxpool7s3(n, h, w):
         d.n, d.h, d.w, d.c, d.f, d.h_lo, d.w_lo, d.storage = n, h, w, 0, f, h3, w3, 0
         d.x, d.y = L.View(ctypes.c_void_p(t["x"].data_ptr()), 16, 0), L.View(ctypes.c_void_p(t["y"].data_ptr()), 16, 0)
         return d
-    _property(_desc_case("esr_maxpool7s3_f32", L.OP_MAXPOOL7S3, "esa", build, {"x": x}, {"y": ((n, h3, w3, 16), torch.float32, "all")}, r"maxpool7s3_kernel"))
+    _property(_desc_case(L.OP_MAXPOOL7S3, build, {"x": x}, {"y": ((n, h3, w3, 16), torch.float32, "all")}, r"maxpool7s3_kernel"))
 
 
 def _lowres_desc(L, t, n, h, w, f, storage, blobs, s2):
@@ -774,7 +773,7 @@ def test_esa_lowres(store, n, h, w, s2):
     blobs = _lowres_blobs(f, g)
     ho, wo = (((h - 3) // 2 + 1 - 7) // 3 + 1, ((w - 3) // 2 + 1 - 7) // 3 + 1) if s2 else ((h - 5) // 7 + 1, (w - 5) // 7 + 1)
     outs = {"pooled": ((n, ho, wo, 16), torch.float32, "all"), "y": ((n, ho, wo, 16), torch.float32, "all")}
-    _property(_desc_case("esr_esa_lowres_f32", L.OP_ESA_LOWRES, "lo", lambda t: _lowres_desc(L, t, n, h, w, f, L.STORE[store], blobs, s2), {"x": x}, outs,
+    _property(_desc_case(L.OP_ESA_LOWRES, lambda t: _lowres_desc(L, t, n, h, w, f, L.STORE[store], blobs, s2), {"x": x}, outs,
                          r"esa_s2pool(16)?_kernel<\d> \+ esa_chain_kernel" if s2 else r"esa_pool7_kernel<\d> \+ esa_pool7_branch_kernel"))
 
 

@@ -285,8 +285,7 @@ def test_tie_pairs_through_the_store(store):
     d.n, d.h, d.w, d.cin, d.storage = 1, ph, pw, 3, L.STORE[store]
     d.inp = L.View(ctypes.c_void_p(xin.data_ptr()), 0, 0)
     d.out0 = L.View(ctypes.c_void_p(slots.data_ptr()), 16, 0)
-    _, name = _traced(rf"pack_input_kernel<{_bf(store)}>", lambda: ops._launch("esr_pack_input_s16", "esr_pack_input_s16", d, torch.cuda.current_stream().cuda_stream,
-                                                                              L.OP_PACK_INPUT, "conv"))
+    _, name = _traced(rf"pack_input_kernel<{_bf(store)}>", lambda: ops._launch(L.OP_PACK_INPUT, d, torch.cuda.current_stream().cuda_stream))
     got = slots.cpu()
     f = planes.permute(0, 2, 3, 1)
     hi = f.to(dt)
@@ -525,7 +524,7 @@ def test_depthwise_kernels(store):
                 d.res = L.View(ctypes.c_void_p(rd.data_ptr()), c, 0)
                 d.wpacked = pk.data_ptr()
                 stream = torch.cuda.current_stream().cuda_stream
-                _, name = _traced(rf"dwconv3x3_kernel<{L.STORE[store]}>", lambda: ops._launch("esr_dwconv3x3_f32", "esr_dwconv3x3_f32", d, stream, L.OP_DWCONV, "conv"))
+                _, name = _traced(rf"dwconv3x3_kernel<{L.STORE[store]}>", lambda: ops._launch(L.OP_DWCONV, d, stream))
                 label = f"dwconv3x3 {store} {wkind} {ACT_NAME[act]} res{res_mode}"
                 conv = x.float() if wkind == "identity" else torch.zeros(n, h, w, c)
                 if act == GELU:
@@ -774,7 +773,7 @@ def test_rfdb_tail(store, form):
     c1 = torch.full((n, h, w, 16), 7.0, dtype=dt, device=DEV)
     d = _tail_desc(L, store, (n, h, w), cp, nf, dc, f, act, r3d, dsd, v, c1, blobs, table)
     _, name = _traced(rf"rfdb_tail_kernel<{_bf(store)}, {'3, true' if esdb else '4, false'}>",
-                      lambda: ops._launch("esr_conv2d_f32", "tail", d, torch.cuda.current_stream().cuda_stream, L.OP_CONV, "conv"))
+                      lambda: ops._launch(L.OP_CONV, d, torch.cuda.current_stream().cuda_stream, "tail"))
     refs = []
     for flush in (False, True):
         op = _flush if flush else (lambda t: t)                   # every MFMA operand: r3 for c4, r4 and d1 for c5 (v is summed from them in fp32)
