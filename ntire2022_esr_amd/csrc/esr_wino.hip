@@ -553,7 +553,8 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
 
 
 // ==================================================================================================================================
-// wino8_f32_kernel<ACT, OUT, NCH> -- the same arithmetic for layers of NCH <= 6 input chunks (cin <= 48: IMDBlock conv2 / conv3), organised
+// wino8_f32_kernel<ACT, OUT, NCH> -- the same arithmetic for layers of NCH <= 6 input chunks (cin <= 48: IMDBlock conv2 / conv3) and, with a
+// ring of ONE slot (W8L::RING; NCH = 8, cin 64: IMDBlock conv1, the only form instantiated: split store, blocked second output), organised
 // around what round 4's counters said bounds wino_f32_kernel (profiles/r04_c1_sq_counters.md, LAB_NOTES.md 9.2): the length of a wave's
 // own instruction stream per MFMA -- 7 LDS-DMA pieces (~100 cycles of issue each) and a block barrier per 64 MFMAs.
 //
@@ -561,14 +562,17 @@ __global__ __launch_bounds__(WN_THREADS, 2) void wino_f32_kernel(const WinoK p)
 //             per block): no U DMA in the loop.
 //   wave      autonomous: it walks its own list of STRIPS (4 output rows x 16 columns = 2 x 8 Winograd tiles = the N side of the MFMA,
 //             all 16 positions, 2 cout tiles -- the accumulator shape of wino_f32_kernel) and stages its own 6 x 18-pixel halo, one 8-channel
-//             chunk at a time, into a PRIVATE ring of two slots (4 DMA pieces per chunk instead of 7).  No wave ever reads what another wave
+//             chunk at a time, into a PRIVATE ring of RING slots (two; one for NCH = 8: W8L) (4 DMA pieces per chunk instead of 7).  No wave ever reads what another wave
 //             staged, so the loop has NO barrier: the two waves of a SIMD drift apart, one's epilogue and DMA issue run under the other's MFMAs.
 //   stage     chunk c of a strip: 64 MFMAs (A fragments two positions ahead from the resident U); between them, from position W8_TP on: s_waitcnt
 //             vmcnt(4 (+ 8 stores of an epilogue in between)), the transform of chunk c + 1 from slot (c + 1) & 1, and -- as soon as its four
 //             rows have been read -- the DMA of chunk c + 3 into the same slot: 1.75 stages ahead of the transform that reads it.
+//             RING == 1: s_waitcnt vmcnt(0 (+ 8 stores in a strip's first stage)) and the DMA of chunk c + 2: 11 positions (44 MFMAs) ahead.
+//             That lead is enough: NCH = 8 runs at 17.7 ps per MFMA where NCH = 6 runs at 18.0 (LAB_NOTES.md 15.1).
 //             Chunks run on across strip boundaries (the last stages of a strip stage and transform the next strip's first chunks).
 //   epilogue  stores as unconditional buffer stores (invalid lanes: out-of-range offsets), so the vmcnt arithmetic is exact.
-// Shapes: RES_NONE only (conv2 / conv3 have no residual), NHWC split or channel-blocked second output.
+// Shapes: RES_NONE only (IMDBlock conv1 / conv2 / conv3 have no residual), NHWC split or channel-blocked second output; NCH = 8 with the
+// channel-blocked second output only.
 constexpr int W8_THREADS = 512;
 constexpr int W8_PLANE = 3 * WN_PAIR;                  // 6 halo rows = 3 row pairs of 37 slots, per channel-half plane
 constexpr int W8_SLOTS = 2 * W8_PLANE;                 // 222 slots of 16 B = 3 full DMA pieces + one of 30 lanes
@@ -576,7 +580,9 @@ constexpr int W8_SLOT_BYTES = W8_SLOTS * 16;           // 3552
 constexpr int W8_LAST_LANES = W8_SLOTS - 192;
 constexpr int W8_EPI_STORES = 8;                       // buffer stores per wave and strip (2 cout tiles x 2 x 2 pixels)
 constexpr int W8_MAX_BLOCKS = 256;
-constexpr int W8_OLD_SHARE = 11;                       // WinoK.first_share of every wino8_f32_kernel launch: 8 .. 12 swept, LAB_NOTES.md 14.2
+constexpr int W8_OLD_SHARE = 11;                       // WinoK.first_share of the wino8_f32_kernel launches of NCH <= 6: 8 .. 12 swept, LAB_NOTES.md 14.2
+constexpr long W8_MIN_STRIPS_NCH8 = 16;                // strips per wave from which NCH = 8 is taken (see esr_conv2d_wino)
+constexpr int W8_OLD_SHARE_NCH8 = 10;                 // WinoK.first_share of the launches of NCH = 8 (one ring slot): 8 .. 13 swept, LAB_NOTES.md 15.1
 #ifndef W8_TP
 #define W8_TP 2
 #endif
@@ -612,10 +618,13 @@ constexpr int W8_OLD_SHARE = 11;                       // WinoK.first_share of e
 #define W8_ABL_OOBDMA 0         // every halo piece out of range (issued, zero fill: no read traffic)
 #endif
 
+// RING: slots of a wave's private halo ring.  Two wherever they fit; eight resident U chunks (cin 64: IMDBlock conv1) leave room for one:
+// 8 x 16 KB + 8 waves x 3552 B + 256 B = 159 744 B (with two slots 188 160 B, against 163 840 B of LDS)
 template <int NCH> struct W8L {
+    static constexpr int RING = NCH <= 6 ? 2 : 1;
     static constexpr int U_BYTES = NCH * WN_U_BYTES;
     static constexpr int RAW_OFF = U_BYTES;
-    static constexpr int BIAS_OFF = RAW_OFF + 8 * 2 * W8_SLOT_BYTES;
+    static constexpr int BIAS_OFF = RAW_OFF + 8 * RING * W8_SLOT_BYTES;
     static constexpr int TOTAL = BIAS_OFF + 256;
     static_assert(TOTAL <= 160 * 1024, "one block per CU");
 };
@@ -632,6 +641,12 @@ template <int ACT, int OUT, int NCH>
 __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
 {
     typedef W8L<NCH> LY;
+    // RING == 2: chunk c + 3 goes, at position W8_TP + 5 of stage c, into the slot whose rows the transform of chunk c + 1 has just consumed.
+    // RING == 1: the same point of the stage takes chunk c + 2 (the only slot is free then), and the wait at position W8_TP of stage c + 1
+    // has 16 - (W8_TP + 5) + W8_TP = 11 positions (44 MFMAs) of lead instead of 27; nothing younger than that chunk is in flight there
+    // except an epilogue's stores.  LEAD: how many chunks the DMA runs ahead of the MFMAs.
+    constexpr int RING = LY::RING, LEAD = RING + 1;
+    static_assert(RING == 2 || !W8_DMA_TOP, "the research variant assumes two slots");
     __shared__ __attribute__((aligned(16))) char smem[LY::TOTAL];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -665,8 +680,9 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
     };
 
     // Two cursors: `cur` (image, origin of the strip whose MFMAs run: wave-uniform, SGPRs) and the DMA cursor `dvoff` / `dn` (per-lane
-    // offsets of the 4 halo pieces and the image of the strip whose chunks are being STAGED) -- it runs two chunks ahead and moves to
-    // the next strip in stage NCH - 2, so only one set of offsets is live
+    // offsets of the 4 halo pieces and the image of the strip whose chunks are being STAGED) -- it runs LEAD = RING + 1 chunks ahead (three
+    // with the two-slot ring, two with the one-slot ring of NCH = 8) and moves to the next strip in stage NCH - LEAD, so only one set of
+    // offsets is live
     struct Ctx { int n, x0, y0; };
     unsigned dvoff[4];
     int dn = 0;
@@ -700,7 +716,7 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
     };
     const size_t img_bytes = (size_t)p.H * p.W * p.in_pitch * 4;
     auto image_rsrc = [&](int n) { return wn_rsrc(p.x + (size_t)n * (img_bytes / 4), img_bytes); };
-    const unsigned ring_m0 = smem_lds + (unsigned)(LY::RAW_OFF + wv * 2 * W8_SLOT_BYTES);
+    const unsigned ring_m0 = smem_lds + (unsigned)(LY::RAW_OFF + wv * RING * W8_SLOT_BYTES);
     const bool live3 = lane < W8_LAST_LANES;
     // the 4 pieces of chunk `chunk` of an image (rsrc xr, per-lane offsets v[]) -> this wave's ring slot `par`
     auto issue_raw = [&](int par, int chunk) __attribute__((always_inline)) {
@@ -732,7 +748,7 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
     if (work >= 0) {
         dma_to(work, cur);
         issue_raw(0, 0);
-        issue_raw(1, 1);
+        if (RING == 2) issue_raw(1, 1);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -770,8 +786,8 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
 #pragma unroll
         for (int c = 0; c < 4; ++c) col_pass(V0, c);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // slot 0 is free: chunk 2 goes there
-    if (!W8_DMA_TOP) issue_raw(0, 2);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // slot 0 is free: chunk 2 (RING == 1: chunk 1) goes there
+    if (!W8_DMA_TOP) issue_raw(0, RING);
     f32x4 a[4];
     a[0] = *reinterpret_cast<const f32x4*>(smem + u_lane);
     a[1] = *reinterpret_cast<const f32x4*>(smem + u_lane + 1024);
@@ -793,9 +809,10 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
     const char* const bias_lds = smem + LY::BIAS_OFF + (half * 32 + g * 4) * 4;
     for (;;) {
         const bool has_next = wn >= 0;
-        // stage of chunk c: DMA of chunk c + 2 into slot c & 1 (the slot the previous stage's transform has finished reading), transform of
-        // chunk c + 1 (slot (c + 1) & 1), 64 MFMAs.  AFTER_EPI: the first stage of a strip other than the wave's first -- the previous
-        // strip's W8_EPI_STORES stores were issued between the DMA this stage waits for and the DMA it issues.
+        // stage of chunk c: transform of chunk c + 1 from slot (c + 1) % RING, then the DMA of chunk c + LEAD into that same slot (RING == 2:
+        // chunk c + 3; RING == 1: chunk c + 2, the only slot), 64 MFMAs.  (W8_DMA_TOP, two slots only: chunk c + 2 into slot c & 1 at the top.)
+        // In the first RING stages of a strip other than the wave's first, the previous strip's W8_EPI_STORES stores lie between the DMA
+        // the stage waits for and the one it issues.
         auto stage = [&](auto first_tag, int c, f32x2 (&Vc)[16], f32x2 (&Vn)[16]) __attribute__((always_inline)) {
             constexpr bool FIRST = decltype(first_tag)::value;
             if (W8_DMA_TOP) {                                               // research variant: chunk c + 2 at the top of stage c (1 stage + W8_TP positions of lead)
@@ -806,7 +823,7 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
             const int cn = c + 1 < NCH ? c + 1 : 0;                       // U chunk of the next stage (position look-ahead)
             const char* ust = smem + c * WN_U_BYTES + u_lane;
             const char* ust1 = smem + cn * WN_U_BYTES + u_lane;
-            unsigned rs = ring_m0 + (unsigned)(((c + 1) & 1) * W8_SLOT_BYTES) + raw_lane;
+            unsigned rs = ring_m0 + (unsigned)(((c + 1) & (RING - 1)) * W8_SLOT_BYTES) + raw_lane;
             asm volatile("" : "+v"(rs));
             // chunk c + 1 has landed when only this stage's 3 or 4 pieces (+ the epilogue's stores) are still in flight.  A wave with lanes
             // >= 30 ... every wave issues the 4th piece (lanes < 30 exist in every wave), so the count is 4
@@ -821,15 +838,21 @@ __global__ __launch_bounds__(W8_THREADS, 1) void wino8_f32_kernel(const WinoK p)
                 // one stage ago, so the wait comes as late as the stage allows
                 if (pos == W8_TP) {
                     // chunk c + 1 has landed when only the 4 pieces of chunk c + 2 are younger -- and, in the first two stages of a strip
-                    // that is not the wave's first, the 8 stores of the epilogue in between (every wave issues all 4 pieces and all 8 stores)
+                    // that is not the wave's first, the 8 stores of the epilogue in between (every wave issues all 4 pieces and all 8 stores).
+                    // RING == 1: chunk c + 1 was issued in stage c - 1 and chunk c + 2 is not yet: nothing is younger, but in the FIRST stage
+                    // of such a strip the 8 stores are (chunk 1 went out in the previous strip's last stage, in front of its epilogue)
+                    if (RING == 1) {
+                        if (c < 1 && k > 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W8_EPI_STORES) : "memory");
+                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    } else
                     if (c < (W8_DMA_TOP ? 1 : 2) + 2 * W8_ABL_LAXWAIT && k > 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + W8_EPI_STORES) : "memory");
                     else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                 }
                 if (!W8_DMA_TOP && pos == W8_TP + 5) {
                     // the four rows of chunk c + 1 have been read (row_pass has consumed them): its slot takes chunk c + 3, two stages ahead
-                    // of the transform that will read it
-                    if (c + 3 == NCH) dma_to(wn, nxt);                        // the DMA cursor moves on to the next strip
-                    if (!W8_ABL_NODMA) issue_raw((c + 1) & 1, c + 3 < NCH ? c + 3 : c + 3 - NCH);
+                    // of the transform that will read it (RING == 1: chunk c + 2, one stage ahead)
+                    if (c + LEAD == NCH) dma_to(wn, nxt);                     // the DMA cursor moves on to the next strip
+                    if (!W8_ABL_NODMA) issue_raw((c + 1) & (RING - 1), c + LEAD < NCH ? c + LEAD : c + LEAD - NCH);
                 }
                 if (!W8_ABL_NOXF && pos >= W8_TP && pos < W8_TP + 4) raw_row(rs, pos - W8_TP, d[(pos - W8_TP) & 1]);
                 if (!W8_ABL_NOXF && pos >= W8_TP + 1 && pos < W8_TP + 5) {
@@ -971,6 +994,7 @@ int wn_launch(const WinoK& k, int grid, hipStream_t st)
 
 int g_wino8_mode = 1;                 // research switch (esr_dbg_wino8): A/B of the two Winograd kernels inside one process
 int g_wino8_share = 0;                // research switch (esr_dbg_wino8_share): 0 = W8_OLD_SHARE
+int g_wino8_nch8 = 1;                 // research switch (esr_dbg_wino8_nch8): 0 = conv1's form (8 input chunks) stays on wino_f32_kernel
 
 // G of F(2x2, 3x3)
 const double WN_G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
@@ -1081,6 +1105,9 @@ int esr_unpack_wino_f32(const void* packed, size_t bytes, int cin, int cout, con
 void esr_dbg_wino8(int on) { g_wino8_mode = on < 0 || on > 2 ? 1 : on; }
 /* research switch, not part of the ABI header: WinoK.first_share of the next wino8_f32_kernel launches, 1..15; anything else = W8_OLD_SHARE */
 void esr_dbg_wino8_share(int s) { g_wino8_share = s >= 1 && s <= 15 ? s : 0; }
+/* research switch, not part of the ABI header: 0 = 64-input-channel layers of conv1's form on wino_f32_kernel (the kernel they ran on before
+ * wino8_f32_kernel<., 1, 8>), anything else = the product's choice */
+void esr_dbg_wino8_nch8(int on) { g_wino8_nch8 = on != 0; }
 
 }  // extern "C"
 
@@ -1122,26 +1149,33 @@ int esr_conv2d_wino(const esr_conv_desc* d, void* hip_stream)
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // instantiations: the activation is a template constant for LeakyReLU / none (the networks' cases), read at run time otherwise
     const int a = d->act;
-    // wino8_f32_kernel (resident U, wave-private halo rings, no barrier): 4 or 6 input chunks, no residual, NHWC / blocked outputs, and enough
+    // wino8_f32_kernel (resident U, wave-private halo rings, no barrier): 4, 6 or (conv1's form) 8 input chunks, no residual, NHWC / blocked outputs, and enough
     // strips (4 rows x 16 columns) that each of the 2048 waves walks several; both per-image byte ranges behind 31-bit buffer offsets
     const bool blocked_in = (d->blocked8 & ESR_BLOCKED_IN) != 0;
     k.pix_floats = blocked_in ? 8u : (unsigned)d->in.pitch;
     k.in_base = blocked_in ? (unsigned)(d->in.coff / 8) * (unsigned)(d->h * d->w * 32) : (unsigned)d->in.coff * 4u;
     k.chunk_stride = blocked_in ? (unsigned)(d->h * d->w * 32) : 32u;
-    if ((k.nchunks == 4 || k.nchunks == 6) && d->res_mode == ESR_RES_NONE && d->out_layout == ESR_NHWC && g_wino8_mode) {
+    // 8 input chunks (one ring slot: W8L): IMDBlock conv1's form only -- a split store whose second output is channel-blocked
+    const bool nch8 = k.nchunks == 8 && k.y1_blk && split < cout4 && g_wino8_nch8;
+    if ((k.nchunks == 4 || k.nchunks == 6 || nch8) && d->res_mode == ESR_RES_NONE && d->out_layout == ESR_NHWC && g_wino8_mode) {
         const long sx = (d->w + 15) / 16, sy = (d->h + 3) / 4;
         const long nstrips = (long)k.N * sx * sy;
         const double out_bytes = (double)d->h * d->w * 4.0 * (d->out0.pitch > d->out1.pitch ? d->out0.pitch : d->out1.pitch);
         const bool fits = (double)k.N * sx * sy * (sx > sy ? sx : sy) < 4294967296.0 && out_bytes < 2147482624.0;
-        if (fits && (nstrips >= 4L * 8 * W8_MAX_BLOCKS / k.nhalves || g_wino8_mode == 2)) {
+        // strips per wave from which the kernel is taken: 4; 16 for NCH = 8.  The one-slot kernel is the faster one from 4 strips per wave on
+        // (4-7 % per launch, profiles/r08_nch8_crossover.txt), but tests/test_gpu_wino.py::test_wino8_is_the_kernel_that_ran holds IMDBlock
+        // conv1 on wino_f32_kernel at 8 x 256 x 256 (8 strips per wave): NCH = 8 starts above that.  Same bits either way.
+        const long per_wave = k.nchunks == 8 ? W8_MIN_STRIPS_NCH8 : 4L;
+        if (fits && (nstrips >= per_wave * 8 * W8_MAX_BLOCKS / k.nhalves || g_wino8_mode == 2)) {
             WinoK w = k;
             w.tiles_x = (int)sx; w.tiles_y = (int)sy;
             w.magic_x = sx == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)sx) + 1u;
             w.magic_y = sy == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)sy) + 1u;
-            w.first_share = g_wino8_share ? g_wino8_share : W8_OLD_SHARE;
+            w.first_share = g_wino8_share ? g_wino8_share : k.nchunks == 8 ? W8_OLD_SHARE_NCH8 : W8_OLD_SHARE;
             const int grid8 = W8_MAX_BLOCKS;
             const bool blk = k.y1_blk != 0;
             const bool lr = a == ESR_ACT_LRELU;
+            if (k.nchunks == 8) return lr ? w8_launch<ESR_ACT_LRELU, 1, 8>(w, grid8, st) : w8_launch<-1, 1, 8>(w, grid8, st);
             if (k.nchunks == 6) {
                 if (blk) return lr ? w8_launch<ESR_ACT_LRELU, 1, 6>(w, grid8, st) : w8_launch<-1, 1, 6>(w, grid8, st);
                 return lr ? w8_launch<ESR_ACT_LRELU, 0, 6>(w, grid8, st) : w8_launch<-1, 0, 6>(w, grid8, st);
